@@ -14,7 +14,10 @@ end-to-end in tests/test_lp_configs.py; configs[2] has a ~0.86 TB factor).  At N
 sharded by diagonal blocks over N ranks ("strong" scaling); the linking-block Schur complement is
 all-reduced with RCCL (torch.distributed, backend nccl).
 
-Prints ONE JSON line on rank 0, with
+A plain run sets up, warms up, times exactly `--steps` Newton steps once, writes the outputs of the last
+timed step if `--dump-outputs DIR` is given, and prints ONE JSON line on rank 0 (`metric`, `value`, `unit`,
+`ms_per_step`, `higher_is_better`, `dtype`, `config`, ...).  `--full` adds everything else below: the
+timed region run `--repeats` (3) times with the median reported, the residual check of the last step, and
   roofline      dominant kernel (fp64-MFMA panel update k_update): ALGORITHMIC flops (the share of
                 sum_j l_j^2 that falls to that kernel, tlpk_stats.flops_update_alg) / its summed launch
                 durations, timed live with HIP events on the library's stream; `frac_executed` is the
@@ -26,6 +29,12 @@ Prints ONE JSON line on rank 0, with
   headline      the north-star instance (1e6 vars / 2e6 constraints block-angular) on the same GPU.
   cpu_baseline  CHOLMOD-class CPU path (oracle/k1_supernodal.c: supernodal multifrontal on OpenBLAS,
                 OpenMP over the elimination tree, ALL host cores) on the same LP, same ordering.
+  (and the unpaired step, the c3 and small-LP legs and the committed multi-GPU projection).
+
+--dump-outputs DIR writes what a caller of the timed step receives after the last timed step, as float64
+DIR/<name>.npy: dx, dy (the last solve) and, when the step solves a pair, dx2, dy2 (the pair's first
+right-hand side).  The inputs are seeded, so two builds given the same arguments can be compared output for
+output.  Beyond DUMP_BYTES in all, every array is cut to the same fixed, seeded sample of its entries.
 """
 import argparse
 import json
@@ -41,6 +50,7 @@ sys.path.insert(0, ROOT)
 FP64_MFMA_PEAK_TFLOPS = 78.6     # MI355X datasheet fp64 matrix peak (not tabulated in the guide;
                                  # = 32 flop/clk/SIMD x 1024 SIMD x 2.4 GHz); see DESIGN.md
 HBM_PEAK_GBS = 8000.0
+DUMP_BYTES = 64_000_000          # --dump-outputs: at most this many bytes of .npy files in all
 
 
 def parse():
@@ -75,10 +85,16 @@ def parse():
                          "factorisation overlaps the first solve's block-level sweeps; measured slower, profiles/r03_async_update.txt)")
     ap.add_argument("--no-small-lp", action="store_true", help="skip the latency-bound legs (25fv47-class and pds-20-class LPs)")
     ap.add_argument("--no-c3", action="store_true", help="skip the general sparse leg (BASELINE configs[2] shape at --c3-rows rows; N=1, workload c4 only)")
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the repeats of the timed region, the residual check, the roofline / "
+                         "per-kernel leg, the host-ABI and unpaired steps, the north-star, c3 and small-LP legs, the CPU comparator and the "
+                         "projection (the --no-* options switch single legs off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the vectors the last timed step computed as float64 DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (exactly --steps Newton steps between two barriers) is run this many times back to back; `ms_per_step` / "
                          "`value` are the MEDIAN run, all runs are listed in `ms_per_step_runs` (round-4 review: the box-to-box spread of the "
-                         "pool, +-0.7 ms, exceeded what a round gained)")
+                         "pool, +-0.7 ms, exceeded what a round gained).  Default 3 with --full, else 1")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="target CPU time of the cpu_baseline sample")
     ap.add_argument("--no-third-party", action="store_true", help="skip the SciPy splu point (BASELINE.md B2) of the cpu_baseline leg")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)   # child-process mode of the cpu_baseline leg
@@ -86,7 +102,24 @@ def parse():
                     help="N = 1 only: run the multi-GPU code path (process group on backend nccl = RCCL, split-phase calls, all-reduce of "
                          "the root panel / root rhs ordered with the library stream by events) with a world of one rank -- the branch the "
                          "8-GPU scaling run takes, exercised on a single-GPU box")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    return args
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each {name: 1-d vector} as float64 DIR/<name>.npy.  If they exceed DUMP_BYTES together, every vector keeps
+    the same share of its entries, at sorted indices drawn without replacement by numpy.random.default_rng(0) for its length --
+    fixed for given arguments, so two builds are compared on the same entries."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.size for a in arrays.values())
+    cap = (DUMP_BYTES - 1024 * len(arrays)) // 8                    # entries that fit, room for the .npy headers aside
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if total > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, size=a.size * cap // total, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def host_info():
@@ -346,8 +379,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(workload, steps, warmup, roofline, repeats=1):
-        """Times `steps` Newton steps of `workload` (`repeats` times: the median run is reported); returns (result dict, A, row_block)."""
+    def run(workload, steps, warmup, roofline, repeats=1, dump=None):
+        """Times `steps` Newton steps of `workload` (`repeats` times: the median run is reported); returns (result dict, A, row_block).
+        dump: directory for the outputs of the last timed step (--dump-outputs)."""
         A, row_block, text = build_workload(args, workload)
         m, n = A.shape
         kkt = tk.setup(A, tk.K1(), tk.Backend(device=local_rank, row_block=row_block, rank=rank, nranks=world))
@@ -442,17 +476,25 @@ def main():
             runs.append(1e3 * elapsed / steps)
         ms_per_step = float(np.median(runs))
 
-        # sanity: the residual identities of the reference's conformance test on the last step
-        dx, dy = d_dx.cpu().numpy(), d_dy.cpu().numpy()
-        if dist is not None:       # block rows / columns live on their owner; linking rows replicated
-            t1, t2 = d_dx.clone(), d_dy.clone()
+        def gather(t_x, t_y):
+            # the whole vectors on the host: block rows / columns live on their owner; linking rows replicated
+            if dist is None:
+                return t_x.cpu().numpy(), t_y.cpu().numpy()
+            t1, t2 = t_x.clone(), t_y.clone()
             dist.all_reduce(t1)
             lk = torch.from_numpy((row_block < 0)).to(dev)   # world > 1 implies a block-angular workload
             t2 = torch.where(lk, t2 / world, t2)
             dist.all_reduce(t2)
-            dx, dy = t1.cpu().numpy(), t2.cpu().numpy()
-        r_p = float(np.abs(A @ dx + rd * dy - xp).max())
-        r_d = float(np.abs(-dx * (th + rp) + A.T @ dy - xd).max())
+            return t1.cpu().numpy(), t2.cpu().numpy()
+
+        if args.full or dump:
+            dx, dy = gather(d_dx, d_dy)
+        if dump:                   # what the last timed step handed its caller, before any other leg reuses the buffers
+            outputs = {"dx": dx, "dy": dy}
+            if pair:
+                outputs["dx2"], outputs["dy2"] = gather(d_dx2, d_dy2)
+            if rank == 0:
+                dump_outputs(dump, outputs)
 
         out = {"ms_per_step": ms_per_step, "value": 1e3 / ms_per_step, "ms_per_step_runs": [round(r, 4) for r in runs],
                "config": {"workload": text, "solves_per_step": args.solves, "regime": args.regime,
@@ -464,9 +506,13 @@ def main():
                           "stored_over_nnzL": st["nnzL_stored"] / max(st["nnzL"], 1), "device_bytes": st["device_bytes"],
                           "flops_chol": st["flops_chol"], "n_supernodes": st["n_supernodes"], "n_levels": st["n_levels"],
                           "max_front": st["max_front"], "launches_update": st["launches_update"],
-                          "launches_solve": st["launches_solve"], "ms_analyse": st["ms_analyse"],
-                          "residual_inf": [r_p, r_d]},
+                          "launches_solve": st["launches_solve"], "ms_analyse": st["ms_analyse"]},
                "frac_step": st["flops_chol"] / (ms_per_step * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS}
+        if args.full:
+            # sanity: the residual identities of the reference's conformance test on the last step
+            r_p = float(np.abs(A @ dx + rd * dy - xp).max())
+            r_d = float(np.abs(-dx * (th + rp) + A.T @ dy - xd).max())
+            out["config"]["residual_inf"] = [r_p, r_d]
 
         def roofline_leg():
                 # Per-kernel-class device time of one Newton step, HIP events around every launch on the
@@ -544,7 +590,7 @@ def main():
                 out["roofline"] = None
                 out["roofline_error"] = repr(e)
 
-        if world == 1 and not split and not args.no_host_abi:
+        if args.full and world == 1 and not split and not args.no_host_abi:
             # The drop-in path: what the Julia glue calls (host pointers in, host pointers out, blocking).
             dxh, dyh = np.empty(n), np.empty(m)
             def host_step():
@@ -563,7 +609,7 @@ def main():
                                "note": "tlpk_update + %d x tlpk_solve with pageable host vectors through pinned staging (pieces of <= 512 KB handled by "
                                        "a pool of host threads, every piece on the link as soon as it is staged); "
                                        "PCIe-inclusive, never reported as `value`" % args.solves}
-        if pair and world == 1 and not split:
+        if args.full and pair and world == 1 and not split:
             # the same step with every right-hand side solved on its own (the round-2 definition of the step), for comparison
             def unpaired_step():          # the round-2 definition of the step: blocking update!, four single solves
                 kkt.update_device(P(d_th), P(d_rp), P(d_rd))
@@ -584,7 +630,8 @@ def main():
 
     # The roofline leg (a second, single-stream-group handle in profile mode) is measured at N = 1 only: with ranks it would run
     # collectives on a handle the timed loop never used, and a rank failing there would leave the others waiting in an all-reduce.
-    res, A, row_block = run(args.workload, args.steps, args.warmup, (not args.no_roofline) and not split, args.repeats)
+    res, A, row_block = run(args.workload, args.steps, args.warmup, args.full and (not args.no_roofline) and not split, args.repeats,
+                            args.dump_outputs)
     out = {
         "metric": "IPM Newton-step rate: KKT.update! (A*D*A'+Rd, supernodal Cholesky) + %d KKT.solve!" % args.solves,
         "value": res["value"], "unit": "iter/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -595,7 +642,7 @@ def main():
     }
     # definition of the timed step, spelled out (round-3 advisor finding: the default changed from four single solves to a pair + two in round 3)
     out["value_definition"] = ("1 KKT.update! + %d right-hand sides per step; since round 3 the first two are solved as ONE pair (HSD's h-system + predictor, "
-                               "one pass over the factor) -- `unpaired_ms_per_step` is the same step with %d single solves (the round-1/2 definition), "
+                               "one pass over the factor) -- with --full, `unpaired_ms_per_step` is the same step with %d single solves (the round-1/2 definition), "
                                "`host_abi.ms_per_step` the drop-in path with host vectors over PCIe; the timed region (exactly `steps` steps between two barriers) is run "
                                "%d times, `ms_per_step` / `value` are the median run, `ms_per_step_runs` lists all" % (args.solves, args.solves, max(1, args.repeats))) if not args.unpaired else \
                               ("1 KKT.update! + %d single KKT.solve! per step (the round-1/2 definition)" % args.solves)
@@ -613,7 +660,7 @@ def main():
         out["roofline_error"] = res["roofline_error"]
     if split and world == 1:
         out["collectives"] = "forced at N = 1: process group on backend nccl (RCCL), split-phase update / solve with all-reduce of the root panel and the root rhs"
-    if rank == 0 and world == 1 and not split and args.workload == "c4" and not args.no_headline:
+    if args.full and rank == 0 and world == 1 and not split and args.workload == "c4" and not args.no_headline:
         try:
             hres, _, _ = run("headline", max(2, min(args.steps, 5)), 1, not args.no_roofline, min(3, max(1, args.repeats)))
             out["headline"] = {"ms_per_step": hres["ms_per_step"], "ms_per_step_runs": hres["ms_per_step_runs"], "value": hres["value"], "unit": "iter/s",
@@ -632,7 +679,7 @@ def main():
                 out["headline"]["cpu_baseline"] = hc
         except Exception as e:          # the headline leg must never cost the main line
             out["headline"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not split and args.workload == "c4" and not args.no_c3:
+    if args.full and rank == 0 and world == 1 and not split and args.workload == "c4" and not args.no_c3:
         # BASELINE configs[2] (general sparse LP, one supernodal tree ending in a dense front): as specified (5e5 rows) the factor is
         # ~0.43 TB packed -- beyond one GPU (memory gate, tests/test_gpu_parity.py::test_memory_gate); the same generator at a size that keeps
         # the default run short, with its own rooflines.  The largest run of the shape is builder-side: 2e5 rows, 160 GB on the device.
@@ -649,7 +696,7 @@ def main():
                     out["c3"][k] = cres[k]
         except Exception as e:
             out["c3"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not split and args.workload == "c4" and not args.no_small_lp:
+    if args.full and rank == 0 and world == 1 and not split and args.workload == "c4" and not args.no_small_lp:
         # The small configs (BASELINE configs[1], configs[4] classes): a Newton step here is bound by launch latency and the
         # serial chain of diagonal blocks, not by the matrix cores -- reported as measured, next to the CPU comparator.
         out["small_lp"] = {}
@@ -676,7 +723,7 @@ def main():
                 out["small_lp"][wl] = leg
             except Exception as e:
                 out["small_lp"][wl] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not split and not args.no_cpu_baseline and args.workload not in ("c3", "stair25", "pds"):
+    if args.full and rank == 0 and world == 1 and not split and not args.no_cpu_baseline and args.workload not in ("c3", "stair25", "pds"):
         out["cpu_baseline"] = cpu_baseline_subprocess(args)
         if "value" in out["cpu_baseline"]:
             out["cpu_baseline"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
@@ -699,7 +746,7 @@ def main():
     out["config"]["drop_in_ms_per_step"] = drop_in
     out["config"]["headline_ms_per_step"] = h.get("ms_per_step")
     out["config"]["headline_drop_in_ms_per_step"] = summary["headline_drop_in_ms_per_step"]
-    if world == 1 and not split:
+    if args.full and world == 1 and not split:
         try:        # multi-GPU: no node has been available to measure on; the committed projection (rank-local times measured on one GPU + modelled reductions), labelled as such
             pj = json.load(open(os.path.join(ROOT, "profiles", "scale_projection.json")))
             out["projected"] = pj

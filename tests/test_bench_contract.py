@@ -20,7 +20,7 @@ def run_bench(*flags, timeout=900):
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    d = run_bench("--steps", "2", "--warmup", "1", "--no-headline", "--no-cpu-baseline", "--no-small-lp")
+    d = run_bench("--full", "--steps", "2", "--warmup", "1", "--no-headline", "--no-cpu-baseline", "--no-small-lp")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "solve_roofline", "host_abi", "kernel_ms"):
         assert k in d, k
@@ -43,8 +43,31 @@ def test_bench_line_contract():
 
 
 @pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps once and runs no other leg; --dump-outputs writes the vectors of the last
+    timed step, which solve the seeded system the bench generated (rebuilt here on the host)."""
+    import numpy as np
+    from workloads import block_angular_lp, kernel_inputs
+    d = run_bench("--steps", "3", "--warmup", "1", "--blocks", "4", "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and len(d["ms_per_step_runs"]) == 1 and d["ms_per_step_runs"][0] == pytest.approx(d["ms_per_step"], rel=1e-3)
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-9 * d["value"] and d["unit"] == "iter/s" and d["dtype"] == "f64"
+    for k in ("roofline", "host_abi", "unpaired_ms_per_step", "headline", "c3", "small_lp", "cpu_baseline", "projected"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ["dx.npy", "dx2.npy", "dy.npy", "dy2.npy"]
+    A, _ = block_angular_lp(4, 5000, 10000, 1000, 4, 0.5)
+    m, n = A.shape
+    th, rp, rd, xp, xd = kernel_inputs(m, n, 7, "mid")
+    for sx, sy in (("dx", "dy"), ("dx2", "dy2")):
+        dx, dy = np.load(tmp_path / (sx + ".npy")), np.load(tmp_path / (sy + ".npy"))
+        assert dx.dtype == np.float64 and dx.shape == (n,) and dy.shape == (m,)
+        assert np.abs(A @ dx + rd * dy - xp).max() <= 1e-6 and np.abs(-dx * (th + rp) + A.T @ dy - xd).max() <= 1e-6
+
+
+@pytest.mark.gpu
 def test_bench_cpu_baseline_leg():
-    d = run_bench("--steps", "2", "--warmup", "1", "--no-headline", "--no-host-abi", "--no-roofline", "--no-small-lp")
+    d = run_bench("--full", "--steps", "2", "--warmup", "1", "--no-headline", "--no-host-abi", "--no-roofline", "--no-small-lp")
     c = d["cpu_baseline"]
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, (k, c)
@@ -60,7 +83,7 @@ def test_bench_cpu_baseline_leg():
 @pytest.mark.gpu
 def test_bench_small_lp_legs():
     """The latency-bound configs (25fv47 class, pds-20 class): GPU step, host-ABI step and the CPU comparator, with the statement."""
-    d = run_bench("--steps", "2", "--warmup", "1", "--no-headline", "--no-roofline", "--no-host-abi", "--blocks", "4")
+    d = run_bench("--full", "--steps", "2", "--warmup", "1", "--no-headline", "--no-roofline", "--no-host-abi", "--blocks", "4")
     for wl in ("stair25", "pds"):
         leg = d["small_lp"][wl]
         assert "error" not in leg, leg
@@ -73,8 +96,8 @@ def test_bench_multi_gpu_branch_with_a_world_of_one():
     """The branch the 8-GPU scaling run takes -- process group on backend nccl (= RCCL), split-phase update / solve, all-reduce of
     the root panel and the root right-hand side on torch's stream ordered with the library stream by events -- executed with one
     rank on this box's single GPU: same step, same residuals as the plain N = 1 path."""
-    a = run_bench("--steps", "2", "--warmup", "1", "--no-headline", "--no-cpu-baseline", "--no-small-lp", "--no-roofline", "--no-host-abi", "--blocks", "8")
-    b = run_bench("--steps", "2", "--warmup", "1", "--blocks", "8", "--force-collectives")
+    a = run_bench("--full", "--steps", "2", "--warmup", "1", "--no-headline", "--no-cpu-baseline", "--no-small-lp", "--no-roofline", "--no-host-abi", "--blocks", "8")
+    b = run_bench("--full", "--steps", "2", "--warmup", "1", "--blocks", "8", "--force-collectives")
     assert "collectives" in b and b["n_gpus"] == 1
     assert max(b["config"]["residual_inf"]) <= 1e-6 and max(a["config"]["residual_inf"]) <= 1e-6
     assert b["ms_per_step"] < 3 * a["ms_per_step"] + 5.0                     # no host round trips hidden in the collective path

@@ -7,12 +7,10 @@ B="python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-hea
 for cfg in "0 1" "2 1" "2 8" "1 1" "2 4"; do
   set -- $cfg
   export TLPK_UPD_REMAP=$1 TLPK_UPD_SUPER=$2
-  timeout 300 python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-headline --no-host-abi > gpurun_out/remap_$1_$2.json 2> gpurun_out/remap_$1_$2.err
-  python - "$1" "$2" <<'P'
-import json,sys
-d=json.loads(open(f"gpurun_out/remap_{sys.argv[1]}_{sys.argv[2]}.json").read().strip().splitlines()[-1])
-print("remap",sys.argv[1],"super",sys.argv[2],"ms/step", round(d["ms_per_step"],2), "update", d["kernel_ms"]["update"], "frac", round(d["roofline"]["frac"],4))
-P
+  timeout 300 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-headline --no-host-abi 2>/dev/null | python -c "
+import sys, json
+d = json.loads(sys.stdin.read().strip().splitlines()[-1])
+print('remap', $1, 'super', $2, 'ms/step', round(d['ms_per_step'], 2), 'update', d['kernel_ms']['update'], 'frac', round(d['roofline']['frac'], 4))"
 done
 for cfg in "0 1" "2 8"; do
   set -- $cfg
