@@ -72,11 +72,23 @@ typedef struct tlpk_options {
     int32_t keep_on_too_large; /* 1: tlpk_create returns a LIVE analyse-only handle together with TLPK_TOO_LARGE (tlpk_info / tlpk_last_error then describe what did not
                                   fit; the caller must destroy it).  0 (default): no handle on any failure -- the message is in tlpk_last_create_error() */
     int64_t max_link_rows;     /* detect_blocks: most linking rows to accept; 0 = max(64, m / 20) */
+    /* Dense (linking) columns, K1 only.  A column of A with c entries puts a c x c clique into A*D*A'.  With dense_cols = 1 the
+     * columns that qualify stay out of A*D*A' and become k extra nodes of a partially augmented, symmetric quasi-definite system
+     *     [ A_s D_s A_s' + Rd    A_d            ] [ dy   ]   [ xi_p + A_s D_s xi_d_s ]
+     *     [ A_d'                 -(Theta_d^-1 + Rp_d) ] [ dx_d ] = [ xi_d_d                ]
+     * of order m + k, factorised by the signed Cholesky of K2 (the k nodes last / in the root front); dx_s = D_s (A_s' dy - xi_d_s).
+     * The caller still solves K1: same vectors, same results (up to rounding), refinement allowed.  Refused with K2, nranks > 1 and
+     * tlpk_create_multi (TLPK_BADARG). */
+    int32_t dense_cols;        /* 0 = off (default): every column is formed into A*D*A'; 1 = qualifying columns become augmented nodes */
+    int32_t max_dense_cols;    /* cap on k; 0 = 1024.  More qualifying columns: the densest are taken (ties: lower index), the rest stay in A*D*A' */
+    int64_t dense_col_min;     /* a column with MORE than this many entries qualifies; 0 = 1000 */
+    const int64_t *col_dense;  /* optional, length n: nonzero = this column qualifies whatever its count (e.g. first-stage variables);
+                                  like row_block, only meaningful on the matrix the caller analyses (no presolve in between) */
 } tlpk_options;
 
 typedef struct tlpk_stats {
     int64_t m, n, nnzA;
-    int64_t nnzS;              /* lower triangle of A*D*A' + Rd, incl. diagonal */
+    int64_t nnzS;              /* lower triangle of A*D*A' + Rd, incl. diagonal (dense_cols: of the order-(m + k) matrix) */
     int64_t nnzL;              /* nnz of the Cholesky factor (incl. diagonal) */
     int64_t nnzL_stored;       /* doubles stored in supernodal panels (>= nnzL) */
     double  flops_chol;        /* sum_j l_j^2 (CHOLMOD `fl` convention) */
@@ -106,6 +118,8 @@ typedef struct tlpk_stats {
     double  flops_update_chain;     /* round 6: the share of flops_update / flops_update_alg whose tiles run as items of the dependency-driven launches */
     double  flops_update_alg_chain; /* (k_chain: fronts with more than one block column on levels with few such fronts) instead of in k_update launches */
     int64_t chain_launches, chain_items;   /* number of those launches per factorisation and the items (update tiles, diagonal blocks, solve strips, reductions) they hold */
+    int64_t n_dense_cols;      /* k: columns of A handled as augmented nodes (tlpk_options.dense_cols); tlpk_symbolic_get(h, "dense_cols") lists them.
+                                  m, n, nnzA are the caller's; nnzS, nnzL, n_pairs, fail_col, ... describe the factored matrix of order m + k */
 } tlpk_stats;
 
 /* per-kernel-class timing, filled when options.profile = 1 */
@@ -131,7 +145,7 @@ void tlpk_default_options(tlpk_options *opt);
  * A is copied; nothing is retained.  Runs the whole analyse phase and uploads the symbolic
  * structures.  Does NOT perform the throw-away numeric factorisation of spd.jl:14-17.
  * Return value != TLPK_OK: *out = NULL and tlpk_last_create_error() holds the diagnostic (for TLPK_TOO_LARGE: the bytes needed against the
- * budget, and -- K1 with a dense column of A -- the hint that KKT_System = K2 does not form A*D*A').  Only with opt->keep_on_too_large = 1 does
+ * budget, and -- K1 with a dense column of A -- the hint that KKT_System = K2 does not form A*D*A', or that K1 with dense_cols = 1 does not either).  Only with opt->keep_on_too_large = 1 does
  * TLPK_TOO_LARGE return a live analyse-only handle (tlpk_info: symbolic nnz(L) ...), which the caller destroys. */
 int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr,
                 const int64_t *rowval, const double *nzval, int index_base,
@@ -228,7 +242,8 @@ int tlpk_kernel_timing(const tlpk_handle *h, tlpk_kernel_times *out);
 int tlpk_set_profile(tlpk_handle *h, int on);   /* toggle per-launch HIP-event timing at run time; while on, the
                                                    stream groups are serialised on the main stream so that the
                                                    per-kernel durations are not inflated by overlap */
-int tlpk_get_perm(const tlpk_handle *h, int64_t *perm /*m, 0-based, perm[new] = old*/);
+int tlpk_get_perm(const tlpk_handle *h, int64_t *perm /*m, 0-based, perm[new] = old*/);   /* dense_cols: the constraint nodes in their order
+                                                   (the whole order-(m + k) permutation: tlpk_symbolic_get(h, "perm"), node m + t = dense column t) */
 /* Symbolic structures, for tests and tools.  `what` selects an array; returns its length and,
  * if buf != NULL, copies min(len, cap) int64 entries. */
 int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, int64_t cap);

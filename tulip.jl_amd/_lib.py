@@ -27,7 +27,8 @@ class Options(C.Structure):
                 ("nranks", C.c_int32), ("streams", C.c_int32),
                 ("user_perm", p64), ("row_block", p64), ("mem_budget_bytes", C.c_int64),
                 ("system", C.c_int32), ("refine_steps", C.c_int32),
-                ("detect_blocks", C.c_int32), ("keep_on_too_large", C.c_int32), ("max_link_rows", C.c_int64)]
+                ("detect_blocks", C.c_int32), ("keep_on_too_large", C.c_int32), ("max_link_rows", C.c_int64),
+                ("dense_cols", C.c_int32), ("max_dense_cols", C.c_int32), ("dense_col_min", C.c_int64), ("col_dense", p64)]
 
 
 class Stats(C.Structure):
@@ -40,7 +41,8 @@ class Stats(C.Structure):
                 ("ms_last_solve", C.c_double), ("n_local_blocks", C.c_int32), ("n_blocks", C.c_int32),
                 ("root_panel_len", C.c_int64), ("flops_update", C.c_double),
                 ("flops_update_alg", C.c_double), ("ms_enqueue_update", C.c_double), ("refine_rejected", C.c_int64),
-                ("flops_update_chain", C.c_double), ("flops_update_alg_chain", C.c_double), ("chain_launches", C.c_int64), ("chain_items", C.c_int64)]
+                ("flops_update_chain", C.c_double), ("flops_update_alg_chain", C.c_double), ("chain_launches", C.c_int64), ("chain_items", C.c_int64),
+                ("n_dense_cols", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

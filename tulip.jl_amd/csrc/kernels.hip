@@ -4199,6 +4199,50 @@ __global__ void k_k2_out(i64 N, i64 n, const i32 *__restrict__ perm, const char 
 }
 
 // ------------------------------------------------------------------------------------------
+// K1 with dense columns (tlpk_options.dense_cols): [A_s D_s A_s' + Rd, A_d; A_d', -(Theta_d^-1 + Rp_d)] of order mu + k, node mu + t =
+// column dense_col[t]; factorised by the signed instances (csign), solved with k_apply_signs between the sweeps.  The kernels below
+// read the caller's full A (K1 layout) and skip the dense columns by the mask sparse_col.
+// ------------------------------------------------------------------------------------------
+// D = [sparse j: 1 / (theta + regP), dense j: theta + regP ; 1]: what the assembly lists refer to (symbolic.cpp step 14: a dense node's
+// diagonal is -1 * D[j], a border entry A[i,j] * D[n])
+__global__ void k_dense_diag(i64 n, const char *__restrict__ sparse_col, const double *__restrict__ theta, const double *__restrict__ regP,
+                             double *__restrict__ D) {
+    const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) { const double t = theta[j] + regP[j]; D[j] = sparse_col[j] ? 1.0 / t : t; }
+    else if (j == n) D[j] = 1.0;
+}
+// permuted right-hand side: constraint node i: xi_p[i] + sum_j A[i,j] w_j (w = D .* xi_d on the sparse columns, 0 on the dense ones:
+// k_rhs_scale with the mask); dense node mu + t: xi_d of its column.  Tp / Tj / Tx: the CSR copy with the rows in permuted order (a dense
+// node's row is empty).  8 lanes per row, fixed shuffle tree (k_rhs); grid y = right-hand side of a pair.
+__global__ __launch_bounds__(256) void k_dense_rhs(i64 N, i64 mu, const i32 *__restrict__ perm, const i64 *__restrict__ Tp,
+                                                   const i32 *__restrict__ Tj, const double *__restrict__ Tx, const double *__restrict__ w,
+                                                   const i32 *__restrict__ dense_col, const double *__restrict__ xi_p,
+                                                   const double *__restrict__ xi_d, double *__restrict__ xw, const double *__restrict__ xi_p1,
+                                                   const double *__restrict__ xi_d1, i64 w2, i64 xw2) {
+    if (blockIdx.y) { xi_p = xi_p1; xi_d = xi_d1; w += w2; xw += xw2; }
+    const i64 ii = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 3;
+    const int lane = threadIdx.x & 7;
+    const bool live = ii < N;
+    const i64 q0 = live ? Tp[ii] : 0, q1 = live ? Tp[ii + 1] : 0;
+    const i32 i = live ? perm[ii] : 0;
+    double s = 0.0;
+    for (i64 q = q0 + lane; q < q1; q += 8) s += Tx[q] * w[Tj[q]];
+#pragma unroll
+    for (int off = 4; off > 0; off >>= 1) s += __shfl_down(s, off, 8);
+    if (live && lane == 0) xw[ii] = (i < mu) ? xi_p[i] + s : xi_d[dense_col[i - mu]];
+}
+// [dy ; dx_d] = P' x  (dx_s follows from dy: k_dx with the mask; local_only = 1 leaves dx_d alone)
+__global__ void k_dense_out(i64 N, i64 mu, const i32 *__restrict__ perm, const i32 *__restrict__ dense_col, const double *__restrict__ xw,
+                            double *__restrict__ dy, double *__restrict__ dx, i64 xw2, double *__restrict__ dy1, double *__restrict__ dx1) {
+    if (blockIdx.y) { xw += xw2; dy = dy1; dx = dx1; }
+    const i64 kk = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (kk >= N) return;
+    const i32 v = perm[kk];
+    if (v < mu) dy[v] = xw[kk];
+    else dx[dense_col[v - mu]] = xw[kk];
+}
+
+// ------------------------------------------------------------------------------------------
 // host-side launchers
 // ------------------------------------------------------------------------------------------
 static inline unsigned nblk(i64 n, int b) { return (unsigned)((n + b - 1) / b); }
@@ -4380,6 +4424,23 @@ void launch_apply_signs(hipStream_t st, const DevArrays &a, int rhs) {
 void launch_k2_out(hipStream_t st, const DevArrays &a, i64 n, double *dx, double *dy, int rhs, int rank, int owned_only) {
     if (a.m > 0) hipLaunchKernelGGL(k_k2_out, dim3(nblk(a.m, 256)), dim3(256), 0, st, a.m, n, a.perm, a.row_local, rank, owned_only, a.ctx.xw + (rhs ? a.ctx.xw2 : 0), dx, dy);
 }
+void launch_dense_diag(hipStream_t st, const DevArrays &a, const double *theta, const double *regP, double *D) {
+    hipLaunchKernelGGL(k_dense_diag, dim3(nblk(a.n + 1, 256)), dim3(256), 0, st, a.n, a.sparse_col, theta, regP, D);
+}
+void launch_dense_rhs(hipStream_t st, const DevArrays &a, const double *D, const double *const *xi_p, const double *const *xi_d, int nrhs) {
+    if (a.m <= 0) return;
+    if (a.n > 0) hipLaunchKernelGGL(k_rhs_scale, dim3(nblk(a.n, 256), (unsigned)nrhs), dim3(256), 0, st, a.n, D, xi_d[0], a.sparse_col, a.rhs_w, xi_d[1]);
+    hipLaunchKernelGGL(k_dense_rhs, dim3(nblk(a.m * 8, 256), (unsigned)nrhs), dim3(256), 0, st, a.m, a.mu, a.perm, a.Pp, a.Pj, a.Px, a.rhs_w, a.dense_col,
+                       xi_p[0], xi_d[0], a.ctx.xw, xi_p[1], xi_d[1], a.n, a.ctx.xw2);
+}
+void launch_dense_out(hipStream_t st, const DevArrays &a, const double *D, double *const *dy, const double *const *xi_d, double *const *dx, int nrhs) {
+    if (a.m > 0)
+        hipLaunchKernelGGL(k_dense_out, dim3(nblk(a.m, 256), (unsigned)nrhs), dim3(256), 0, st, a.m, a.mu, a.perm, a.dense_col, a.ctx.xw, dy[0], dx[0],
+                           a.ctx.xw2, dy[1], dx[1]);
+    if (a.n > 0)
+        hipLaunchKernelGGL(k_dx, dim3(nblk(a.n, 256), (unsigned)nrhs), dim3(256), 0, st, a.n, a.Ap, a.Ai, a.Ax, D, dy[0], xi_d[0], a.sparse_col, dx[0], 1,
+                           dy[1], xi_d[1], dx[1]);
+}
 void launch_rhs(hipStream_t st, const DevArrays &a, const double *D, const double *xi_p, const double *xi_d, int rank, int rhs) {
     if (a.m > 0)
     {
@@ -4424,7 +4485,7 @@ void launch_unpermute(hipStream_t st, const DevArrays &a, double *dy, double *dy
 }
 void launch_residuals(hipStream_t st, const DevArrays &a, const double *xi_p, const double *xi_d, const double *theta, const double *regP,
                       const double *regD, const double *dx, const double *dy, double *r1, double *r2, int rank, int xip_all) {
-    if (a.m > 0) hipLaunchKernelGGL(k_resid_rows, dim3(nblk(a.m, 256)), dim3(256), 0, st, a.m, a.Tp, a.Tj, a.Tx, xi_p, regD, dx, dy, a.row_local, rank, xip_all, r1);
+    if (a.mu > 0) hipLaunchKernelGGL(k_resid_rows, dim3(nblk(a.mu, 256)), dim3(256), 0, st, a.mu, a.Tp, a.Tj, a.Tx, xi_p, regD, dx, dy, a.row_local, rank, xip_all, r1);
     if (a.n > 0) hipLaunchKernelGGL(k_resid_cols, dim3(nblk(a.n, 256)), dim3(256), 0, st, a.n, a.Ap, a.Ai, a.Ax, xi_d, theta, regP, dx, dy, r2);
 }
 void launch_publish(hipStream_t st, const DevArrays &a, const double *dx, double *dx_job, const double *dy, double *dy_job) {
@@ -4436,8 +4497,8 @@ void launch_axpy2(hipStream_t st, i64 n, double *x, const double *dxc, i64 m, do
     if (len > 0) hipLaunchKernelGGL(k_axpy2, dim3(nblk(len, 256)), dim3(256), 0, st, n, x, dxc, m, y, dyc);
 }
 void launch_absmax2(hipStream_t st, const DevArrays &a, const double *r1, const double *r2, unsigned long long *out, int owned_only) {
-    const i64 len = a.m + a.n;
-    if (len > 0) hipLaunchKernelGGL(k_absmax2, dim3((unsigned)std::min<i64>(nblk(len, 256), 1024)), dim3(256), 0, st, a.m, r1, owned_only ? a.row_local : nullptr,
+    const i64 len = a.mu + a.n;
+    if (len > 0) hipLaunchKernelGGL(k_absmax2, dim3((unsigned)std::min<i64>(nblk(len, 256), 1024)), dim3(256), 0, st, a.mu, r1, owned_only ? a.row_local : nullptr,
                                     a.n, r2, owned_only ? a.col_local : nullptr, out);
 }
 void launch_refine_decide(hipStream_t st, unsigned long long *ref) { hipLaunchKernelGGL(k_refine_decide, dim3(1), dim3(1), 0, st, ref); }

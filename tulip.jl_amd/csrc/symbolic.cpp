@@ -400,18 +400,34 @@ int analyse_common(Symbolic &S, i64 m64, i64 n64, const i64 *colptr, const i64 *
     std::vector<i32> order0;
     order0.reserve(m);
     std::vector<char> is_link(m, 0);
+    // dense-column nodes (analyse_dense, general path): the constraint nodes [0, mc) are ordered as the K1 matrix of A_s alone -- the subgraph
+    // without the dense nodes --, the dense nodes follow as the forced root front (is_link)
+    const i32 mc = m - (i32)opt.n_dense;
+    auto append_dense = [&]() { for (i32 v = mc; v < m; ++v) { order0.push_back(v); is_link[v] = 1; ++nlink; } };
     if (opt.ordering == TLPK_ORDER_USER) {
         if (!opt.user_perm) return fail(S, TLPK_BADARG, "user_perm is null");
-        std::vector<char> seen(m, 0);
-        for (i32 i = 0; i < m; ++i) {
+        std::vector<char> seen(mc, 0);
+        for (i32 i = 0; i < mc; ++i) {
             const i64 v = opt.user_perm[i];
-            if (v < 0 || v >= m || seen[v]) return fail(S, TLPK_BADARG, "user_perm is not a permutation");
+            if (v < 0 || v >= mc || seen[v]) return fail(S, TLPK_BADARG, "user_perm is not a permutation");
             seen[v] = 1; order0.push_back((i32)v);
         }
         if (opt.row_block) return fail(S, TLPK_BADARG, "user_perm cannot be combined with row_block");
+        append_dense();
     } else if (!opt.row_block) {
-        if (opt.ordering == TLPK_ORDER_NATURAL) { order0.resize(m); std::iota(order0.begin(), order0.end(), 0); }
-        else amd_order(m, xadj, adj, order0);
+        if (opt.ordering == TLPK_ORDER_NATURAL) { order0.resize(mc); std::iota(order0.begin(), order0.end(), 0); }
+        else if (mc == m) amd_order(m, xadj, adj, order0);
+        else {
+            std::vector<i64> cx((size_t)mc + 1, 0);
+            std::vector<i32> ca;
+            ca.reserve((size_t)xadj[mc]);
+            for (i32 v = 0; v < mc; ++v) {
+                for (i64 p = xadj[v]; p < xadj[v + 1]; ++p) if (adj[p] < mc) ca.push_back(adj[p]);
+                cx[(size_t)v + 1] = (i64)ca.size();
+            }
+            amd_order(mc, cx, ca, order0);
+        }
+        append_dense();
     } else {
         // each diagonal block on its own (blocks are mutually non-adjacent in S); linking rows last
         std::vector<std::vector<i32>> members(nblocks);
@@ -1204,6 +1220,9 @@ int analyse_rank(Symbolic &S, const Options &opt) {
         // products: cache-resident) and appends the column to its own stream; the counts go to pair_ptr.  After the prefix sum every column is ONE contiguous
         // copy from its thread's stream to its final place.  The lists are the lists of the two-pass version, entry by entry (tests/test_symbolic.py: digests).
         const unsigned nthreads = host_threads(ns_total);
+        // K1 with dense columns: constraint nodes [0, dense_m); the incidence matrix's columns [0, dense_n) are A's (the dense ones empty)
+        const i32 dense_m = S.n_dense > 0 ? m - (i32)S.n_dense : -1;
+        const i32 dense_n = (i32)S.dense_n;
         struct Stream { std::vector<double> w; std::vector<i32> j; std::vector<i32> le, cj, start; std::vector<double> cw; std::vector<i32> pos_in_front; std::vector<i64> epos; };
         std::vector<Stream> st(nthreads);
         uvec<i64> col_off((size_t)m);                     // per pivot column: offset of its products in the stream of ...
@@ -1229,6 +1248,7 @@ int analyse_rank(Symbolic &S, const Options &opt) {
                         S.s_local[e] = 1;
                     }
                     if (opt.system == 1) { if (k >= opt.k2_n && (!is_root || opt.rank == 0)) S.s_diag_row[e0] = k - (i32)opt.k2_n; }   // constraint node: regD
+                    else if (dense_m >= 0) { if (k < dense_m) S.s_diag_row[e0] = k; }                                        // dense node: no regD
                     else if (!is_root || opt.rank == 0) S.s_diag_row[e0] = k;
                     T.le.clear(); T.cw.clear(); T.cj.clear();
                     T.start.assign((size_t)ne + 1, 0);
@@ -1250,6 +1270,22 @@ int analyse_rank(Symbolic &S, const Options &opt) {
                                     if (ii <= kk) continue;
                                     emit(epos[ii], akj * S.Ax[p], (i32)opt.k2_n);
                                 }
+                            }
+                        }
+                    } else if (dense_m >= 0) {
+                        // K1 with dense columns; D = [sparse j: 1 / (theta + regP), dense j: theta + regP ; 1] (kernels.hip: k_dense_diag).
+                        //   constraint node: the products A[i,j] A[k,j] D_j of the SPARSE columns (columns [0, dense_n) of the incidence matrix; a dense
+                        //   column is empty there) and the border entries A[i,j] = A[i,j] * D[dense_n] of the incidence columns (A[i,j] on row i, 1 on node
+                        //   m + t); dense node m + t: -1 * D[dense_cols[t]] on the diagonal (its border entries come from the constraint nodes, ordered before it)
+                        if (k >= dense_m) emit(e0, -1.0, (i32)S.dense_cols[(size_t)(k - dense_m)]);
+                        for (i64 q = S.Tp[k]; q < S.Tp[k + 1]; ++q) {
+                            const i32 j = S.Tj[q];
+                            const double akj = S.Ax[S.Tpos[q]];
+                            const bool incidence = j >= dense_n;
+                            for (i64 p = S.Ap[j]; p < S.Ap[j + 1]; ++p) {
+                                const i32 ii = S.iperm[S.Ai[p]];
+                                if (incidence ? ii <= kk : ii < kk) continue;
+                                emit(epos[ii], akj * S.Ax[p], incidence ? dense_n : j);
                             }
                         }
                     } else {
@@ -1393,6 +1429,90 @@ int analyse_k2(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowval, 
     Options opt;
     const int rc = analyse_k2_common(S, m, n, colptr, rowval, nzval, base, opt_in, &opt);
     return rc != TLPK_OK ? rc : analyse_rank(S, opt);
+}
+
+// ---------------------------------------------------------------------------------------------
+// K1 with dense columns (tlpk_options.dense_cols): [A_s D_s A_s' + Rd, A_d; A_d', -(Theta_d^-1 + Rp_d)] of order m + k.  Its graph is
+// that of B B' for the incidence matrix B (m + k rows) whose first n columns are A's with the dense ones emptied (constraint nodes: the
+// pattern of A_s A_s') and whose further columns hold one entry A[i,j] of dense column j = dense[t] each: A[i,j] on row i, 1 on node m + t
+// (the dense node is adjacent to the rows of its column, no clique).  The dense nodes go last (general path: behind the AMD order of the
+// constraint nodes; block path: block -1, the root front), carry the sign -1 and are factorised by the signed instances of K2; step 14
+// builds the assembly lists of this layout.  Afterwards S.Ap ... hold A itself: the solve, refinement and device-resident kernels read the
+// caller's full A in K1 layout.
+// ---------------------------------------------------------------------------------------------
+int analyse_dense(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowval, const double *nzval,
+                  int base, const Options &opt_in, const std::vector<i64> &dense) {
+    if (m < 0 || n < 0 || (base != 0 && base != 1) || !colptr) return fail(S, TLPK_BADARG, "bad dimensions or index base");
+    if (opt_in.nranks != 1) return fail(S, TLPK_BADARG, "dense_cols: one rank only");
+    const i64 k = (i64)dense.size(), nnz = colptr[n] - base;
+    if (nnz < 0 || m + k >= ((i64)1 << 31) || n >= ((i64)1 << 31) || nnz >= ((i64)1 << 30)) return fail(S, TLPK_TOO_LARGE, "m + dense columns or nnz(A) exceeds int32");
+    if (nnz > 0 && (!rowval || !nzval)) return fail(S, TLPK_BADARG, "null rowval/nzval");
+    for (i64 j = 0; j < n; ++j)
+        if (colptr[j] - base < 0 || colptr[j + 1] < colptr[j] || colptr[j + 1] - base > nnz) return fail(S, TLPK_BADARG, "colptr not monotone");
+    std::vector<char> isd((size_t)n, 0);
+    i64 nnz_d = 0;
+    for (i64 t = 0; t < k; ++t) {
+        const i64 j = dense[(size_t)t];
+        if (j < 0 || j >= n || (t > 0 && j <= dense[(size_t)t - 1])) return fail(S, TLPK_INTERNAL, "dense columns not ascending");
+        isd[(size_t)j] = 1; nnz_d += colptr[j + 1] - colptr[j];
+    }
+    const i64 nb = n + nnz_d;
+    if (nb >= ((i64)1 << 31)) return fail(S, TLPK_TOO_LARGE, "incidence matrix exceeds int32");
+    std::vector<i64> bp((size_t)nb + 1), bi; std::vector<double> bx;
+    bi.reserve((size_t)(nnz + nnz_d)); bx.reserve((size_t)(nnz + nnz_d));
+    for (i64 j = 0; j < n; ++j) {
+        bp[(size_t)j] = (i64)bi.size();
+        if (isd[(size_t)j]) continue;
+        for (i64 p = colptr[j] - base; p < colptr[j + 1] - base; ++p) {
+            const i64 r = rowval[p] - base;
+            if (r < 0 || r >= m) return fail(S, TLPK_BADARG, "row index out of range");
+            bi.push_back(r); bx.push_back(nzval[p]);
+        }
+    }
+    i64 col = n;
+    for (i64 t = 0; t < k; ++t) {
+        const i64 j = dense[(size_t)t];
+        for (i64 p = colptr[j] - base; p < colptr[j + 1] - base; ++p) {
+            const i64 r = rowval[p] - base;
+            if (r < 0 || r >= m) return fail(S, TLPK_BADARG, "row index out of range");
+            bp[(size_t)col++] = (i64)bi.size();
+            bi.push_back(r); bx.push_back(nzval[p]);                 // constraint node
+            bi.push_back(m + t); bx.push_back(1.0);                  // dense node
+        }
+    }
+    bp[(size_t)nb] = (i64)bi.size();
+    Options opt = opt_in;
+    opt.system = 0; opt.n_dense = k;
+    std::vector<i64> node_block;
+    if (opt_in.row_block) {                    // the dense nodes join the linking rows in the root front
+        node_block.assign((size_t)(m + k), -1);
+        std::copy(opt_in.row_block, opt_in.row_block + m, node_block.begin());
+        opt.row_block = node_block.data();
+    }
+    S.n_dense = k; S.dense_n = n; S.dense_cols = dense;
+    int rc = analyse_common(S, m + k, nb, bp.data(), bi.data(), bx.data(), 0, opt);
+    if (rc != TLPK_OK) return rc;
+    S.csign.resize((size_t)(m + k));
+    for (i64 kk = 0; kk < m + k; ++kk) S.csign[(size_t)kk] = (S.perm[(size_t)kk] >= m) ? -1.0 : 1.0;
+    opt.row_block = nullptr;                    // (points into a local; analyse_rank reads the copy inside S)
+    rc = analyse_rank(S, opt);
+    if (rc != TLPK_OK) return rc;
+    // the matrix kept for SpMV: A itself (CSC + CSR, the layout analyse_common builds for K1)
+    S.n = n; S.nnzA = nnz;
+    S.Ap.assign((size_t)n + 1, 0); S.Ai.resize((size_t)nnz); S.Ax.resize((size_t)nnz); S.Acol.resize((size_t)nnz);
+    for (i64 j = 0; j < n; ++j) {
+        S.Ap[(size_t)j + 1] = colptr[j + 1] - base;
+        for (i64 p = colptr[j] - base; p < colptr[j + 1] - base; ++p) { S.Ai[(size_t)p] = (i32)(rowval[p] - base); S.Ax[(size_t)p] = nzval[p]; S.Acol[(size_t)p] = (i32)j; }
+    }
+    S.Tp.assign((size_t)m + 1, 0); S.Tj.resize((size_t)nnz); S.Tpos.resize((size_t)nnz);
+    for (i64 p = 0; p < nnz; ++p) S.Tp[(size_t)S.Ai[(size_t)p] + 1]++;
+    for (i64 i = 0; i < m; ++i) S.Tp[(size_t)i + 1] += S.Tp[(size_t)i];
+    {
+        std::vector<i64> cur(S.Tp.begin(), S.Tp.end() - 1);
+        for (i64 p = 0; p < nnz; ++p) { const i64 q = cur[(size_t)S.Ai[(size_t)p]]++; S.Tj[(size_t)q] = S.Acol[(size_t)p]; S.Tpos[(size_t)q] = (i32)p; }
+    }
+    S.col_local.assign((size_t)n, 1);
+    return TLPK_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -239,6 +239,8 @@ int upload_all(tlpk_handle *h) {
     Symbolic &S = h->S;
     DevArrays &d = h->d;
     d.m = S.m; d.n = S.n;
+    d.mu = (S.system == 1) ? S.k2_m : S.m - S.n_dense;
+    const i64 mu = d.mu;
     int rc;
 #define UP(dst, vec) if ((rc = dev_upload(h, &(dst), (vec))) != TLPK_OK) return rc
     UP(d.Ap, S.Ap); UP(d.Ai, S.Ai); UP(d.Ax, S.Ax);
@@ -254,14 +256,24 @@ int upload_all(tlpk_handle *h) {
         // with the original row order each 8-lane group started with perm[ii] -> Tp[i] -> Tj[q] -> w[j], four dependent loads at scattered
         // addresses, 65 us = 0.6 TB/s on config C4; now Tp / Tj / Tx are streamed).  Entries keep their order inside a row: same sums.
         std::vector<i64> Pp((size_t)S.m + 1, 0);
-        for (i64 ii = 0; ii < S.m; ++ii) { const i32 i = S.perm[(size_t)ii]; Pp[(size_t)ii + 1] = Pp[(size_t)ii] + (S.Tp[(size_t)i + 1] - S.Tp[(size_t)i]); }
+        // (dense columns: the rows of the dense nodes, i >= mu, are empty)
+        for (i64 ii = 0; ii < S.m; ++ii) { const i32 i = S.perm[(size_t)ii]; Pp[(size_t)ii + 1] = Pp[(size_t)ii] + (i < mu ? S.Tp[(size_t)i + 1] - S.Tp[(size_t)i] : 0); }
         std::vector<i32> Pj((size_t)Pp[(size_t)S.m]); std::vector<double> Px((size_t)Pp[(size_t)S.m]);
         for (i64 ii = 0; ii < S.m; ++ii) {
             const i32 i = S.perm[(size_t)ii];
+            if (i >= mu) continue;
             i64 o = Pp[(size_t)ii];
             for (i64 q = S.Tp[(size_t)i]; q < S.Tp[(size_t)i + 1]; ++q, ++o) { Pj[(size_t)o] = S.Tj[(size_t)q]; Px[(size_t)o] = S.Ax[(size_t)S.Tpos[(size_t)q]]; }
         }
         UP(d.Pp, Pp); UP(d.Pj, Pj); UP(d.Px, Px);
+    }
+    if (S.n_dense > 0) {
+        std::vector<char> sc((size_t)S.n, 1);
+        for (i64 j : S.dense_cols) sc[(size_t)j] = 0;
+        UP(d.sparse_col, sc);
+        std::vector<i32> dc(S.dense_cols.begin(), S.dense_cols.end());
+        UP(d.dense_col, dc);
+        d.n_dense = S.n_dense;
     }
     UP(d.row_local, S.row_local); UP(d.col_local, S.col_local);
     {
@@ -358,7 +370,7 @@ int upload_all(tlpk_handle *h) {
     if (std::getenv("TLPK_POISON") && S.lval_len > 0) { HIPCHK(h, hipMemset(d.ctx.Lval, 0xFF, (size_t)S.lval_len * 8)); HIPCHK(h, hipDeviceSynchronize()); }
     AL(d.ctx.uc, 2 * S.uc_len); AL(d.ctx.xw, 2 * S.m); AL(d.ctx.info, 16);      // two copies: the second right-hand side of tlpk_solve2_device
     d.ctx.xw2 = S.m; d.ctx.uc2 = S.uc_len; AL(d.ctx.dinv, S.dinv_len); AL(d.ctx.spart, S.spart_len);
-    const i64 nn = std::max<i64>(S.n, S.k2_n + 1);             // K2: user vectors have k2_n entries, D2 one more
+    const i64 nn = std::max<i64>(S.n + (S.n_dense > 0 ? 1 : 0), S.k2_n + 1);   // K2: user vectors have k2_n entries, D2 one more; dense columns: D one more
     AL(h->d_theta, nn); AL(h->d_regP, nn); AL(h->d_regD, S.m); AL(h->d_D, nn);
     AL(h->d_xip, S.m); AL(h->d_xid, nn); AL(h->d_dx, nn); AL(h->d_dy, S.m);
     AL(d.rhs_w, std::max<i64>(2 * S.n, 1));
@@ -372,7 +384,7 @@ int upload_all(tlpk_handle *h) {
     d.ctx.small_full = std::getenv("TLPK_SMALL_FULL") ? std::atoi(std::getenv("TLPK_SMALL_FULL")) : 0;
     d.ctx.upd_remap = 2;
     if (const char *e = std::getenv("TLPK_UPD_REMAP")) d.ctx.upd_remap = std::atoi(e);      // tuning knob
-    if (S.system == 1) { double *p; if ((rc = dev_upload(h, &p, S.csign)) != TLPK_OK) return rc; d.ctx.csign = p; }
+    if (S.system == 1 || S.n_dense > 0) { double *p; if ((rc = dev_upload(h, &p, S.csign)) != TLPK_OK) return rc; d.ctx.csign = p; }      // signed Cholesky
 #undef AL
     {
         // persistent sweeps: one ticket counter per sweep launch, one hand-over word per column and direction
@@ -469,7 +481,7 @@ int graph_or_direct(tlpk_handle *h, const GraphKey &key, F &&body, bool usable) 
 
 // user-visible dimensions: for K2 the Symbolic describes the augmented matrix (order n + m)
 inline i64 user_n(const tlpk_handle *h) { return h->S.system == 1 ? h->S.k2_n : h->S.n; }
-inline i64 user_m(const tlpk_handle *h) { return h->S.system == 1 ? h->S.k2_m : h->S.m; }
+inline i64 user_m(const tlpk_handle *h) { return h->S.system == 1 ? h->S.k2_m : h->S.m - h->S.n_dense; }      // dense columns: S.m = m + k
 
 }  // namespace
 
@@ -515,6 +527,28 @@ static int create_host(tlpk_handle *h, const tlpk_options &def, int64_t m, int64
         h->last_error = "refine_steps: K1 on one rank only, >= 0";
         rc = TLPK_BADARG;
     }
+    // dense columns (K1): classified on the caller's matrix before the block detection, which then runs on A without them -- a two-stage
+    // stochastic LP's scenarios become the blocks, its first-stage columns the root
+    std::vector<i64> dense;
+    if (rc == TLPK_OK && def.dense_cols) {
+        if (def.dense_cols != 1 || def.max_dense_cols < 0 || def.dense_col_min < 0) {
+            h->last_error = "dense_cols: 0 or 1; max_dense_cols, dense_col_min >= 0"; rc = TLPK_BADARG;
+        } else if (h->opt.system == 1) {
+            h->last_error = "dense_cols: K1 only (the augmented system K2 never forms A*D*A')"; rc = TLPK_BADARG;
+        } else if (h->opt.nranks > 1 || common) {
+            h->last_error = "dense_cols: not on sharded handles (nranks > 1)"; rc = TLPK_BADARG;
+        } else if (colptr && n > 0) {
+            const i64 thr = def.dense_col_min > 0 ? def.dense_col_min : 1000, cap = def.max_dense_cols > 0 ? def.max_dense_cols : 1024;
+            std::vector<std::pair<i64, i64>> q;                     // (-count, column): the densest first, ties to the lower index
+            for (i64 j = 0; j < n; ++j) {
+                const i64 c = colptr[j + 1] - colptr[j];
+                if (c > thr || (def.col_dense && def.col_dense[j] != 0)) q.emplace_back(-c, j);
+            }
+            if ((i64)q.size() > cap) { std::sort(q.begin(), q.end()); q.resize((size_t)cap); }
+            for (const auto &e : q) dense.push_back(e.second);
+            std::sort(dense.begin(), dense.end());
+        }
+    }
     if (def.row_block && m > 0) {
         h->row_block_copy.assign(def.row_block, def.row_block + m);
         h->opt.row_block = h->row_block_copy.data();
@@ -522,7 +556,20 @@ static int create_host(tlpk_handle *h, const tlpk_options &def, int64_t m, int64
         // the hook that survives Tulip's presolve: find the block structure of the matrix KKT.setup actually received
         h->row_block_copy.assign((size_t)m, 0);
         int64_t nb = 1, nl = 0;
-        const int drc = tlpk_detect_blocks(m, n, colptr, rowval, index_base, def.max_link_rows, h->row_block_copy.data(), &nb, &nl);
+        std::vector<int64_t> cs, rs;                                // A without its dense columns (left empty)
+        const int64_t *cp = colptr, *rv = rowval;
+        if (!dense.empty()) {
+            std::vector<char> isd((size_t)n, 0);
+            for (i64 j : dense) isd[(size_t)j] = 1;
+            cs.assign((size_t)n + 1, index_base);
+            for (i64 j = 0; j < n; ++j) {
+                if (!isd[(size_t)j]) for (int64_t p = colptr[j] - index_base; p < colptr[j + 1] - index_base; ++p) rs.push_back(rowval[p]);
+                cs[(size_t)j + 1] = (int64_t)rs.size() + index_base;
+            }
+            if (rs.empty()) rs.push_back(index_base);
+            cp = cs.data(); rv = rs.data();
+        }
+        const int drc = tlpk_detect_blocks(m, n, cp, rv, index_base, def.max_link_rows, h->row_block_copy.data(), &nb, &nl);
         if (drc != TLPK_OK && drc != TLPK_BADARG) { rc = drc; h->last_error = "tlpk_detect_blocks failed"; }
         if (drc == TLPK_OK && nb >= 2) h->opt.row_block = h->row_block_copy.data();
         else h->row_block_copy.clear();          // no structure (or malformed input: analyse reports it): general sparse path
@@ -542,6 +589,7 @@ static int create_host(tlpk_handle *h, const tlpk_options &def, int64_t m, int64
     const auto t0 = std::chrono::steady_clock::now();
     if (rc == TLPK_OK) {
         if (common) { h->S = *common; h->opt.k2_n = common->k2_n; rc = analyse_rank(h->S, h->opt); }
+        else if (!dense.empty()) rc = analyse_dense(h->S, m, n, colptr, rowval, nzval, index_base, h->opt, dense);
         else rc = (h->opt.system == 1) ? analyse_k2(h->S, m, n, colptr, rowval, nzval, index_base, h->opt)
                                        : analyse(h->S, m, n, colptr, rowval, nzval, index_base, h->opt);
     }
@@ -616,7 +664,8 @@ static int create_device(tlpk_handle *h, const tlpk_options &def) {
                     for (i64 j = 0; j < h->S.n; ++j) { const i64 cj = h->S.Ap[(size_t)j + 1] - h->S.Ap[(size_t)j]; if (cj > cmax) { cmax = cj; jmax = j; } }
                     if (cmax >= 1000 && (double)cmax * (double)cmax >= 0.05 * (double)h->S.nnzL)
                         h->last_error += "; column " + std::to_string(jmax) + " of A has " + std::to_string(cmax) + " entries (a dense column fills the normal equations): "
-                                         "the augmented system KKT_System = K2 (TLPK_SYSTEM_K2) does not form A*D*A'";
+                                         "the augmented system KKT_System = K2 (TLPK_SYSTEM_K2) does not form A*D*A'" +
+                                         std::string(def.dense_cols == 0 ? "; or keep K1 with dense_cols = 1" : "");
                 }
                 rc = TLPK_TOO_LARGE;
             }
@@ -731,6 +780,7 @@ static int enq_update_local(tlpk_handle *h) {
     {
         ProfScope ps(h, TLPK_KC_ASSEMBLE);
         if (S.system == 1) launch_k2_diag(h->stream, user_n(h), h->d_theta, h->d_regP, h->d_D);      // D2 = [theta + regP ; 1]  (sqd.jl:44-50)
+        else if (S.n_dense > 0) launch_dense_diag(h->stream, h->d, h->d_theta, h->d_regP, h->d_D);  // [1 / (theta + regP) | theta + regP on dense columns ; 1]
         else launch_compute_d(h->stream, S.n, h->d_theta, h->d_regP, h->d_D);
     }
     // step 13d: zero-fill + assembly of the upper fronts (97 % of the factor's bytes on a block-angular LP) on the last stream group's side stream,
@@ -1079,6 +1129,7 @@ static int enq_solve_local(tlpk_handle *h, const double *d_xip, const double *d_
         //  flag may be that update's: it stays)
         if (h->S.sweep && !h->root_pending) HIPCHK(h, hipMemsetAsync(h->d.ctx.info + 1, 0, sizeof(int), h->stream));
         if (h->S.system == 1) launch_k2_rhs(h->stream, h->d, h->S.k2_n, d_xip, d_xid, 0, rhs_rank >= 0 ? rhs_rank : h->opt.rank);        // [xi_d ; xi_p] permuted (sqd.jl:62-66)
+        else if (h->S.n_dense > 0) { const double *p[2] = {d_xip, d_xip}, *q[2] = {d_xid, d_xid}; launch_dense_rhs(h->stream, h->d, h->d_D, p, q, 1); }
         else launch_rhs(h->stream, h->d, h->d_D, d_xip, d_xid, rhs_rank >= 0 ? rhs_rank : h->opt.rank);
         launch_single_solve(h->stream, h->d);
     }
@@ -1089,12 +1140,17 @@ static int enq_solve_local(tlpk_handle *h, const double *d_xip, const double *d_
 static int enq_solve_finish(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xid) {
     if (h->root_pending) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_root, 0));      // the root front is being factorised on its own stream
     run_launches(h, h->S.fwd_launches, h->fwd_marker, h->S.fwd_launches.size(), 0);
-    if (h->S.system == 1) { ProfScope ps(h, TLPK_KC_SPMV); launch_apply_signs(h->stream, h->d); }     // L S L' x = b: z = S y between the sweeps
+    if (h->S.system == 1 || h->S.n_dense > 0) { ProfScope ps(h, TLPK_KC_SPMV); launch_apply_signs(h->stream, h->d); }     // L S L' x = b: z = S y between the sweeps
     run_launches(h, h->S.bwd_launches, 0, h->S.bwd_launches.size(), 1);
     if (h->S.system == 1) {
         // multi-device mode: every shard stores the nodes it owns straight into the lead device's job-wide dx / dy
         ProfScope ps(h, TLPK_KC_SPMV);
         launch_k2_out(h->stream, h->d, h->S.k2_n, d_dx, h->shared_dy ? h->shared_dy : d_dy, 0, h->opt.rank, h->dx_local_only ? 1 : 0);
+    } else if (h->S.n_dense > 0) {
+        ProfScope ps(h, TLPK_KC_SPMV);
+        double *y[2] = {d_dy, d_dy}, *x[2] = {d_dx, d_dx};
+        const double *q[2] = {d_xid, d_xid};
+        launch_dense_out(h->stream, h->d, h->d_D, y, q, x, 1);
     } else {
         { ProfScope ps(h, TLPK_KC_SPMV); launch_unpermute(h->stream, h->d, d_dy, h->shared_dy, h->opt.rank); }
         { ProfScope ps(h, TLPK_KC_SPMV); launch_dx(h->stream, h->d, h->d_D, d_dy, d_xid, d_dx, h->dx_local_only ? 1 : 0); }
@@ -1179,12 +1235,12 @@ int tlpk_solve_device(tlpk_handle *h, double *d_dx, double *d_dy, const double *
         rc = whole ? solve_whole(h, h->d_cx, h->d_cy, h->d_r1, h->d_r2) : tlpk_solve_local(h, h->d_r1, h->d_r2);
         if (rc == TLPK_OK && !whole) rc = tlpk_solve_finish(h, h->d_cx, h->d_cy, h->d_r2);
         if (rc != TLPK_OK) break;
-        launch_candidate(h->stream, h->S.n, d_dx, h->d_cx, h->S.m, d_dy, h->d_cy);
+        launch_candidate(h->stream, h->S.n, d_dx, h->d_cx, user_m(h), d_dy, h->d_cy);
         // residuals of the candidate: the next step's right-hand side if the candidate is kept (after a rejection nothing is kept any more)
         launch_residuals(h->stream, h->d, d_xip, d_xid, h->d_theta, h->d_regP, h->d_regD, h->d_cx, h->d_cy, h->d_r1, h->d_r2, 0);
         launch_absmax2(h->stream, h->d, h->d_r1, h->d_r2, h->d_ref + 2);
         launch_refine_decide(h->stream, h->d_ref);
-        launch_refine_commit(h->stream, h->S.n, d_dx, h->d_cx, h->S.m, d_dy, h->d_cy, h->d_ref);
+        launch_refine_commit(h->stream, h->S.n, d_dx, h->d_cx, user_m(h), d_dy, h->d_cy, h->d_ref);
         HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     }
     if (h->refine_steps > 0 && rc == TLPK_OK)
@@ -1240,7 +1296,7 @@ int tlpk_refine_finish(tlpk_handle *h, double *d_dx, double *d_dy) {
     const int rc = enq_solve_finish(h, h->d_cx, h->d_cy, h->d_r2);
     h->shared_dy = keep; h->dx_local_only = keep_lo;
     if (rc != TLPK_OK) return rc;
-    launch_axpy2(h->stream, h->S.n, d_dx, h->d_cx, h->S.m, d_dy, h->d_cy);
+    launch_axpy2(h->stream, h->S.n, d_dx, h->d_cx, user_m(h), d_dy, h->d_cy);
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     HIPCHK(h, hipGetLastError());
     h->solve_timed = true;
@@ -1257,7 +1313,8 @@ static int enq_solve2_local(tlpk_handle *h, const double *const *xip, const doub
         if (h->S.n_sweep_flags > 0) HIPCHK(h, hipMemsetAsync(h->d.sweep_tickets, 0xFF, (size_t)h->d.sweep_reset_bytes2, h->stream));
         if (k2) {
             for (int r = 0; r < 2; ++r) launch_k2_rhs(h->stream, h->d, h->S.k2_n, xip[r], xid[r], r, rank);
-        } else launch_rhs2(h->stream, h->d, h->d_D, xip, xid, rank);          // both right-hand sides in one launch each (round 6)
+        } else if (h->S.n_dense > 0) launch_dense_rhs(h->stream, h->d, h->d_D, xip, xid, 2);
+        else launch_rhs2(h->stream, h->d, h->d_D, xip, xid, rank);          // both right-hand sides in one launch each (round 6)
         launch_single_solve(h->stream, h->d, 2);
     }
     run_launches(h, h->S.fwd_launches, 0, h->fwd_marker, 0, 2);
@@ -1268,11 +1325,12 @@ static int enq_solve2_finish(tlpk_handle *h, double *const *dx, double *const *d
     const bool k2 = h->S.system == 1;
     if (h->root_pending) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_root, 0));      // the root front is being factorised on its own stream
     run_launches(h, h->S.fwd_launches, h->fwd_marker, h->S.fwd_launches.size(), 0, 2);
-    if (k2) { ProfScope ps(h, TLPK_KC_SPMV); launch_apply_signs(h->stream, h->d, 0); launch_apply_signs(h->stream, h->d, 1); }
+    if (k2 || h->S.n_dense > 0) { ProfScope ps(h, TLPK_KC_SPMV); launch_apply_signs(h->stream, h->d, 0); launch_apply_signs(h->stream, h->d, 1); }
     run_launches(h, h->S.bwd_launches, 0, h->S.bwd_launches.size(), 1, 2);
     {
         ProfScope ps(h, TLPK_KC_SPMV);
         if (k2) { for (int r = 0; r < 2; ++r) launch_k2_out(h->stream, h->d, h->S.k2_n, dx[r], dy[r], r, h->opt.rank, 0); }
+        else if (h->S.n_dense > 0) launch_dense_out(h->stream, h->d, h->d_D, dy, xid, dx, 2);
         else if (h->shared_dy || h->dx_local_only) {                              // (shards of a multi-device handle publish into the lead's vectors: per right-hand side)
             for (int r = 0; r < 2; ++r) {
                 launch_unpermute(h->stream, h->d, dy[r], nullptr, h->opt.rank, r);
@@ -1854,6 +1912,12 @@ int tlpk_create_multi(tlpk_handle **out, int64_t m, int64_t n, const int64_t *co
                       int index_base, const tlpk_options *uopt, int ngpus, const int32_t *devices) {
     if (!out) return TLPK_BADARG;
     *out = nullptr;
+    if (uopt && uopt->struct_size == (int32_t)sizeof(tlpk_options) && uopt->dense_cols) {
+        // the dense nodes would be replicated root nodes whose columns span shards, while the multi-shard device-resident loops give every
+        // column to exactly one shard: not supported
+        g_create_error = "dense_cols: not on tlpk_create_multi handles";
+        return TLPK_BADARG;
+    }
     if (!uopt || uopt->struct_size != (int32_t)sizeof(tlpk_options) || ngpus < 1 || ngpus > MAX_DEVICES ||
         (!uopt->row_block && !uopt->detect_blocks))
         return TLPK_BADARG;                              // block-angular LPs only (general sparse LPs stay single-GPU)
@@ -2025,6 +2089,7 @@ int tlpk_info(const tlpk_handle *h, tlpk_stats *out) {
     for (const Launch &L : S.factor_launches) if (L.kind == LK_CHAIN) { out->chain_launches++; out->chain_items += L.count; }
     out->refine_rejected = h->refine_rejected;
     out->root_panel_len = (S.root_front >= 0) ? pk_len(S.fronts[S.root_front].lda, S.fronts[S.root_front].ns) : 0;
+    out->n_dense_cols = S.n_dense;
     return TLPK_OK;
 }
 
@@ -2045,7 +2110,10 @@ int tlpk_set_profile(tlpk_handle *h, int on) {
 int tlpk_get_perm(const tlpk_handle *h, int64_t *perm) {
     if (!h || !perm) return TLPK_BADARG;
     if (!h->sub.empty()) return tlpk_get_perm(h->sub[0], perm);
-    for (i64 i = 0; i < h->S.m; ++i) perm[i] = h->S.perm[(size_t)i];
+    // (dense columns: the constraint nodes in their order; the dense nodes m .. m + k - 1 are left out)
+    const i64 mu = user_m(h);
+    i64 o = 0;
+    for (i64 i = 0; i < h->S.m; ++i) if (h->S.system == 1 || h->S.perm[(size_t)i] < mu) perm[o++] = h->S.perm[(size_t)i];
     return TLPK_OK;
 }
 
@@ -2090,6 +2158,7 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
     else if (w == "front_child_ptr") field([](const FrontDesc &f) { return f.child_ptr; });
     else if (w == "front_nchild") field([](const FrontDesc &f) { return f.nchild; });
     else if (w == "root_front") tmp.assign(1, S.root_front);
+    else if (w == "dense_cols") tmp = S.dense_cols;
     else if (w == "potrf_tasks") { for (auto &t : S.potrf_tasks) { tmp.push_back(t.front); tmp.push_back(t.k0); tmp.push_back(t.nb); tmp.push_back(t.kprev); } }
     else if (w == "trsm_tasks") { for (auto &t : S.trsm_tasks) { tmp.push_back(t.front); tmp.push_back(t.k0); tmp.push_back(t.nb); tmp.push_back(t.row0); tmp.push_back(t.kprev); tmp.push_back(t.pad1); } }
     else if (w == "update_tasks") { for (auto &t : S.update_tasks) { tmp.push_back(t.front); tmp.push_back(t.k0); tmp.push_back(t.kw); tmp.push_back(t.i0); tmp.push_back(t.j0); tmp.push_back(t.jlim); tmp.push_back(t.beta0); tmp.push_back(t.pad1); tmp.push_back(t.seg); tmp.push_back(t.nsl); } }

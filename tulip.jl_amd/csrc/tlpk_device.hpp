@@ -41,7 +41,11 @@ struct SweepArgs {
 
 struct DevArrays {
     DevCtx ctx{};
-    i64 m = 0, n = 0;
+    i64 m = 0, n = 0;                         // m: order of the factored matrix (K2: n + m; dense columns: m + k), n: columns of the stored matrix
+    i64 mu = 0;                               // rows of A as the caller sees them (= m for plain K1): the residual kernels of the refinement
+    // K1 with dense columns (tlpk_options.dense_cols): sparse_col[j] = 1 for a column formed into A_s D_s A_s', 0 for a dense one;
+    // dense_col[t] = the column of node mu + t
+    char *sparse_col = nullptr; i32 *dense_col = nullptr; i64 n_dense = 0;
     // A (CSC + CSR)
     i64 *Ap = nullptr; i32 *Ai = nullptr; double *Ax = nullptr;
     i64 *Tp = nullptr; i32 *Tj = nullptr; double *Tx = nullptr;
@@ -105,5 +109,11 @@ void launch_k2_diag(hipStream_t st, i64 n, const double *theta, const double *re
 void launch_k2_rhs(hipStream_t st, const DevArrays &a, i64 n, const double *xi_p, const double *xi_d, int rhs = 0, int rank = 0);
 void launch_apply_signs(hipStream_t st, const DevArrays &a, int rhs = 0);
 void launch_k2_out(hipStream_t st, const DevArrays &a, i64 n, double *dx, double *dy, int rhs = 0, int rank = 0, int owned_only = 0);
+// K1 with dense columns (kernels.hip: k_dense_*): D = [sparse j: 1 / (theta + regP), dense j: theta + regP ; 1]; the permuted right-hand side
+// [xi_p + A_s D_s xi_d_s ; xi_d_d]; [dy ; dx_d] = P' x and dx_s = D_s (A_s' dy - xi_d_s).  nrhs = 2: both right-hand sides of a pair in one
+// launch each (grid y), slots 0 / 1 of xw -- the same arithmetic per right-hand side as two single solves
+void launch_dense_diag(hipStream_t st, const DevArrays &a, const double *theta, const double *regP, double *D);
+void launch_dense_rhs(hipStream_t st, const DevArrays &a, const double *D, const double *const *xi_p, const double *const *xi_d, int nrhs);
+void launch_dense_out(hipStream_t st, const DevArrays &a, const double *D, double *const *dy, const double *const *xi_d, double *const *dx, int nrhs);
 
 }  // namespace tlpk

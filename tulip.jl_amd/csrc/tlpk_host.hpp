@@ -132,6 +132,8 @@ struct Options {
                                       // GPU the in-role waits gave up in ~1 % of the runs of the eight-shards tests even with lean polling (profiles/r06_chain_poll_storm.txt)
     const i64 *user_perm = nullptr;   // 0-based here
     const i64 *row_block = nullptr;
+    i64 n_dense = 0;                  // K1 with dense columns (analyse_dense): the last n_dense nodes of the matrix are the dense-column nodes -- ordered after
+                                      // every constraint node, in the root front (general path: behind the AMD order of the constraint nodes; block path: row_block -1)
 };
 
 // std::vector without the value-initialisation of resize(n): the large arrays of the analyse phase are written exactly once, by the host threads that own their
@@ -151,7 +153,11 @@ struct Symbolic {
     i64 m = 0, n = 0, nnzA = 0;          // K2: m = order of the augmented matrix (n_var + m_con), n / nnzA those of the incidence matrix below
     i32 system = 0; i64 k2_n = 0, k2_m = 0;   // K2: user dimensions (variables, constraints)
     i32 shared_device = 0;               // Options::shared_device of the rank this schedule is built for
-    std::vector<double> csign;           // K2: +1 / -1 per permuted column (constraint / variable node)
+    std::vector<double> csign;           // K2 and dense columns: +1 / -1 per permuted column (constraint / variable node)
+    // K1 with dense columns (analyse_dense): m = order m_user + n_dense of the factored matrix, n / nnzA / Ap ... = the caller's A (K1 layout: what the
+    // solve, refinement and device-resident kernels read); node m_user + t = column dense_cols[t] (ascending), csign -1 there
+    i64 n_dense = 0, dense_n = 0;        // dense_n: the caller's n (= the leading columns of the incidence matrix while it is analysed)
+    std::vector<i64> dense_cols;
     // A, CSC and CSR (0-based, int32 indices); csr_pos[q] = CSC position of the CSR entry q
     std::vector<i64> Ap; std::vector<i32> Ai; std::vector<double> Ax;
     std::vector<i64> Tp; std::vector<i32> Tj; std::vector<i32> Tpos;
@@ -245,5 +251,10 @@ int analyse_k2_common(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *r
                       int index_base, const Options &opt, Options *opt_out);
 int analyse_k2(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowval, const double *nzval,
                int index_base, const Options &opt);
+// K1 with dense columns: the partially augmented system [A_s D_s A_s' + Rd, A_d; A_d', -(Theta_d^-1 + Rp_d)] of order m + k, k = dense.size()
+// (dense: ascending column indices).  Analysed through the incidence matrix [A_s | B_d] (A with the dense columns emptied, then one column per
+// entry of a dense column: A[i,j] on row i, 1 on node m + t); afterwards S.Ap ... hold A itself.  One rank.
+int analyse_dense(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowval, const double *nzval,
+                  int index_base, const Options &opt, const std::vector<i64> &dense);
 
 }  // namespace tlpk

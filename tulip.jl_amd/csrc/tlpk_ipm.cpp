@@ -180,7 +180,7 @@ int tlpk_ipm_load(tlpk_handle *h, const double *b, const double *c, const double
 static int ipm_load_impl(tlpk_handle *h, const double *b, const double *c, const double *l, const double *u, bool shard) {
     HIPCHK(h, hipSetDevice(h->device));
     const bool k2 = h->S.system == 1;
-    const i64 m = k2 ? h->S.k2_m : h->S.m, n = k2 ? h->S.k2_n : h->S.n;
+    const i64 m = k2 ? h->S.k2_m : h->S.m - h->S.n_dense, n = k2 ? h->S.k2_n : h->S.n;      // (dense columns: S.m is the order m + k of the factored matrix)
     IpmState *sp = new (std::nothrow) IpmState();
     if (!sp) return TLPK_OOM;
     h->ipm = sp;

@@ -22,7 +22,8 @@ import ..KKT: setup, update!, solve!, backend, linear_system
 using ...TLPLinearAlgebra.LibTLPK
 
 """
-    Backend(; device=0, row_block=nothing, streams=0, ngpus=1, devices=nothing, refine=0, max_link_rows=0)
+    Backend(; device=0, row_block=nothing, streams=0, ngpus=1, devices=nothing, refine=0, max_link_rows=0,
+              dense_cols=nothing, max_dense_cols=0, dense_col_min=0)
 
 HIP (gfx950) backend.  `row_block` is the optional block-angular structure hook:
   * `:auto` -- the library finds the structure of the matrix `KKT.setup` receives (`tlpk_detect_blocks`).  This is the
@@ -35,6 +36,9 @@ HIP (gfx950) backend.  `row_block` is the optional block-angular structure hook:
 diagonal blocks over `ngpus` devices of the node (`devices`: HIP ordinals, default `0:ngpus-1`); the
 linking-block reductions happen inside the library.  `streams`: concurrent stream groups (0 = auto).
 `refine`: iterative-refinement steps per `solve!` (0 = none, as `spd.jl:68`; `K1`, one GPU or `ngpus > 1`).
+`dense_cols` (`K1`, one GPU): `:auto` -- columns with more than `dense_col_min` entries (0 = 1000) stay out of `A D Aᵀ` and
+become augmented nodes of a quasi-definite system of order m + k (at most `max_dense_cols` of them, 0 = 1024); a
+`Vector{Int}` of column indices also marks those columns (first-stage variables; `Presolve_Level = 0`).
 """
 struct Backend <: AbstractKKTBackend
     device::Int
@@ -44,10 +48,16 @@ struct Backend <: AbstractKKTBackend
     devices::Union{Nothing,Vector{Int32}}
     refine::Int
     max_link_rows::Int
+    dense_cols::Union{Nothing,Symbol,Vector{Int}}
+    max_dense_cols::Int
+    dense_col_min::Int
 end
-function Backend(; device::Int=0, row_block=nothing, streams::Int=0, ngpus::Int=1, devices=nothing, refine::Int=0, max_link_rows::Int=0)
+function Backend(; device::Int=0, row_block=nothing, streams::Int=0, ngpus::Int=1, devices=nothing, refine::Int=0, max_link_rows::Int=0,
+                 dense_cols=nothing, max_dense_cols::Int=0, dense_col_min::Int=0)
     row_block isa Symbol && row_block !== :auto && throw(ArgumentError("row_block: a vector of block ids, nothing, or :auto"))
-    return Backend(device, row_block, streams, ngpus, devices === nothing ? nothing : Vector{Int32}(devices), refine, max_link_rows)
+    dense_cols isa Symbol && dense_cols !== :auto && throw(ArgumentError("dense_cols: nothing, :auto, or a vector of column indices"))
+    return Backend(device, row_block, streams, ngpus, devices === nothing ? nothing : Vector{Int32}(devices), refine, max_link_rows,
+                   dense_cols, max_dense_cols, dense_col_min)
 end
 
 """
@@ -140,14 +150,16 @@ _system_code(::K2) = LibTLPK.TLPK_SYSTEM_K2
 # a BlockAngularMatrix brings its own partition (unless the backend names one explicitly)
 function setup(B::BlockAngularMatrix, system::Union{K1,K2}, b::Backend)
     rb = b.row_block isa Vector{Int} ? b.row_block : (B.n_blocks >= 2 ? B.row_block : nothing)
-    return setup(B.A, system, Backend(b.device, rb, b.streams, b.ngpus, b.devices, b.refine, b.max_link_rows))
+    return setup(B.A, system, Backend(b.device, rb, b.streams, b.ngpus, b.devices, b.refine, b.max_link_rows,
+                                      b.dense_cols, b.max_dense_cols, b.dense_col_min))
 end
 
 function setup(A::SparseMatrixCSC{Float64,Int}, system::Union{K1,K2}, b::Backend)
     m, n = size(A)
     rc, h = LibTLPK.create(m, n, A.colptr, A.rowval, A.nzval; device=b.device,
                            row_block=(b.row_block isa Vector{Int} ? b.row_block : nothing), detect_blocks=(b.row_block === :auto),
-                           max_link_rows=b.max_link_rows,
+                           max_link_rows=b.max_link_rows, dense_cols=b.dense_cols, max_dense_cols=b.max_dense_cols,
+                           dense_col_min=b.dense_col_min,
                            system=_system_code(system), streams=b.streams, ngpus=b.ngpus, devices=b.devices, refine=b.refine)
     rc == LibTLPK.TLPK_OK || (h == C_NULL || LibTLPK.destroy(h); _check(rc, C_NULL, "KKT.setup"))
     return HIPNormalEquations(m, n, A, h)

@@ -53,6 +53,10 @@ Base.@kwdef mutable struct Options
     detect_blocks::Int32 = 0     # 1: the library finds the block-angular structure of the matrix it is given
     keep_on_too_large::Int32 = 0   # 1: tlpk_create returns a live analyse-only handle with TLPK_TOO_LARGE
     max_link_rows::Int64 = 0
+    dense_cols::Int32 = 0        # 1: columns with more than dense_col_min entries (or flagged in col_dense) become augmented nodes (K1)
+    max_dense_cols::Int32 = 0    # cap on their number; 0 = 1024
+    dense_col_min::Int64 = 0     # 0 = 1000
+    col_dense::Ptr{Int64} = C_NULL
 end
 
 strerror(code::Integer) = unsafe_string(ccall((:tlpk_strerror, libtlpk[]), Cstring, (Cint,), code))
@@ -72,7 +76,8 @@ with its 1-based `colptr`/`rowval` (index_base = 1); the library copies everythi
 function create(m::Int, n::Int, colptr::Vector{Int}, rowval::Vector{Int}, nzval::Vector{Float64};
                 device::Integer=0, row_block::Union{Nothing,Vector{Int}}=nothing, system::Int32=TLPK_SYSTEM_K1,
                 streams::Integer=0, ngpus::Integer=1, devices::Union{Nothing,Vector{Int32}}=nothing, refine::Integer=0,
-                detect_blocks::Bool=false, max_link_rows::Integer=0)
+                detect_blocks::Bool=false, max_link_rows::Integer=0,
+                dense_cols::Union{Nothing,Symbol,Vector{Int}}=nothing, max_dense_cols::Integer=0, dense_col_min::Integer=0)
     opt = Options()
     opt.struct_size = Int32(sizeof(Options))
     opt.device = Int32(device)
@@ -81,11 +86,18 @@ function create(m::Int, n::Int, colptr::Vector{Int}, rowval::Vector{Int}, nzval:
     opt.refine_steps = Int32(refine)
     opt.detect_blocks = Int32(detect_blocks && row_block === nothing)
     opt.max_link_rows = Int64(max_link_rows)
+    # dense_cols: nothing = off, :auto = the count rule, a vector of 1-based column indices = those columns (and the rule)
+    opt.dense_cols = Int32(dense_cols !== nothing)
+    opt.max_dense_cols = Int32(max_dense_cols)
+    opt.dense_col_min = Int64(dense_col_min)
+    cd = zeros(Int64, dense_cols isa Vector{Int} ? n : 0)
+    dense_cols isa Vector{Int} && (cd[dense_cols] .= 1)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     rb = row_block === nothing ? Int[] : row_block
     dv = devices === nothing ? Int32[] : devices
-    rc = GC.@preserve colptr rowval nzval rb dv opt begin
+    rc = GC.@preserve colptr rowval nzval rb dv cd opt begin
         row_block === nothing || (opt.row_block = pointer(rb))
+        dense_cols isa Vector{Int} && (opt.col_dense = pointer(cd))
         if ngpus > 1
             # one Julia process, several GPUs: block-angular LPs only (tlpk_create_multi, include/tlpk.h)
             ccall((:tlpk_create_multi, libtlpk[]), Cint,

@@ -51,11 +51,15 @@ class Backend:
     or "auto": the library finds the structure of the matrix it is given (tlpk_detect_blocks).  An explicit
     map indexes the rows of the matrix KKT.setup receives, i.e. it is only meaningful without presolve
     (Tulip's presolve removes and renumbers rows, model.jl:88-131); "auto" works on the presolved matrix.
+
+    dense_cols (K1, one GPU): None = off; "auto" = columns with more than `dense_col_min` entries (0 = 1000) stay out of
+    A*D*A' and become augmented nodes of a quasi-definite system of order m + k (at most `max_dense_cols`, 0 = 1024, the
+    densest first); a sequence of column indices additionally marks those columns (only meaningful without presolve).
     """
 
     def __init__(self, device=0, ordering="amd", relax=True, row_block=None, user_perm=None,
                  profile=False, rank=0, nranks=1, mem_budget_bytes=0, streams=0, ngpus=1, devices=None, refine=0,
-                 max_link_rows=0):
+                 max_link_rows=0, dense_cols=None, max_dense_cols=0, dense_col_min=0):
         self.device = device
         self.ordering = {"amd": _lib.ORDER_AMD, "natural": _lib.ORDER_NATURAL, "user": _lib.ORDER_USER}[ordering]
         self.relax = bool(relax)
@@ -75,6 +79,11 @@ class Backend:
         # single-process multi-GPU (block-angular LPs): one handle shards the diagonal blocks over `ngpus` devices
         self.ngpus = int(ngpus)
         self.devices = None if devices is None else np.ascontiguousarray(devices, dtype=np.int32)
+        if isinstance(dense_cols, str) and dense_cols != "auto":
+            raise ValueError("dense_cols: None, 'auto', or column indices")
+        self.dense_cols = dense_cols if dense_cols is None or isinstance(dense_cols, str) else np.unique(np.asarray(dense_cols, dtype=np.int64))
+        self.max_dense_cols = int(max_dense_cols)
+        self.dense_col_min = int(dense_col_min)
 
 
 def detect_blocks(A, max_link_rows=0):
@@ -144,6 +153,18 @@ class HIPNormalEquations:
         if backend_.user_perm is not None:
             opt.user_perm = _lib.as_p64(backend_.user_perm)
             self._keep.append(backend_.user_perm)
+        dense = getattr(backend_, "dense_cols", None)
+        if dense is not None:
+            opt.dense_cols = 1
+            opt.max_dense_cols = backend_.max_dense_cols
+            opt.dense_col_min = backend_.dense_col_min
+            if not isinstance(dense, str):
+                if dense.size and (dense[0] < 0 or dense[-1] >= self.n):
+                    raise DimensionMismatch(f"dense_cols: column index out of range for n={self.n}")
+                flags = np.zeros(max(self.n, 1), dtype=np.int64)
+                flags[dense] = 1
+                opt.col_dense = _lib.as_p64(flags)
+                self._keep.append(flags)           # read by tlpk_create only; kept alive with the handle all the same
         colptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
         rowval = np.ascontiguousarray(A.indices, dtype=np.int64)
         nzval = np.ascontiguousarray(A.data, dtype=np.float64)
