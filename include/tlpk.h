@@ -120,6 +120,8 @@ typedef struct tlpk_stats {
     int64_t chain_launches, chain_items;   /* number of those launches per factorisation and the items (update tiles, diagonal blocks, solve strips, reductions) they hold */
     int64_t n_dense_cols;      /* k: columns of A handled as augmented nodes (tlpk_options.dense_cols); tlpk_symbolic_get(h, "dense_cols") lists them.
                                   m, n, nnzA are the caller's; nnzS, nnzL, n_pairs, fail_col, ... describe the factored matrix of order m + k */
+    double  flops_syrk;        /* dense-matrix handles (tlpk_create_dense): n m (m + 1), the flops of the lower triangle of A*D*A' on the matrix cores
+                                  (2 per product); 0 on sparse handles */
 } tlpk_stats;
 
 /* per-kernel-class timing, filled when options.profile = 1 */
@@ -150,6 +152,16 @@ void tlpk_default_options(tlpk_options *opt);
 int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr,
                 const int64_t *rowval, const double *nzval, int index_base,
                 const tlpk_options *opt);
+/* Dense constraint matrix (the reference's dense backend, src/KKT/Dense/lapack.jl; K1 only).  A: m x n, column-major, leading dimension
+ * lda >= m (a Julia Matrix{Float64}); copied, nothing retained.  The handle then behaves like any single-device K1 handle: natural order,
+ * ONE dense front of m columns, A*D*A' + Rd formed on the fp64 matrix cores (timed as TLPK_KC_ASSEMBLE) straight into the front's panel,
+ * the blocked dense Cholesky and the sweeps of the sparse handles, two dense matrix-vector products per solve (TLPK_KC_SPMV).  No pattern
+ * of S and no assembly lists are built: host memory beyond the copy of A is O(m + schedule), tlpk_stats.n_pairs = 0.
+ * Honoured options: device (-1 = analyse only), profile, mem_budget_bytes, keep_on_too_large; ordering, relax, streams are ignored.
+ * TLPK_BADARG (sentence in tlpk_last_create_error()): A == NULL, lda < m, m < 1, system = K2, nranks > 1, row_block / detect_blocks,
+ * user_perm, dense_cols, refine_steps > 0.  TLPK_TOO_LARGE: the device copy of A + the panel + workspace exceed the budget (the message
+ * states the bytes).  The split-phase calls (tlpk_*_local / tlpk_*_finish, tlpk_root_*, tlpk_refine_*) do not apply: TLPK_BADARG. */
+int tlpk_create_dense(tlpk_handle **out, int64_t m, int64_t n, const double *A, int64_t lda, const tlpk_options *opt);
 void tlpk_destroy(tlpk_handle *h);
 
 /* Host-pointer entry points (what the Julia glue calls). */

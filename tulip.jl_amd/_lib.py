@@ -42,7 +42,7 @@ class Stats(C.Structure):
                 ("root_panel_len", C.c_int64), ("flops_update", C.c_double),
                 ("flops_update_alg", C.c_double), ("ms_enqueue_update", C.c_double), ("refine_rejected", C.c_int64),
                 ("flops_update_chain", C.c_double), ("flops_update_alg_chain", C.c_double), ("chain_launches", C.c_int64), ("chain_items", C.c_int64),
-                ("n_dense_cols", C.c_int64)]
+                ("n_dense_cols", C.c_int64), ("flops_syrk", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -69,7 +69,7 @@ EXPORTS = [
     "tlpk_mpc_start", "tlpk_mpc_newton", "tlpk_mpc_gap", "tlpk_mpc_targets", "tlpk_mpc_advance",
     "tlpk_detect_blocks", "tlpk_solve2_device", "tlpk_ipm_hsolve_newton", "tlpk_update_device_async", "tlpk_ipm_factor_hsolve_newton",
     "tlpk_refine_local", "tlpk_refine_finish", "tlpk_solve2_local", "tlpk_root_rhs2", "tlpk_solve2_finish", "tlpk_last_create_error",
-    "tlpk_host_copy_threads",
+    "tlpk_host_copy_threads", "tlpk_create_dense",
 ]
 
 
@@ -89,6 +89,8 @@ def lib():
     L.tlpk_create.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, p64, p64, pd, C.c_int, C.POINTER(Options)]
     L.tlpk_create_multi.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, p64, p64, pd, C.c_int, C.POINTER(Options), C.c_int, C.POINTER(C.c_int32)]
     L.tlpk_create_multi.restype = C.c_int
+    L.tlpk_create_dense.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, pd, C.c_int64, C.POINTER(Options)]
+    L.tlpk_create_dense.restype = C.c_int
     L.tlpk_destroy.argtypes = [vp]
     L.tlpk_destroy.restype = None
     L.tlpk_update.argtypes = [vp, pd, pd, pd]

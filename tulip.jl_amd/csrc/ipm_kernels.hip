@@ -87,7 +87,8 @@ __global__ __launch_bounds__(IPM_T) void k_ipm_res_cols(IpmVecs v, double tau, d
     const i64 stride = (i64)gridDim.x * blockDim.x;
     for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) {
         double aty = 0.0;
-        for (i64 p = v.Ap[j]; p < v.Ap[j + 1]; ++p) aty += v.Ax[p] * v.y[v.Ai[p]];
+        if (v.aty) aty = v.aty[j];
+        else for (i64 p = v.Ap[j]; p < v.Ap[j + 1]; ++p) aty += v.Ax[p] * v.y[v.Ai[p]];
         const double x = v.x[j], xl = v.xl[j], xu = v.xu[j], zl = v.zl[j], zu = v.zu[j], lf = v.lflag[j], uf = v.uflag[j];
         const double rl = (-x + xl + tau * v.lz[j]) * lf, ru = (-x - xu + tau * v.uz[j]) * uf;
         const double rd = tau * v.c[j] - aty + zu * uf - zl * lf;
@@ -120,7 +121,8 @@ __global__ __launch_bounds__(IPM_T) void k_ipm_res_rows(IpmVecs v, double tau, d
     for (i64 i = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 3; i < mround; i += stride) {
         const bool live = i < v.m;
         double ax = 0.0;
-        if (live)
+        if (live && v.ax) ax = (lane == 0) ? v.ax[i] : 0.0;
+        else if (live)
             for (i64 q = v.Tp[i] + lane; q < v.Tp[i + 1]; q += 8) ax += v.Tx[q] * v.x[v.Tj[q]];
 #pragma unroll
         for (int off = 4; off > 0; off >>= 1) ax += __shfl_down(ax, off, 8);
@@ -305,7 +307,8 @@ __global__ __launch_bounds__(IPM_T) void k_mpc_start2(IpmVecs v, double dxs, dou
         v.xl[j] = (lf != 0.0) ? (x - v.lz[j]) + dxs : 0.0;
         v.xu[j] = (uf != 0.0) ? (v.uz[j] - x) + dxs : 0.0;
         double aty = 0.0;
-        for (i64 p = v.Ap[j]; p < v.Ap[j + 1]; ++p) aty += v.Ax[p] * v.y[v.Ai[p]];
+        if (v.aty) aty = v.aty[j];
+        else for (i64 p = v.Ap[j]; p < v.Ap[j + 1]; ++p) aty += v.Ax[p] * v.y[v.Ai[p]];
         const double z = v.c[j] - aty, nb = lf + uf;
         const double zl = (lf != 0.0) ? z / nb : 0.0, zu = (uf != 0.0) ? -z / nb : 0.0;
         v.zl[j] = zl; v.zu[j] = zu;

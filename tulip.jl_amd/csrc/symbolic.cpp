@@ -1516,7 +1516,86 @@ int analyse_dense(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowva
 }
 
 // ---------------------------------------------------------------------------------------------
-// Launch schedules.  All task lists are static for the lifetime of the handle: one IPM run
+// Dense constraint matrix (tlpk_create_dense; the reference's dense backend, src/KKT/Dense/lapack.jl:52-119).  A matrix without zeros
+// gives a full S = A D A' + Rd: identity order (nothing to reduce), the elimination tree is the chain 0 -> 1 -> ... -> m - 1, column j
+// of L has m - j entries, ONE supernode of m columns without children.  Written down directly -- steps 1 - 9 and 13 - 14 of the sparse
+// analysis would spend n m (m + 1) / 2 list entries to find the same --, then the storage offsets of step 12 and the schedules of
+// build_schedule for that front.  S itself is formed by k_dense_syrk (dense_kernels.hip) straight into the packed panel.
+// ---------------------------------------------------------------------------------------------
+int analyse_dense_matrix(Symbolic &S, i64 m64, i64 n64) {
+    if (m64 < 1 || n64 < 0) return fail(S, TLPK_BADARG, "dense matrix: m >= 1, n >= 0");
+    if (m64 >= ((i64)1 << 24) || n64 >= ((i64)1 << 31)) return fail(S, TLPK_TOO_LARGE, "dense matrix: m < 2^24 and n < 2^31");
+    const i32 m = (i32)m64;
+    S.m = m64; S.n = n64; S.nnzA = m64 * n64; S.system = 0; S.dense_matrix = 1;
+    S.perm.resize((size_t)m); S.iperm.resize((size_t)m); S.parent.resize((size_t)m); S.colcount.resize((size_t)m); S.sn_of_col.assign((size_t)m, 0);
+    S.flops_chol = 0;
+    for (i32 j = 0; j < m; ++j) {
+        S.perm[(size_t)j] = S.iperm[(size_t)j] = j;
+        S.parent[(size_t)j] = (j + 1 < m) ? j + 1 : -1;
+        S.colcount[(size_t)j] = m - j;
+        S.flops_chol += (double)(m - j) * (double)(m - j);
+    }
+    S.Sp.assign((size_t)m + 1, 0);                 // no pattern of S is stored: every column "holds" no listed entry
+    S.nnzS = S.nnzL = m64 * (m64 + 1) / 2;
+    S.flops_syrk = (double)n64 * (double)m64 * (double)(m64 + 1);
+    S.nsuper = 1; S.max_front = m; S.nblocks = 0; S.root_front = -1; S.ngroups = 1; S.n_local_blocks = 0;
+    FrontDesc w{};
+    w.f = m; w.ns = m; w.col0 = 0; w.parent = -1; w.child_ptr = 0; w.nchild = 0; w.rowoff = 0; w.reloff = 0; w.eatab = -1; w.flagoff = -1; w.ubuf = 0;
+    w.lda = (w.f >= LDA_PAD_MIN_F) ? (w.f + 15) / 16 * 16 : w.f;                      // step 12
+    w.loff = 0; S.lval_len = pk_len(w.lda, w.ns);
+    w.uoff = 0; w.ucoff = 0; S.uc_len = 0; S.ubuf_len[0] = S.ubuf_len[1] = 0;
+    w.dinvoff = 0; S.dinv_len = (w.ns >= NB_IN) ? (i64)((w.ns + NB_IN - 1) / NB_IN) * NB_IN * NB_IN : (i64)w.ns * w.ns;
+    S.fronts.assign(1, w);
+    S.rowidx.resize((size_t)m);
+    for (i32 j = 0; j < m; ++j) S.rowidx[(size_t)j] = j;
+    S.sparent_v.assign(1, -1);
+    S.depth.assign(1, 0); S.nlevels = 1; S.level_ptr = {0, 1}; S.level_fronts.assign(1, 0);
+    S.front_block.assign(1, -1); S.front_local.assign(1, 1); S.front_group.assign(1, 0); S.front_fa.assign(1, 0);
+    S.col_local.assign((size_t)n64, 1); S.row_local.assign((size_t)m, 1);
+    S.skip_off.assign(1, -1);                      // no amalgamation padding: nothing to skip
+    S.gth_ptr.assign((size_t)m + 1, 0);            // no children: empty gather lists
+    {
+        const double f = m;
+        S.flops_panel = f * f * f / 3.0;
+        S.flops_update_alg = 0;
+        for (i32 c = 0; c < m; ++c) { const double l = (double)(m - c) - (double)(std::min((c / NB_OUT + 1) * NB_OUT, m) - c); if (l > 0) S.flops_update_alg += l * l; }
+    }
+    S.error.clear();
+    build_schedule(S);
+    if (!S.error.empty()) return TLPK_INTERNAL;
+    for (const UpdateTask &u : S.update_tasks)
+        if ((u.k0 & 15) != 0) return fail(S, TLPK_INTERNAL, "update task: K range does not start on a multiple of 16 columns");
+    S.zero_tasks.clear(); S.zero_small.clear(); S.n_zero_lower = 0;      // k_dense_syrk writes every stored entry of the panel: no zero-fill
+    // k_dense_syrk: 128 x 128 tiles of the lower triangle, two workgroups per CU = 512 at a time.  When the tiles do not fill whole rounds of 512
+    // (m = 2048: 136 tiles; m = 4096: 528 tiles = one full round and 16 stragglers) K = n is cut into parts of whole 16-column slabs, one workgroup
+    // each, whose raw tiles k_dense_syrk_reduce sums in part order: the smallest number of parts that fills its rounds best (2 % or more over
+    // every smaller one), with at least 512 columns per part (a part writes a 128 KB raw tile; 64 while the first round is not full) and at most
+    // 4096 raw tiles of scratch.
+    const i64 T = (m64 + TILE - 1) / TILE, ntiles = T * (T + 1) / 2;
+    i64 split = 1;
+    {
+        auto fill = [&](i64 s_) { const i64 w_ = ntiles * s_; return (double)w_ / (double)((w_ + 511) / 512 * 512); };
+        double best = fill(1);
+        for (i64 s_ = 2; s_ <= 64 && ntiles * s_ <= 4096; ++s_) {
+            if (n64 / s_ < (ntiles * s_ <= 512 ? 64 : 512)) break;            // (inside the first round -- small m -- shorter parts still pay)
+            if (fill(s_) >= best + 0.02) { best = fill(s_); split = s_; }
+        }
+    }
+    const i64 kc = std::max<i64>(16, ((n64 + split - 1) / split + 15) / 16 * 16);
+    split = std::max<i64>(1, (n64 + kc - 1) / kc);
+    S.syrk_split = (i32)split; S.syrk_kc = kc;
+    S.syrk_slots = split > 1 ? ntiles * split : 0;
+    S.spart_len = std::max(S.spart_len, S.syrk_slots * TILE * TILE);      // (shared with k_update's split-K parts: the product is complete before the factorisation starts)
+    // k_dense_gemv_n: row blocks x column chunks, ~1024 workgroups
+    const i64 rowblocks = (dense_lda(m64) + DGEMV_ROWS - 1) / DGEMV_ROWS;
+    i64 chunks = std::max<i64>(1, std::min<i64>(1024 / rowblocks, (n64 + 15) / 16));
+    const i64 cw = std::max<i64>(1, (n64 + chunks - 1) / chunks);
+    S.gemv_chunks = std::max<i64>(1, (n64 + cw - 1) / cw);
+    return TLPK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Launch schedules. All task lists are static for the lifetime of the handle: one IPM run
 // replays them once per update! (factor) and 2..6 times per Newton step (solves).
 // ---------------------------------------------------------------------------------------------
 static void build_schedule(Symbolic &S) {

@@ -243,6 +243,15 @@ int upload_all(tlpk_handle *h) {
     const i64 mu = d.mu;
     int rc;
 #define UP(dst, vec) if ((rc = dev_upload(h, &(dst), (vec))) != TLPK_OK) return rc
+    if (S.dense_matrix) {
+        // launch geometry of the dense kernels (analyse_dense_matrix); A itself is uploaded by tlpk_create_dense
+        d.dlda = dense_lda(S.m);
+        d.syrk_split = S.syrk_split;
+        d.syrk_kc = S.syrk_kc;
+        d.gemv_chunks = S.gemv_chunks;
+        d.gemv_cw = std::max<i64>(1, (S.n + S.gemv_chunks - 1) / S.gemv_chunks);
+        if ((rc = dev_alloc(h, &d.gemv_part, 2 * S.gemv_chunks * d.dlda)) != TLPK_OK) return rc;
+    }
     UP(d.Ap, S.Ap); UP(d.Ai, S.Ai); UP(d.Ax, S.Ax);
     UP(d.Tp, S.Tp); UP(d.Tj, S.Tj);
     {
@@ -251,7 +260,7 @@ int upload_all(tlpk_handle *h) {
         UP(d.Tx, Tx);
     }
     UP(d.perm, S.perm);
-    if (S.system == 0) {
+    if (S.system == 0 && !S.dense_matrix) {
         // a second CSR copy with the rows in PERMUTED order, for the right-hand-side kernel of every solve (k_rhs walks the permuted rows:
         // with the original row order each 8-lane group started with perm[ii] -> Tp[i] -> Tj[q] -> w[j], four dependent loads at scattered
         // addresses, 65 us = 0.6 TB/s on config C4; now Tp / Tj / Tx are streamed).  Entries keep their order inside a row: same sums.
@@ -280,10 +289,11 @@ int upload_all(tlpk_handle *h) {
         // compact the assembly lists to the entries this rank owns.  One rank (every entry local): the lists of the analyse phase ARE the compact ones -- no copies
         // (round 5: the element-by-element compaction of 5 - 30 million entries and an unconditional second copy of the target list were ~70 ms of KKT.setup on C4)
         bool every = true;
-        for (i64 e = 0; e < S.nnzS && every; ++e) every = S.s_local[(size_t)e] != 0;
+        for (i64 e = 0; e < S.nnzS && every && !S.dense_matrix; ++e) every = S.s_local[(size_t)e] != 0;
         std::vector<i64> tgt, ptr; std::vector<i32> diag;
         i64 np = 0;
-        if (every) { d.n_asm = S.nnzS; np = S.pair_ptr[(size_t)S.nnzS]; }
+        if (S.dense_matrix) d.n_asm = 0;                     // no assembly lists: k_dense_syrk forms S
+        else if (every) { d.n_asm = S.nnzS; np = S.pair_ptr[(size_t)S.nnzS]; }
         else {
             tgt.reserve((size_t)S.nnzS); diag.reserve((size_t)S.nnzS); ptr.reserve((size_t)S.nnzS + 1);
             ptr.push_back(0);
@@ -656,6 +666,19 @@ static int create_device(tlpk_handle *h, const tlpk_options &def) {
                                 (double)sizeof(UpdateTask) * (double)(h->S.update_tasks.size() + h->S.reduce_tasks.size()) +
                                 (double)sizeof(EaTask) * (double)h->S.ea_tasks.size() + (double)sizeof(TrsmTask) * (double)h->S.trsm_tasks.size() +
                                 4.0 * (double)h->S.upd_seg.size() + 32.0 * (double)h->S.m;
+            if (h->S.dense_matrix) {
+                // the device copy of A, the panel, the workspace of the factorisation and of the two dense kernels
+                const double need_d = 8.0 * ((double)h->S.n * (double)dense_lda(h->S.m) + (double)h->S.lval_len + (double)h->S.spart_len + (double)h->S.dinv_len +
+                                             2.0 * (double)h->S.gemv_chunks * (double)dense_lda(h->S.m) + 8.0 * (double)h->S.n + 12.0 * (double)h->S.m) +
+                                      (double)sizeof(UpdateTask) * (double)(h->S.update_tasks.size() + h->S.reduce_tasks.size()) +
+                                      (double)sizeof(TrsmTask) * (double)h->S.trsm_tasks.size() + (double)sizeof(ChainItem) * (double)h->S.chain_items.size();
+                if (need_d > budget) {
+                    h->last_error = "dense matrix: the device copy of A (" + std::to_string(8.0 * (double)h->S.n * (double)dense_lda(h->S.m)) + " bytes), the panel (" +
+                                    std::to_string(8.0 * (double)h->S.lval_len) + " bytes) and the workspace need " + std::to_string((long long)need_d) +
+                                    " bytes, budget " + std::to_string((long long)budget) + " bytes";
+                    rc = TLPK_TOO_LARGE;
+                }
+            } else
             if (need > budget) {
                 h->last_error = "factor needs " + std::to_string(need / 1e9) + " GB, budget " + std::to_string(budget / 1e9) + " GB";
                 if (h->S.system == 0 && !h->S.Ap.empty()) {
@@ -673,8 +696,13 @@ static int create_device(tlpk_handle *h, const tlpk_options &def) {
         if (rc == TLPK_OK) rc = upload_all(h);
         if (rc == TLPK_OK) h->has_device = true;
     } else if (def.mem_budget_bytes > 0) {
-        const double need = 8.0 * ((double)h->S.lval_len + (double)h->S.ubuf_len[0] + (double)h->S.ubuf_len[1]);
-        if (need > (double)def.mem_budget_bytes) { h->last_error = "factor exceeds mem_budget_bytes"; rc = TLPK_TOO_LARGE; }
+        const double need = 8.0 * ((double)h->S.lval_len + (double)h->S.ubuf_len[0] + (double)h->S.ubuf_len[1] +
+                                   (h->S.dense_matrix ? (double)h->S.n * (double)dense_lda(h->S.m) + (double)h->S.spart_len : 0.0));
+        if (need > (double)def.mem_budget_bytes) {
+            h->last_error = "factor exceeds mem_budget_bytes";
+            if (h->S.dense_matrix) h->last_error += ": " + std::to_string((long long)need) + " bytes needed (the device copy of A, the panel, the split-K scratch), budget " + std::to_string((long long)def.mem_budget_bytes) + " bytes";
+            rc = TLPK_TOO_LARGE;
+        }
     }
     return rc;
 }
@@ -704,6 +732,71 @@ int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr, 
         g_create_error = h->last_error;
         // no live handle on failure (a C caller that treats rc != 0 as "no handle" would leak the host symbolic data) -- unless the caller
         // asks for the analyse-only handle that describes what did not fit
+        if (!(rc == TLPK_TOO_LARGE && def.keep_on_too_large)) { tlpk_destroy(h); return rc; }
+    } else g_create_error.clear();
+    *out = h;
+    return rc;
+}
+
+// Dense constraint matrix: analyse_dense_matrix (one front, no lists), the ordinary device set-up, then A goes to the device
+// into a copy with a line-aligned leading dimension and zero padding rows.  Nothing of A stays on the host.
+int tlpk_create_dense(tlpk_handle **out, int64_t m, int64_t n, const double *A, int64_t lda, const tlpk_options *uopt) {
+    if (!out) return TLPK_BADARG;
+    *out = nullptr;
+    tlpk_options def;
+    tlpk_default_options(&def);
+    if (uopt) {
+        if (uopt->struct_size != (int32_t)sizeof(tlpk_options)) { g_create_error = "tlpk_create_dense: options.struct_size does not match this library"; return TLPK_BADARG; }
+        def = *uopt;
+    }
+    const char *bad = nullptr;
+    if (m < 1 || n < 0) bad = "m >= 1 and n >= 0 are required";
+    else if (!A && n > 0) bad = "A is NULL";
+    else if (lda < m) bad = "lda < m";
+    else if (def.system != TLPK_SYSTEM_K1) bad = "K1 only (the reference's dense solver factorises the normal equations)";
+    else if (def.nranks > 1 || def.rank != 0) bad = "one rank only (nranks = 1)";
+    else if (def.row_block || def.detect_blocks) bad = "row_block / detect_blocks do not apply (a dense matrix has no block structure)";
+    else if (def.user_perm) bad = "user_perm does not apply (the order is natural: a dense matrix has no fill to reduce)";
+    else if (def.dense_cols) bad = "dense_cols does not apply (every column is dense; the product is formed on the matrix cores)";
+    else if (def.refine_steps != 0) bad = "refine_steps > 0 is not supported (the refinement kernels read a sparse A)";
+    if (bad) { g_create_error = std::string("tlpk_create_dense: ") + bad; return TLPK_BADARG; }
+    tlpk_handle *h = new (std::nothrow) tlpk_handle();
+    if (!h) return TLPK_OOM;
+    int rc = TLPK_OK;
+    try {
+        h->opt = Options{};
+        h->opt.ordering = TLPK_ORDER_NATURAL;
+        h->profile = def.profile != 0;
+        if (const char *e = std::getenv("TLPK_SERIAL")) h->serial = std::atoi(e) != 0;
+        if (const char *e = std::getenv("TLPK_GRAPH")) h->use_graph = std::atoi(e) != 0;      // (one stream group: nothing beyond on / off)
+        if (const char *e = std::getenv("TLPK_POLL")) std::sscanf(e, "%d,%d,%d", &h->poll[0], &h->poll[1], &h->poll[2]);
+        const auto t0 = std::chrono::steady_clock::now();
+        rc = analyse_dense_matrix(h->S, m, n);
+        h->ms_analyse = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (!h->S.error.empty()) h->last_error = h->S.error;
+        if (rc == TLPK_OK) { find_markers(h); h->nlink = 0; h->first_link = h->S.m; }
+        if (rc == TLPK_OK) rc = create_device(h, def);
+        if (rc == TLPK_OK && h->has_device) {
+            h->has_device = false;                       // (until A is on the device)
+            const i64 ld = h->d.dlda;
+            double *dA = nullptr;
+            rc = dev_alloc(h, &dA, std::max<i64>(n, 1) * ld);
+            if (rc == TLPK_OK) {
+                hipError_t e = hipSuccess;
+                if (ld != m) e = hipMemset(dA, 0, (size_t)(std::max<i64>(n, 1) * ld) * 8);
+                if (e == hipSuccess && n > 0) e = hipMemcpy2D(dA, (size_t)ld * 8, A, (size_t)lda * 8, (size_t)m * 8, (size_t)n, hipMemcpyHostToDevice);
+                if (e == hipSuccess) e = hipDeviceSynchronize();
+                if (e != hipSuccess) rc = hip_fail(h, e, "upload of the dense matrix");
+            }
+            if (rc == TLPK_OK) { h->d.dA = dA; h->has_device = true; }
+        }
+    } catch (const std::bad_alloc &) {
+        rc = TLPK_OOM; h->last_error = "host out of memory during analyse";
+    } catch (...) {
+        rc = TLPK_INTERNAL; h->last_error = "unexpected exception";
+    }
+    if (rc != TLPK_OK) {
+        g_create_error = h->last_error;
         if (!(rc == TLPK_TOO_LARGE && def.keep_on_too_large)) { tlpk_destroy(h); return rc; }
     } else g_create_error.clear();
     *out = h;
@@ -760,6 +853,20 @@ void tlpk_destroy(tlpk_handle *h) {
 }
 
 // ---- update ----
+// Dense-matrix handles (tlpk_create_dense) have one front, one rank and nothing to reduce: the split-phase calls do not apply to them.  The composed
+// entry points run the same halves internally (Composed marks that).
+static int dense_no_split(tlpk_handle *h, const char *what) {
+    if (h && h->S.dense_matrix && !h->composed) {
+        h->last_error = std::string(what) + ": the split-phase calls do not apply to a dense-matrix handle (tlpk_create_dense)";
+        return TLPK_BADARG;
+    }
+    return TLPK_OK;
+}
+struct Composed {
+    tlpk_handle *h; bool old = false;
+    explicit Composed(tlpk_handle *h_) : h(h_) { if (h) { old = h->composed; h->composed = true; } }
+    ~Composed() { if (h) h->composed = old; }
+};
 static int update_async_wait(tlpk_handle *h);
 // everything of an update up to the reduction of the root panel, on the handle-owned copies of theta / regP / regD
 static int enq_update_local(tlpk_handle *h) {
@@ -777,6 +884,18 @@ static int enq_update_local(tlpk_handle *h) {
     }
     ++h->n_updates;
     if (h->d.n_chain_cnt > 0) HIPCHK(h, hipMemsetAsync(h->d.chain_cnt, 0, (size_t)h->d.n_chain_cnt * sizeof(unsigned), h->stream));     // tickets + completion counters of the chain launches
+    if (S.dense_matrix) {
+        // D, then the whole of S = A D A' + Rd on the matrix cores, straight into the panel of the one front (no zero-fill, no lists)
+        { ProfScope ps(h, TLPK_KC_ASSEMBLE); launch_compute_d(h->stream, S.n, h->d_theta, h->d_regP, h->d_D); }
+        {
+            ProfScope ps(h, TLPK_KC_ASSEMBLE);
+            launch_dense_syrk(h->stream, h->d, h->d_D, h->d_regD, h->d.ctx.Lval + S.fronts[0].loff, S.fronts[0].lda);
+            launch_single_factor(h->stream, h->d);       // (m = 1)
+        }
+        run_launches(h, S.factor_launches, 0, h->factor_marker);
+        HIPCHK(h, hipGetLastError());
+        return TLPK_OK;
+    }
     {
         ProfScope ps(h, TLPK_KC_ASSEMBLE);
         if (S.system == 1) launch_k2_diag(h->stream, user_n(h), h->d_theta, h->d_regP, h->d_D);      // D2 = [theta + regP ; 1]  (sqd.jl:44-50)
@@ -816,6 +935,7 @@ static int enq_update_finish(tlpk_handle *h, hipStream_t root_stream = nullptr) 
 }
 
 int tlpk_update_local(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
+    if (int g = dense_no_split(h, "tlpk_update_local")) return g;
     if (!h || !d_theta || !d_regP || !d_regD) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (!h->has_device) return TLPK_NO_DEVICE;
@@ -839,6 +959,7 @@ int tlpk_update_local(tlpk_handle *h, const double *d_theta, const double *d_reg
 }
 
 int tlpk_root_panel(tlpk_handle *h, double **d_ptr, int64_t *count) {
+    if (int g = dense_no_split(h, "tlpk_root_panel")) return g;
     if (!h || !d_ptr || !count) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (!h->has_device) return TLPK_NO_DEVICE;
@@ -850,6 +971,7 @@ int tlpk_root_panel(tlpk_handle *h, double **d_ptr, int64_t *count) {
 }
 
 int tlpk_root_copy(tlpk_handle *h, int which, int dir, double *d_buf) {
+    if (int g = dense_no_split(h, "tlpk_root_copy")) return g;
     if (!h || !d_buf || which < 0 || which > 2 || (dir != 0 && dir != 1)) return TLPK_BADARG;
     if (!h->has_device) return TLPK_NO_DEVICE;
     double *p = nullptr; int64_t n = 0;
@@ -901,6 +1023,7 @@ static int update_finish_wait(tlpk_handle *h) {
 }
 
 int tlpk_update_finish(tlpk_handle *h) {
+    if (int g = dense_no_split(h, "tlpk_update_finish")) return g;
     if (!h) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (int rc = update_finish_enqueue(h)) return rc;
@@ -960,6 +1083,7 @@ int tlpk_update_device_async(tlpk_handle *h, const double *d_theta, const double
 }
 
 int tlpk_update_device(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
+    Composed composed(h);
     if (int g = sharded_needs_split(h, "tlpk_update_device")) return g;
     if (!h || !h->sub.empty() || !h->has_device || !graph_usable(h)) {
         int rc = tlpk_update_local(h, d_theta, d_regP, d_regD);
@@ -1128,7 +1252,8 @@ static int enq_solve_local(tlpk_handle *h, const double *d_xip, const double *d_
         // (the give-up flag of an EARLIER solve must not fail this one; while the root front of an asynchronous update is still being factorised on its own stream the
         //  flag may be that update's: it stays)
         if (h->S.sweep && !h->root_pending) HIPCHK(h, hipMemsetAsync(h->d.ctx.info + 1, 0, sizeof(int), h->stream));
-        if (h->S.system == 1) launch_k2_rhs(h->stream, h->d, h->S.k2_n, d_xip, d_xid, 0, rhs_rank >= 0 ? rhs_rank : h->opt.rank);        // [xi_d ; xi_p] permuted (sqd.jl:62-66)
+        if (h->S.dense_matrix) { const double *q[1] = {d_xid}, *p[1] = {d_xip}; double *o[1] = {h->d.ctx.xw}; launch_dense_gemv_n(h->stream, h->d, h->d_D, q, p, o, 1); }   // xi_p + A (D .* xi_d); identity order
+        else if (h->S.system == 1) launch_k2_rhs(h->stream, h->d, h->S.k2_n, d_xip, d_xid, 0, rhs_rank >= 0 ? rhs_rank : h->opt.rank);        // [xi_d ; xi_p] permuted (sqd.jl:62-66)
         else if (h->S.n_dense > 0) { const double *p[2] = {d_xip, d_xip}, *q[2] = {d_xid, d_xid}; launch_dense_rhs(h->stream, h->d, h->d_D, p, q, 1); }
         else launch_rhs(h->stream, h->d, h->d_D, d_xip, d_xid, rhs_rank >= 0 ? rhs_rank : h->opt.rank);
         launch_single_solve(h->stream, h->d);
@@ -1142,7 +1267,13 @@ static int enq_solve_finish(tlpk_handle *h, double *d_dx, double *d_dy, const do
     run_launches(h, h->S.fwd_launches, h->fwd_marker, h->S.fwd_launches.size(), 0);
     if (h->S.system == 1 || h->S.n_dense > 0) { ProfScope ps(h, TLPK_KC_SPMV); launch_apply_signs(h->stream, h->d); }     // L S L' x = b: z = S y between the sweeps
     run_launches(h, h->S.bwd_launches, 0, h->S.bwd_launches.size(), 1);
-    if (h->S.system == 1) {
+    if (h->S.dense_matrix) {
+        // dy = the solution (identity order), dx = D .* (A' dy - xi_d)
+        ProfScope ps(h, TLPK_KC_SPMV);
+        HIPCHK(h, hipMemcpyAsync(d_dy, h->d.ctx.xw, (size_t)h->S.m * 8, hipMemcpyDeviceToDevice, h->stream));
+        const double *y[1] = {h->d.ctx.xw}, *q[1] = {d_xid}; double *o[1] = {d_dx};
+        launch_dense_gemv_t(h->stream, h->d, h->d_D, y, q, o, 1);
+    } else if (h->S.system == 1) {
         // multi-device mode: every shard stores the nodes it owns straight into the lead device's job-wide dx / dy
         ProfScope ps(h, TLPK_KC_SPMV);
         launch_k2_out(h->stream, h->d, h->S.k2_n, d_dx, h->shared_dy ? h->shared_dy : d_dy, 0, h->opt.rank, h->dx_local_only ? 1 : 0);
@@ -1160,6 +1291,7 @@ static int enq_solve_finish(tlpk_handle *h, double *d_dx, double *d_dy, const do
 }
 
 int tlpk_solve_local(tlpk_handle *h, const double *d_xip, const double *d_xid) {
+    if (int g = dense_no_split(h, "tlpk_solve_local")) return g;
     if (!h || !d_xip || !d_xid) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (!h->has_device) return TLPK_NO_DEVICE;
@@ -1176,6 +1308,7 @@ int tlpk_solve_local(tlpk_handle *h, const double *d_xip, const double *d_xid) {
 }
 
 int tlpk_root_rhs(tlpk_handle *h, double **d_ptr, int64_t *count) {
+    if (int g = dense_no_split(h, "tlpk_root_rhs")) return g;
     if (!h || !d_ptr || !count) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (!h->has_device) return TLPK_NO_DEVICE;
@@ -1185,6 +1318,7 @@ int tlpk_root_rhs(tlpk_handle *h, double **d_ptr, int64_t *count) {
 }
 
 int tlpk_solve_finish(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xid) {
+    if (int g = dense_no_split(h, "tlpk_solve_finish")) return g;
     if (!h || !d_dx || !d_dy || !d_xid) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (!h->has_device) return TLPK_NO_DEVICE;
@@ -1216,6 +1350,7 @@ static int solve_whole(tlpk_handle *h, double *d_dx, double *d_dy, const double 
 }
 
 int tlpk_solve_device(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
+    Composed composed(h);
     if (int g = sharded_needs_split(h, "tlpk_solve_device")) return g;
     const bool whole = h && h->sub.empty() && h->has_device && graph_usable_solve(h);
     int rc = whole ? solve_whole(h, d_dx, d_dy, d_xip, d_xid) : tlpk_solve_local(h, d_xip, d_xid);
@@ -1266,6 +1401,7 @@ static int refine_buffers(tlpk_handle *h) {
     return TLPK_OK;
 }
 int tlpk_refine_local(tlpk_handle *h, const double *d_dx, const double *d_dy, const double *d_xip, const double *d_xid) {
+    if (int g = dense_no_split(h, "tlpk_refine_local")) return g;
     if (!h || !d_dx || !d_dy || !d_xip || !d_xid) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (h->S.system == 1) { h->last_error = "iterative refinement: K1 only"; return TLPK_BADARG; }
@@ -1285,6 +1421,7 @@ int tlpk_refine_local(tlpk_handle *h, const double *d_dx, const double *d_dy, co
     return TLPK_OK;
 }
 int tlpk_refine_finish(tlpk_handle *h, double *d_dx, double *d_dy) {
+    if (int g = dense_no_split(h, "tlpk_refine_finish")) return g;
     if (!h || !d_dx || !d_dy) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (!h->has_device) return TLPK_NO_DEVICE;
@@ -1311,7 +1448,8 @@ static int enq_solve2_local(tlpk_handle *h, const double *const *xip, const doub
     {
         ProfScope ps(h, TLPK_KC_SPMV);
         if (h->S.n_sweep_flags > 0) HIPCHK(h, hipMemsetAsync(h->d.sweep_tickets, 0xFF, (size_t)h->d.sweep_reset_bytes2, h->stream));
-        if (k2) {
+        if (h->S.dense_matrix) { double *o[2] = {h->d.ctx.xw, h->d.ctx.xw + h->d.ctx.xw2}; launch_dense_gemv_n(h->stream, h->d, h->d_D, xid, xip, o, 2); }
+        else if (k2) {
             for (int r = 0; r < 2; ++r) launch_k2_rhs(h->stream, h->d, h->S.k2_n, xip[r], xid[r], r, rank);
         } else if (h->S.n_dense > 0) launch_dense_rhs(h->stream, h->d, h->d_D, xip, xid, 2);
         else launch_rhs2(h->stream, h->d, h->d_D, xip, xid, rank);          // both right-hand sides in one launch each (round 6)
@@ -1329,6 +1467,11 @@ static int enq_solve2_finish(tlpk_handle *h, double *const *dx, double *const *d
     run_launches(h, h->S.bwd_launches, 0, h->S.bwd_launches.size(), 1, 2);
     {
         ProfScope ps(h, TLPK_KC_SPMV);
+        if (h->S.dense_matrix) {
+            const double *y[2] = {h->d.ctx.xw, h->d.ctx.xw + h->d.ctx.xw2};
+            for (int r = 0; r < 2; ++r) HIPCHK(h, hipMemcpyAsync(dy[r], y[r], (size_t)h->S.m * 8, hipMemcpyDeviceToDevice, h->stream));
+            launch_dense_gemv_t(h->stream, h->d, h->d_D, y, xid, dx, 2);
+        } else
         if (k2) { for (int r = 0; r < 2; ++r) launch_k2_out(h->stream, h->d, h->S.k2_n, dx[r], dy[r], r, h->opt.rank, 0); }
         else if (h->S.n_dense > 0) launch_dense_out(h->stream, h->d, h->d_D, dy, xid, dx, 2);
         else if (h->shared_dy || h->dx_local_only) {                              // (shards of a multi-device handle publish into the lead's vectors: per right-hand side)
@@ -1382,6 +1525,7 @@ int tlpk_solve2_device(tlpk_handle *h, double *d_dx0, double *d_dy0, const doubl
 // The pair in two halves, for sharded handles: tlpk_solve2_local -> all-reduce of tlpk_root_rhs AND tlpk_root_rhs2 (the root right-hand
 // sides of the two systems; one collective over both buffers if the communicator allows) -> tlpk_solve2_finish.
 int tlpk_solve2_local(tlpk_handle *h, const double *d_xip0, const double *d_xid0, const double *d_xip1, const double *d_xid1) {
+    if (int g = dense_no_split(h, "tlpk_solve2_local")) return g;
     if (!h || !d_xip0 || !d_xid0 || !d_xip1 || !d_xid1) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (!h->has_device) return TLPK_NO_DEVICE;
@@ -1399,6 +1543,7 @@ int tlpk_solve2_local(tlpk_handle *h, const double *d_xip0, const double *d_xid0
     return TLPK_OK;
 }
 int tlpk_root_rhs2(tlpk_handle *h, double **d_ptr, int64_t *count) {
+    if (int g = dense_no_split(h, "tlpk_root_rhs2")) return g;
     if (!h || !d_ptr || !count) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (!h->has_device) return TLPK_NO_DEVICE;
@@ -1407,6 +1552,7 @@ int tlpk_root_rhs2(tlpk_handle *h, double **d_ptr, int64_t *count) {
     return TLPK_OK;
 }
 int tlpk_solve2_finish(tlpk_handle *h, double *d_dx0, double *d_dy0, const double *d_xid0, double *d_dx1, double *d_dy1, const double *d_xid1) {
+    if (int g = dense_no_split(h, "tlpk_solve2_finish")) return g;
     if (!h || !d_dx0 || !d_dy0 || !d_xid0 || !d_dx1 || !d_dy1 || !d_xid1) return TLPK_BADARG;
     if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
     if (!h->has_device) return TLPK_NO_DEVICE;
@@ -2090,6 +2236,7 @@ int tlpk_info(const tlpk_handle *h, tlpk_stats *out) {
     out->refine_rejected = h->refine_rejected;
     out->root_panel_len = (S.root_front >= 0) ? pk_len(S.fronts[S.root_front].lda, S.fronts[S.root_front].ns) : 0;
     out->n_dense_cols = S.n_dense;
+    out->flops_syrk = S.flops_syrk;
     return TLPK_OK;
 }
 

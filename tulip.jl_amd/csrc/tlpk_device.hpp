@@ -46,6 +46,11 @@ struct DevArrays {
     // K1 with dense columns (tlpk_options.dense_cols): sparse_col[j] = 1 for a column formed into A_s D_s A_s', 0 for a dense one;
     // dense_col[t] = the column of node mu + t
     char *sparse_col = nullptr; i32 *dense_col = nullptr; i64 n_dense = 0;
+    // dense-matrix handle (tlpk_create_dense): A column-major with leading dimension dlda (tlpk_host.hpp: dense_lda), padding rows zero; then the
+    // CSC / CSR arrays below and the assembly lists stay null.  Launch geometry of the dense kernels from analyse_dense_matrix
+    const double *dA = nullptr; i64 dlda = 0;
+    i32 syrk_split = 1; i64 syrk_kc = 0;
+    double *gemv_part = nullptr; i64 gemv_chunks = 0, gemv_cw = 0;      // k_dense_gemv_n: [2][chunks][dlda] partial sums
     // A (CSC + CSR)
     i64 *Ap = nullptr; i32 *Ai = nullptr; double *Ax = nullptr;
     i64 *Tp = nullptr; i32 *Tj = nullptr; double *Tx = nullptr;
@@ -115,5 +120,11 @@ void launch_k2_out(hipStream_t st, const DevArrays &a, i64 n, double *dx, double
 void launch_dense_diag(hipStream_t st, const DevArrays &a, const double *theta, const double *regP, double *D);
 void launch_dense_rhs(hipStream_t st, const DevArrays &a, const double *D, const double *const *xi_p, const double *const *xi_d, int nrhs);
 void launch_dense_out(hipStream_t st, const DevArrays &a, const double *D, double *const *dy, const double *const *xi_d, double *const *dx, int nrhs);
+// dense-matrix handles (dense_kernels.hip).  S = A diag(D) A' + diag(regD), lower triangle, into the packed panel P (leading dimension plda)
+void launch_dense_syrk(hipStream_t st, const DevArrays &a, const double *D, const double *regD, double *P, i32 plda);
+// out[r] = add[r] + A (D .* x[r])  (D, add[r] may be null), r < nrhs <= 2: one pass over A
+void launch_dense_gemv_n(hipStream_t st, const DevArrays &a, const double *D, const double *const *x, const double *const *add, double *const *out, int nrhs);
+// out[r] = D .* (A' y[r] - xi_d[r])  (D null: A' y[r]), r < nrhs <= 2: one pass over A
+void launch_dense_gemv_t(hipStream_t st, const DevArrays &a, const double *D, const double *const *y, const double *const *xi_d, double *const *out, int nrhs);
 
 }  // namespace tlpk

@@ -90,6 +90,8 @@ struct tlpk_handle {
     std::vector<hipGraphExec_t> graph_execs;
     std::vector<std::vector<char>> graph_keys;
     IpmState *ipm = nullptr;            // device-resident interior-point vectors (tlpk_ipm_load), freed by tlpk_destroy
+    bool composed = false;              // dense-matrix handles: a composed entry point (tlpk_update_device, tlpk_solve_device) is running its two halves -- the
+                                        // split-phase calls themselves are refused on such a handle (tlpk_api.cpp: dense_no_split)
     std::string last_error;
 };
 

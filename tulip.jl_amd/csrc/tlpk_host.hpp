@@ -157,6 +157,14 @@ struct Symbolic {
     // K1 with dense columns (analyse_dense): m = order m_user + n_dense of the factored matrix, n / nnzA / Ap ... = the caller's A (K1 layout: what the
     // solve, refinement and device-resident kernels read); node m_user + t = column dense_cols[t] (ascending), csign -1 there
     i64 n_dense = 0, dense_n = 0;        // dense_n: the caller's n (= the leading columns of the incidence matrix while it is analysed)
+    // dense-MATRIX handle (tlpk_create_dense, analyse_dense_matrix): A is a column-major m x n array on the device, S = A D A' + Rd is one dense
+    // front formed by k_dense_syrk (dense_kernels.hip).  No CSC / CSR copy of A, no pattern of S, no assembly lists: Ap ... Tpos, Si, pair_* stay empty
+    i32 dense_matrix = 0;
+    i64 syrk_slots = 0;                  // split-K parts of k_dense_syrk: TILE x TILE doubles each in the split-K scratch (spart)
+    i32 syrk_split = 1;                  // K (= n) parts per tile of the lower triangle (1: the tiles go straight into the panel)
+    i64 syrk_kc = 16;                    // columns per part, a multiple of 16
+    i64 gemv_chunks = 0;                 // column chunks of k_dense_gemv_n (partial sums per chunk, summed in chunk order)
+    double flops_syrk = 0;               // n m (m + 1): 2 flops per product of the lower triangle
     std::vector<i64> dense_cols;
     // A, CSC and CSR (0-based, int32 indices); csr_pos[q] = CSC position of the CSR entry q
     std::vector<i64> Ap; std::vector<i32> Ai; std::vector<double> Ax;
@@ -256,5 +264,12 @@ int analyse_k2(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowval, 
 // entry of a dense column: A[i,j] on row i, 1 on node m + t); afterwards S.Ap ... hold A itself.  One rank.
 int analyse_dense(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowval, const double *nzval,
                   int index_base, const Options &opt, const std::vector<i64> &dense);
+// Dense constraint matrix (tlpk_create_dense): natural order, ONE front of m columns built directly -- what the analyse phase would find for a
+// matrix without zeros, without forming the m (m + 1) / 2 entries of the pattern or the n m (m + 1) / 2 products of the assembly lists.  The
+// factorisation and solve schedules are those of build_schedule for that front; host memory O(m + schedule).  Needs only the shape of A.
+int analyse_dense_matrix(Symbolic &S, i64 m, i64 n);
+// launch geometry of the dense kernels (shared by analyse_dense_matrix and dense_kernels.hip)
+constexpr int DGEMV_ROWS = 512;    // rows per k_dense_gemv_n workgroup (256 threads x 2 rows)
+inline i64 dense_lda(i64 m) { return (m + 15) / 16 * 16; }     // leading dimension of the device copy of A: columns start on 128-byte lines, padding rows are zero
 
 }  // namespace tlpk

@@ -130,6 +130,14 @@ int solve_all(tlpk_handle *h, Shards &sh, F &&pick) {
 
 }  // namespace
 
+// dense-matrix handle: A'y and / or A x of the current iterate into the vectors the residual kernels read
+static void dense_products(tlpk_handle *c, bool cols, bool rows) {
+    if (!c->S.dense_matrix) return;
+    const IpmVecs &v = c->ipm->v;
+    if (cols) { const double *y[1] = {v.y}, *none[1] = {nullptr}; double *o[1] = {const_cast<double *>(v.aty)}; launch_dense_gemv_t(c->stream, c->d, nullptr, y, none, o, 1); }
+    if (rows) { const double *x[1] = {v.x}, *none[1] = {nullptr}; double *o[1] = {const_cast<double *>(v.ax)}; launch_dense_gemv_n(c->stream, c->d, nullptr, x, none, o, 1); }
+}
+
 void ipm_free(tlpk_handle *h) {
     if (!h || !h->ipm) return;
     if (h->ipm->h_out) hipHostFree(h->ipm->h_out);
@@ -186,14 +194,21 @@ static int ipm_load_impl(tlpk_handle *h, const double *b, const double *c, const
     h->ipm = sp;
     IpmState &s = *sp;
     IpmVecs &v = s.v;
-    v.m = m; v.n = n; v.row_skip = nullptr;
+    v.m = m; v.n = n; v.row_skip = nullptr; v.aty = nullptr; v.ax = nullptr;
     int rc;
     const Symbolic &S = h->S;
     // ownership of columns (variables) and rows (constraints) on a shard: K1 -- the column / row maps of the analyse phase; K2 -- the
     // node map (variable nodes 0 .. n-1, constraint nodes n .. n+m-1): a node of the replicated root front belongs to the lead shard
     auto own_col = [&](i64 j) { if (!shard) return true; if (!k2) return S.col_local[(size_t)j] != 0; const char nl = S.row_local[(size_t)j]; return nl == 1 || (nl == 2 && h->opt.rank == 0); };
     auto row_kind = [&](i64 i) -> char { return k2 ? S.row_local[(size_t)(n + i)] : S.row_local[(size_t)i]; };      // 0 other shard, 1 own, 2 linking (replicated)
-    if (!shard && !k2) { v.Ap = h->d.Ap; v.Ai = h->d.Ai; v.Ax = h->d.Ax; v.Tp = h->d.Tp; v.Tj = h->d.Tj; v.Tx = h->d.Tx; }
+    if (h->S.dense_matrix) {
+        // no index arrays for a dense A (they would cost 12 m n bytes beside the 8 m n of A): the kernels read A'y and A x from two vectors
+        // that dense_products() fills with the GEMV kernels of the solves
+        double *p1, *p2;
+        if ((rc = dev_alloc(h, &p1, n)) != TLPK_OK) return rc;
+        if ((rc = dev_alloc(h, &p2, m)) != TLPK_OK) return rc;
+        v.aty = p1; v.ax = p2;
+    } else if (!shard && !k2) { v.Ap = h->d.Ap; v.Ai = h->d.Ai; v.Ax = h->d.Ax; v.Tp = h->d.Tp; v.Tj = h->d.Tj; v.Tx = h->d.Tx; }
     else {
         // host copy of A, column-major: K1 -- the analyse phase's copy; K2 -- rebuilt from the incidence matrix of the augmented system
         // it holds (column p = entry p of A: 1 on variable node j, A[i,j] on constraint node n + i, in A's column-major entry order).
@@ -293,6 +308,7 @@ int tlpk_ipm_residuals(tlpk_handle *h, double tau, double *out) {
     for (int r = 0; r < sh.n; ++r) {
         tlpk_handle *c = sh.c[r]; IpmState &s = *c->ipm;
         HIPCHK(h, hipSetDevice(c->device));
+        dense_products(c, true, true);
         const int nbc = ipm_launch_res_cols(c->stream, s.v, tau, s.partials[0]);
         const int nbr = ipm_launch_res_rows(c->stream, s.v, tau, s.partials[1]);
         ipm_launch_finalize(c->stream, nbc, 4, 6, 0, s.partials[0], s.d_out);
@@ -576,6 +592,7 @@ int tlpk_mpc_start(tlpk_handle *h, double *out) {
         for (int r = 0; r < sh.n; ++r) {
             tlpk_handle *c = sh.c[r]; IpmState &s = *c->ipm;
             HIPCHK(h, hipSetDevice(c->device));
+            if (st == 2) dense_products(c, true, false);
             const int nb = mpc_launch_start(c->stream, s.v, st, a, b, s.partials[0]);
             ipm_launch_finalize(c->stream, nb, nsum, 0, nmin, s.partials[0], s.d_out);
         }

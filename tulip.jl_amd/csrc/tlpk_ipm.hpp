@@ -28,6 +28,8 @@ struct IpmVecs {
     double *hxid;                                         // its right-hand side c - th_l lz - th_u uz (own vector: the h-system and the
                                                           // predictor are solved as a pair, tlpk_ipm_hsolve_newton)
     double *xil, *xiu, *xzl, *xzu, *xid, *xip;            // right-hand sides of the current Newton system
+    const double *aty, *ax;                               // dense-matrix handles (A is not stored as CSC / CSR: Ap ... Tx are null): A'y (n) and A x (m), formed by
+                                                          // k_dense_gemv_t / k_dense_gemv_n in front of the kernels that need them; else nullptr
     const char *row_skip;                                 // shard of a multi-device handle: 1 on the linking rows (partial sums there: no part in the maxima); else nullptr
 };
 

@@ -17,7 +17,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .kkt import K1, K2, Backend, DimensionMismatch, OutOfMemoryError, PosDefException, _raise_for, setup
+from .kkt import K1, K2, Backend, DenseBackend, DimensionMismatch, OutOfMemoryError, PosDefException, _raise_for, setup
 
 SQRT_EPS = float(np.sqrt(np.finfo(np.float64).eps))
 INF = float("inf")
@@ -36,7 +36,8 @@ class Options:
 
 
 class DeviceHSD:
-    def __init__(self, A, b, c, l, u, c0=0.0, objsense_min=True, options=None, system="K1", pair_solves=True, overlap_root=False, **backend_kw):
+    def __init__(self, A, b, c, l, u, c0=0.0, objsense_min=True, options=None, system="K1", pair_solves=True, overlap_root=False, dense=False, **backend_kw):
+        # dense: A is a dense 2-D array and goes to the dense backend (tlpk_create_dense; K1, one device: device, profile, mem_budget_bytes)
         # pair_solves: the h-system and the predictor share one pass over the factor (tlpk_ipm_hsolve_newton; same arithmetic)
         # overlap_root: the factorisation does not wait for its status before that pair is enqueued (tlpk_ipm_factor_hsolve_newton);
         # off by default: the root front's serial chain beside the chip-filling sweeps measured 1.1 ms slower per step on C4
@@ -49,7 +50,12 @@ class DeviceHSD:
         if int(backend_kw.get("nranks", 1)) > 1:
             raise ValueError("the device-resident interior-point loops need one handle for the whole LP: nranks must be 1 "
                              "(ngpus > 1 is fine; sharded handles serve the split-phase KKT.update! / KKT.solve!)")
-        self.kkt = setup(A, K2() if str(system).upper() == "K2" else K1(), Backend(**backend_kw))
+        if dense:
+            if str(system).upper() == "K2":
+                raise TypeError("the dense backend solves the normal equations (K1) only")
+            self.kkt = setup(A, K1(), DenseBackend(**backend_kw))
+        else:
+            self.kkt = setup(A, K2() if str(system).upper() == "K2" else K1(), Backend(**backend_kw))
         self.m, self.n = self.kkt.m, self.kkt.n
         self.opt = options or Options()
         self._b = np.ascontiguousarray(b, dtype=np.float64); self._c = np.ascontiguousarray(c, dtype=np.float64)

@@ -61,6 +61,25 @@ function Backend(; device::Int=0, row_block=nothing, streams::Int=0, ngpus::Int=
 end
 
 """
+    DenseBackend(; device=0, profile=false, mem_budget_bytes=0)
+
+The dense counterpart, selected like `TlpDense.Backend` (`/root/reference/src/KKT/Dense/lapack.jl:17`) together with
+`MatrixFactory = Factory(Matrix)` and `KKT_System = K1()`: `A` stays a `Matrix{Float64}`, `A·D·Aᵀ + Rd` is formed on the fp64
+matrix cores into one dense front (no scaled copy of `A`, no pattern, no assembly lists) and factorised by the blocked dense
+Cholesky of the sparse handles.  `K1` only, one GPU.
+
+    set_parameter(model, "MatrixFactory", Tulip.Factory(Matrix))
+    set_parameter(model, "KKT_Backend", Tulip.KKT.TlpHIP.DenseBackend())
+    set_parameter(model, "KKT_System",  Tulip.KKT.K1())
+"""
+struct DenseBackend <: AbstractKKTBackend
+    device::Int
+    profile::Bool
+    mem_budget_bytes::Int
+end
+DenseBackend(; device::Int=0, profile::Bool=false, mem_budget_bytes::Int=0) = DenseBackend(device, profile, mem_budget_bytes)
+
+"""
     BlockAngularMatrix(A, row_block)
 
 Tulip's structured-matrix hook (`/root/reference/src/parameters.jl:11` `MatrixFactory`,
@@ -114,7 +133,7 @@ Supported arithmetic: `Float64`.
 mutable struct HIPNormalEquations <: AbstractKKTSolver{Float64}
     m::Int
     n::Int
-    A::SparseMatrixCSC{Float64,Int}   # kept by reference like cholmod.jl:50; never mutated
+    A::Union{SparseMatrixCSC{Float64,Int},Matrix{Float64}}   # kept by reference like cholmod.jl:50 / lapack.jl:47; never mutated
     handle::Ptr{Cvoid}
 
     function HIPNormalEquations(m, n, A, handle)
@@ -164,6 +183,16 @@ function setup(A::SparseMatrixCSC{Float64,Int}, system::Union{K1,K2}, b::Backend
     rc == LibTLPK.TLPK_OK || (h == C_NULL || LibTLPK.destroy(h); _check(rc, C_NULL, "KKT.setup"))
     return HIPNormalEquations(m, n, A, h)
 end
+
+# Dense constraint matrix (lapack.jl:52-63): the handle of tlpk_create_dense behaves like any single-device K1 handle
+function setup(A::Matrix{Float64}, ::K1, b::DenseBackend)
+    m, n = size(A)
+    rc, h = LibTLPK.create_dense(A; device=b.device, profile=b.profile, mem_budget_bytes=b.mem_budget_bytes)
+    rc == LibTLPK.TLPK_OK || (h == C_NULL || LibTLPK.destroy(h); _check(rc, C_NULL, "KKT.setup"))
+    return HIPNormalEquations(m, n, A, h)
+end
+setup(A::AbstractMatrix, system::K1, b::DenseBackend) = setup(Matrix{Float64}(A), system, b)
+setup(::AbstractMatrix, ::K2, ::DenseBackend) = throw(ArgumentError("TlpHIP.DenseBackend solves the normal equations (K1) only"))
 
 function update!(kkt::HIPNormalEquations, θ::Vector{Float64}, regP::Vector{Float64}, regD::Vector{Float64})
     m, n = kkt.m, kkt.n

@@ -112,6 +112,26 @@ function create(m::Int, n::Int, colptr::Vector{Int}, rowval::Vector{Int}, nzval:
     return rc, h[]
 end
 
+"""
+    create_dense(A; device, profile, mem_budget_bytes) -> (rc, Ptr{Cvoid})
+
+`tlpk_create_dense`: a dense column-major `Matrix{Float64}` (leading dimension = its number of rows); K1 only, one GPU.  The
+library copies `A` to the device; nothing is retained.
+"""
+function create_dense(A::Matrix{Float64}; device::Integer=0, profile::Bool=false, mem_budget_bytes::Integer=0)
+    m, n = size(A)
+    opt = Options()
+    opt.struct_size = Int32(sizeof(Options))
+    opt.device = Int32(device)
+    opt.profile = Int32(profile)
+    opt.mem_budget_bytes = Int64(mem_budget_bytes)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = GC.@preserve A opt ccall((:tlpk_create_dense, libtlpk[]), Cint,
+        (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Float64}, Int64, Ref{Options}),
+        h, m, n, A, max(m, 1), opt)
+    return rc, h[]
+end
+
 destroy(h::Ptr{Cvoid}) = ccall((:tlpk_destroy, libtlpk[]), Cvoid, (Ptr{Cvoid},), h)
 
 """

@@ -86,6 +86,20 @@ class Backend:
         self.dense_col_min = int(dense_col_min)
 
 
+class DenseBackend:
+    """`TlpHIP.DenseBackend`: the analogue of `TlpDense.Backend` (/root/reference/src/KKT/Dense/lapack.jl:17) -- `A` is a dense
+    matrix, `A*D*A' + Rd` is formed on the fp64 matrix cores into one dense front and factorised by the blocked dense
+    Cholesky of the sparse handles.  K1 only, one GPU; no pattern of `A*D*A'` and no assembly lists are built."""
+
+    def __init__(self, device=0, profile=False, mem_budget_bytes=0):
+        self.device = int(device)
+        self.profile = bool(profile)
+        self.mem_budget_bytes = int(mem_budget_bytes)
+        # what the shared code of HIPNormalEquations and the test tools read from a backend object
+        self.rank, self.nranks, self.ngpus = 0, 1, 1
+        self.refine = 0
+
+
 def detect_blocks(A, max_link_rows=0):
     """tlpk_detect_blocks on a scipy sparse matrix: (row_block, n_blocks, n_link); n_blocks == 1: no block structure."""
     import scipy.sparse as sp
@@ -305,10 +319,52 @@ class HIPNormalEquations:
             pass
 
 
+class HIPDenseNormalEquations(HIPNormalEquations):
+    """`setup(A::Matrix{Float64}, ::K1, ::DenseBackend)`: a handle of `tlpk_create_dense`; everything else is inherited."""
+
+    def __init__(self, A, backend_):
+        import scipy.sparse as sp
+        if sp.issparse(A):
+            raise TypeError("DenseBackend takes a dense 2-D array; a sparse matrix goes to Backend")
+        A = np.asarray(A)
+        if A.ndim != 2:
+            raise TypeError("DenseBackend takes a 2-D array")
+        # column-major float64: a Fortran-ordered array (or a view into one with unit row stride) is passed as it is, anything else is copied once
+        s0, s1 = A.strides
+        if not (A.dtype == np.float64 and A.flags.aligned and A.shape[0] >= 1 and s0 == 8 and (A.shape[1] <= 1 or (s1 % 8 == 0 and s1 >= 8 * A.shape[0]))):
+            A = np.asfortranarray(A, dtype=np.float64)
+        self.m, self.n = A.shape
+        lda = max(self.m, 1) if self.n <= 1 else A.strides[1] // 8
+        self.A = A                                                # stored by reference, never mutated
+        self.system = _lib.SYSTEM_K1
+        self._keep = []
+        L = _lib.lib()
+        opt = _lib.Options()
+        L.tlpk_default_options(C.byref(opt))
+        opt.device = backend_.device
+        opt.profile = int(backend_.profile)
+        opt.mem_budget_bytes = backend_.mem_budget_bytes
+        self._h = C.c_void_p()
+        rc = L.tlpk_create_dense(C.byref(self._h), self.m, self.n, A.ctypes.data_as(_lib.pd), lda, C.byref(opt))
+        if rc != _lib.OK:
+            h = self._h if self._h else None
+            try:
+                _raise_for(rc, h, "KKT.setup: ")
+            finally:
+                if self._h:
+                    L.tlpk_destroy(self._h)
+                    self._h = C.c_void_p()
+        self.backend_options = backend_
+
+
 def setup(A, system=None, backend_=None):
     """KKT.setup(A, ::K1, ::TlpHIP.Backend)  (KKT.jl:59, spd.jl:5-20).  Runs the analyse phase on
     the host and uploads the symbolic structures; skips the throw-away numeric factorisation of
     spd.jl:14-17."""
+    if isinstance(backend_, DenseBackend):
+        if not (system is None or isinstance(system, K1) or system is K1):
+            raise TypeError("the dense backend solves the normal equations (K1) only")
+        return HIPDenseNormalEquations(A, backend_)
     if system is None or isinstance(system, K1) or system is K1:
         return HIPNormalEquations(A, backend_ or Backend())
     if isinstance(system, K2) or system is K2:
@@ -373,7 +429,7 @@ def run_ls_tests(A, kkt, atol=SQRT_EPS):
     both residual infinity-norms <= atol.  Returns (rp_norm, rd_norm)."""
     import scipy.sparse as sp
     assert callable(update) and callable(solve)          # test.jl:19-20 hasmethod checks
-    Ad = A if sp.issparse(A) else sp.csc_matrix(np.asarray(A, dtype=np.float64))
+    Ad = A if sp.issparse(A) or isinstance(kkt, HIPDenseNormalEquations) else sp.csc_matrix(np.asarray(A, dtype=np.float64))
     m, n = Ad.shape
     th = np.ones(n); rp = np.ones(n); rd = np.ones(m)
     update(kkt, th, rp, rd)                              # test.jl:26-29
