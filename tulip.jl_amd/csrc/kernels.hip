@@ -4266,11 +4266,12 @@ void launch_single_factor(hipStream_t st, const DevArrays &a) {
         hipLaunchKernelGGL(k_single_factor, dim3(nblk(a.n_single, 256)), dim3(256), 0, st, a.n_single, a.single_loff, a.single_dinvoff,
                            a.single_col, a.ctx.Lval, a.ctx.dinv, a.ctx.info, a.ctx.csign);
 }
-// rhs: 0 / 1 = that right-hand side, 2 = both in one launch (grid y)
-void launch_single_solve(hipStream_t st, const DevArrays &a, int rhs) {
+// The launchers of the per-right-hand-side solve kernels: `nrhs` right-hand sides (1, or the 2 of a pair) in slots 0 .. nrhs - 1 of xw; pointer arrays hold one entry
+// per right-hand side.  Kernels with a grid-y form take both in one launch (grid y = right-hand side), the K2 kernels are launched once each.
+void launch_single_solve(hipStream_t st, const DevArrays &a, int nrhs) {
     if (a.n_single > 0)
-        hipLaunchKernelGGL(k_single_solve, dim3(nblk(a.n_single, 256), rhs == 2 ? 2u : 1u), dim3(256), 0, st, a.n_single, a.single_dinvoff, a.single_col,
-                           a.ctx.dinv, a.ctx.xw + (rhs == 1 ? a.ctx.xw2 : 0), a.ctx.xw2);
+        hipLaunchKernelGGL(k_single_solve, dim3(nblk(a.n_single, 256), (unsigned)nrhs), dim3(256), 0, st, a.n_single, a.single_dinvoff, a.single_col,
+                           a.ctx.dinv, a.ctx.xw, a.ctx.xw2);
 }
 // nrhs = 2 (solve schedules only): the two persistent sweep kernels run their two-right-hand-side instances (one pass over L for
 // both), every other solve kernel is launched once per right-hand side (the second on a context whose xw / uc point at the copies)
@@ -4415,14 +4416,17 @@ void launch_tasks(hipStream_t st, const DevArrays &a, const Launch &L, const Swe
 void launch_k2_diag(hipStream_t st, i64 n, const double *theta, const double *regP, double *D2) {
     hipLaunchKernelGGL(k_k2_diag, dim3(nblk(n + 1, 256)), dim3(256), 0, st, n, theta, regP, D2);
 }
-void launch_k2_rhs(hipStream_t st, const DevArrays &a, i64 n, const double *xi_p, const double *xi_d, int rhs, int rank) {
-    if (a.m > 0) hipLaunchKernelGGL(k_k2_rhs, dim3(nblk(a.m, 256)), dim3(256), 0, st, a.m, n, a.perm, a.row_local, rank, xi_p, xi_d, a.ctx.xw + (rhs ? a.ctx.xw2 : 0));
+void launch_k2_rhs(hipStream_t st, const DevArrays &a, i64 n, const double *const *xi_p, const double *const *xi_d, int rank, int nrhs) {
+    for (int r = 0; r < nrhs && a.m > 0; ++r)
+        hipLaunchKernelGGL(k_k2_rhs, dim3(nblk(a.m, 256)), dim3(256), 0, st, a.m, n, a.perm, a.row_local, rank, xi_p[r], xi_d[r], a.ctx.xw + (r ? a.ctx.xw2 : 0));
 }
-void launch_apply_signs(hipStream_t st, const DevArrays &a, int rhs) {
-    if (a.m > 0) hipLaunchKernelGGL(k_apply_signs, dim3(nblk(a.m, 256)), dim3(256), 0, st, a.m, a.ctx.csign, a.ctx.xw + (rhs ? a.ctx.xw2 : 0));
+void launch_apply_signs(hipStream_t st, const DevArrays &a, int nrhs) {
+    for (int r = 0; r < nrhs && a.m > 0; ++r)
+        hipLaunchKernelGGL(k_apply_signs, dim3(nblk(a.m, 256)), dim3(256), 0, st, a.m, a.ctx.csign, a.ctx.xw + (r ? a.ctx.xw2 : 0));
 }
-void launch_k2_out(hipStream_t st, const DevArrays &a, i64 n, double *dx, double *dy, int rhs, int rank, int owned_only) {
-    if (a.m > 0) hipLaunchKernelGGL(k_k2_out, dim3(nblk(a.m, 256)), dim3(256), 0, st, a.m, n, a.perm, a.row_local, rank, owned_only, a.ctx.xw + (rhs ? a.ctx.xw2 : 0), dx, dy);
+void launch_k2_out(hipStream_t st, const DevArrays &a, i64 n, double *const *dx, double *const *dy, int rank, int owned_only, int nrhs) {
+    for (int r = 0; r < nrhs && a.m > 0; ++r)
+        hipLaunchKernelGGL(k_k2_out, dim3(nblk(a.m, 256)), dim3(256), 0, st, a.m, n, a.perm, a.row_local, rank, owned_only, a.ctx.xw + (r ? a.ctx.xw2 : 0), dx[r], dy[r]);
 }
 void launch_dense_diag(hipStream_t st, const DevArrays &a, const double *theta, const double *regP, double *D) {
     hipLaunchKernelGGL(k_dense_diag, dim3(nblk(a.n + 1, 256)), dim3(256), 0, st, a.n, a.sparse_col, theta, regP, D);
@@ -4441,29 +4445,12 @@ void launch_dense_out(hipStream_t st, const DevArrays &a, const double *D, doubl
         hipLaunchKernelGGL(k_dx, dim3(nblk(a.n, 256), (unsigned)nrhs), dim3(256), 0, st, a.n, a.Ap, a.Ai, a.Ax, D, dy[0], xi_d[0], a.sparse_col, dx[0], 1,
                            dy[1], xi_d[1], dx[1]);
 }
-void launch_rhs(hipStream_t st, const DevArrays &a, const double *D, const double *xi_p, const double *xi_d, int rank, int rhs) {
-    if (a.m > 0)
-    {
-        double *w = a.rhs_w + (rhs ? a.n : 0);
-        if (a.n > 0) hipLaunchKernelGGL(k_rhs_scale, dim3(nblk(a.n, 256)), dim3(256), 0, st, a.n, D, xi_d, a.col_local, w, xi_d);
-        hipLaunchKernelGGL(k_rhs, dim3(nblk(a.m * 8, 256)), dim3(256), 0, st, a.m, a.perm, a.Pp, a.Pj, a.Px, w, xi_p, xi_d,
-                           a.row_local, a.col_local, rank, a.ctx.xw + (rhs ? a.ctx.xw2 : 0), xi_p, (i64)0, (i64)0);
-    }
-}
-// both right-hand sides of a pair in one launch each (grid y)
-void launch_rhs2(hipStream_t st, const DevArrays &a, const double *D, const double *const *xi_p, const double *const *xi_d, int rank) {
-    if (a.m > 0)
-    {
-        if (a.n > 0) hipLaunchKernelGGL(k_rhs_scale, dim3(nblk(a.n, 256), 2), dim3(256), 0, st, a.n, D, xi_d[0], a.col_local, a.rhs_w, xi_d[1]);
-        hipLaunchKernelGGL(k_rhs, dim3(nblk(a.m * 8, 256), 2), dim3(256), 0, st, a.m, a.perm, a.Pp, a.Pj, a.Px, a.rhs_w, xi_p[0], xi_d[0],
-                           a.row_local, a.col_local, rank, a.ctx.xw, xi_p[1], a.n, a.ctx.xw2);
-    }
-}
-void launch_unpermute2(hipStream_t st, const DevArrays &a, double *const *dy, int rank) {
-    if (a.m > 0) hipLaunchKernelGGL(k_unpermute, dim3(nblk(a.m, 256), 2), dim3(256), 0, st, a.m, a.perm, a.row_local, a.ctx.xw, dy[0], (double *)nullptr, rank, dy[1], a.ctx.xw2);
-}
-void launch_dx2(hipStream_t st, const DevArrays &a, const double *D, double *const *dy, const double *const *xi_d, double *const *dx) {
-    if (a.n > 0) hipLaunchKernelGGL(k_dx, dim3(nblk(a.n, 256), 2), dim3(256), 0, st, a.n, a.Ap, a.Ai, a.Ax, D, dy[0], xi_d[0], a.col_local, dx[0], 0, dy[1], xi_d[1], dx[1]);
+void launch_rhs(hipStream_t st, const DevArrays &a, const double *D, const double *const *xi_p, const double *const *xi_d, int rank, int nrhs) {
+    if (a.m <= 0) return;
+    const int l = nrhs - 1;                                          // (the second set of arguments is read by grid y = 1 alone)
+    if (a.n > 0) hipLaunchKernelGGL(k_rhs_scale, dim3(nblk(a.n, 256), (unsigned)nrhs), dim3(256), 0, st, a.n, D, xi_d[0], a.col_local, a.rhs_w, xi_d[l]);
+    hipLaunchKernelGGL(k_rhs, dim3(nblk(a.m * 8, 256), (unsigned)nrhs), dim3(256), 0, st, a.m, a.perm, a.Pp, a.Pj, a.Px, a.rhs_w, xi_p[0], xi_d[0],
+                       a.row_local, a.col_local, rank, a.ctx.xw, xi_p[l], l ? a.n : (i64)0, l ? a.ctx.xw2 : (i64)0);
 }
 // reduce-scatter step of the multi-device reductions: this shard's slice, summed over ALL ranks in rank order (its own contribution at position
 // own_rank, the peers' slices from the staging area: rank s at slot s, or s - 1 behind own_rank) -- every slice gets the same order whoever owns it
@@ -4480,8 +4467,10 @@ void launch_sum_ranked(hipStream_t st, i64 len, double *inout, const double *sta
 void launch_sum_to(hipStream_t st, i64 len, double *out, const double *own, const double *src, int nsrc, i64 stride) {
     if (len > 0) hipLaunchKernelGGL(k_sum_to, dim3(nblk(len, 256)), dim3(256), 0, st, len, out, own, src, nsrc, stride);
 }
-void launch_unpermute(hipStream_t st, const DevArrays &a, double *dy, double *dy_shared, int rank, int rhs) {
-    if (a.m > 0) hipLaunchKernelGGL(k_unpermute, dim3(nblk(a.m, 256)), dim3(256), 0, st, a.m, a.perm, a.row_local, a.ctx.xw + (rhs ? a.ctx.xw2 : 0), dy, dy_shared, rank, dy, (i64)0);
+// dy_shared (multi-device shards publishing into the lead's vector): one right-hand side only
+void launch_unpermute(hipStream_t st, const DevArrays &a, double *const *dy, double *dy_shared, int rank, int nrhs) {
+    if (a.m > 0) hipLaunchKernelGGL(k_unpermute, dim3(nblk(a.m, 256), (unsigned)nrhs), dim3(256), 0, st, a.m, a.perm, a.row_local, a.ctx.xw, dy[0],
+                                    dy_shared, rank, dy[nrhs - 1], nrhs == 2 ? a.ctx.xw2 : (i64)0);
 }
 void launch_residuals(hipStream_t st, const DevArrays &a, const double *xi_p, const double *xi_d, const double *theta, const double *regP,
                       const double *regD, const double *dx, const double *dy, double *r1, double *r2, int rank, int xip_all) {
@@ -4510,8 +4499,10 @@ void launch_refine_commit(hipStream_t st, i64 n, double *x, const double *cx, i6
     const i64 len = std::max(n, m);
     if (len > 0) hipLaunchKernelGGL(k_refine_commit, dim3(nblk(len, 256)), dim3(256), 0, st, n, x, cx, m, y, cy, ref);
 }
-void launch_dx(hipStream_t st, const DevArrays &a, const double *D, const double *dy, const double *xi_d, double *dx, int local_only) {
-    if (a.n > 0) hipLaunchKernelGGL(k_dx, dim3(nblk(a.n, 256)), dim3(256), 0, st, a.n, a.Ap, a.Ai, a.Ax, D, dy, xi_d, a.col_local, dx, local_only, dy, xi_d, dx);
+void launch_dx(hipStream_t st, const DevArrays &a, const double *D, double *const *dy, const double *const *xi_d, double *const *dx, int local_only, int nrhs) {
+    const int l = nrhs - 1;
+    if (a.n > 0) hipLaunchKernelGGL(k_dx, dim3(nblk(a.n, 256), (unsigned)nrhs), dim3(256), 0, st, a.n, a.Ap, a.Ai, a.Ax, D, dy[0], xi_d[0], a.col_local, dx[0], local_only,
+                                    dy[l], xi_d[l], dx[l]);
 }
 
 }  // namespace tlpk

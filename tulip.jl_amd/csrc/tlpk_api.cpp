@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -853,20 +854,25 @@ void tlpk_destroy(tlpk_handle *h) {
 }
 
 // ---- update ----
-// Dense-matrix handles (tlpk_create_dense) have one front, one rank and nothing to reduce: the split-phase calls do not apply to them.  The composed
-// entry points run the same halves internally (Composed marks that).
-static int dense_no_split(tlpk_handle *h, const char *what) {
-    if (h && h->S.dense_matrix && !h->composed) {
+// The refusals the split-phase and device-pointer entry points share, tested in THIS order (it decides which code a doubly wrong call gets); `checks` names
+// the ones that apply to the caller, `args_ok` = none of its pointer arguments is null.
+//   R_DENSE    dense-matrix handles (tlpk_create_dense) have one front, one rank and nothing to reduce: the split-phase calls do not apply to them (the
+//              public split-phase entry points alone pass it: the composed ones run the same halves through the internal functions)
+//   R_MULTI    a tlpk_create_multi parent: its shards are driven by the library
+//   R_DEVICE   an analysis-only handle;   R_FACTORED   a solve before a successful update
+enum : unsigned { R_DENSE = 1, R_MULTI = 2, R_DEVICE = 4, R_FACTORED = 8 };
+static int refuse(tlpk_handle *h, bool args_ok, unsigned checks, const char *what = "") {
+    if ((checks & R_DENSE) && h && h->S.dense_matrix) {
         h->last_error = std::string(what) + ": the split-phase calls do not apply to a dense-matrix handle (tlpk_create_dense)";
         return TLPK_BADARG;
     }
+    if (!h || !args_ok) return TLPK_BADARG;
+    if ((checks & R_MULTI) && !h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
+    if ((checks & R_DEVICE) && !h->has_device) return TLPK_NO_DEVICE;
+    if ((checks & R_FACTORED) && !h->factored) return TLPK_NOT_FACTORED;
     return TLPK_OK;
 }
-struct Composed {
-    tlpk_handle *h; bool old = false;
-    explicit Composed(tlpk_handle *h_) : h(h_) { if (h) { old = h->composed; h->composed = true; } }
-    ~Composed() { if (h) h->composed = old; }
-};
+static bool hostio_timing() { static const bool on = [] { const char *e = std::getenv("TLPK_HOSTIO_TIMING"); return e && std::atoi(e) != 0; }(); return on; }
 static int update_async_wait(tlpk_handle *h);
 // everything of an update up to the reduction of the root panel, on the handle-owned copies of theta / regP / regD
 static int enq_update_local(tlpk_handle *h) {
@@ -934,16 +940,12 @@ static int enq_update_finish(tlpk_handle *h, hipStream_t root_stream = nullptr) 
     return TLPK_OK;
 }
 
-int tlpk_update_local(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
-    if (int g = dense_no_split(h, "tlpk_update_local")) return g;
-    if (!h || !d_theta || !d_regP || !d_regD) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
+// checks and prologue of every device-pointer update: the state of a handle that is being refactorised, ev0, the stored copies of the caller's vectors
+static int update_begin(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
+    if (int g = refuse(h, d_theta && d_regP && d_regD, R_MULTI | R_DEVICE)) return g;
     HIPCHK(h, hipSetDevice(h->device));
-    const Symbolic &S = h->S;
-    (void)S;
     if (h->root_pending) { (void)update_async_wait(h); }      // an unchecked tlpk_update_device_async: complete it (its status is the caller's loss)
-    h->factored = false; h->local_done = false; h->solve_local_done = false; h->fail_col = -1; h->solve_timed = false;
+    h->factored = false; h->local_done = false; h->pending = tlpk_handle::Pending::None; h->fail_col = -1; h->solve_timed = false;
     prof_begin(h, true);
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     // stored copies (spd.jl:36-38): the caller may mutate its vectors right after the call
@@ -952,30 +954,43 @@ int tlpk_update_local(tlpk_handle *h, const double *d_theta, const double *d_reg
     if (d_regP != h->d_regP) HIPCHK(h, hipMemcpyAsync(h->d_regP, d_regP, (size_t)un * 8, hipMemcpyDeviceToDevice, h->stream));
     if (d_regD != h->d_regD) HIPCHK(h, hipMemcpyAsync(h->d_regD, d_regD, (size_t)um * 8, hipMemcpyDeviceToDevice, h->stream));
     h->h_info[0] = INT_MAX;
-    if (h->update_whole) return TLPK_OK;                 // tlpk_update_device on an unsharded handle: the caller enqueues both halves (graph)
+    return TLPK_OK;
+}
+// the first half of a split-phase update (the multi-device mode calls it on its shards)
+static int update_local(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
+    if (int rc = update_begin(h, d_theta, d_regP, d_regD)) return rc;
     if (int rc = enq_update_local(h)) return rc;
     h->local_done = true;
     return TLPK_OK;
 }
-
-int tlpk_root_panel(tlpk_handle *h, double **d_ptr, int64_t *count) {
-    if (int g = dense_no_split(h, "tlpk_root_panel")) return g;
-    if (!h || !d_ptr || !count) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
-    if (h->S.root_front < 0) { *d_ptr = nullptr; *count = 0; return TLPK_OK; }
-    const FrontDesc &fd = h->S.fronts[h->S.root_front];
-    *d_ptr = h->d.ctx.Lval + fd.loff;
-    *count = pk_len(fd.lda, fd.ns);          // whole (packed) panel incl. the alignment rows (they stay zero)
-    return TLPK_OK;
+int tlpk_update_local(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
+    if (int g = refuse(h, true, R_DENSE, "tlpk_update_local")) return g;
+    return update_local(h, d_theta, d_regP, d_regD);
 }
 
+// The buffers the caller (or the multi-device mode) reduces across ranks.  which: 0 root panel, 1 root right-hand side, 2 root right-hand side of the second
+// system of a pair
+static int root_buf(tlpk_handle *h, int which, double **d_ptr, int64_t *count, const char *what = "", unsigned dense = 0) {
+    if (int g = refuse(h, d_ptr && count, dense | R_MULTI | R_DEVICE, what)) return g;
+    if (which == 0) {
+        if (h->S.root_front < 0) { *d_ptr = nullptr; *count = 0; return TLPK_OK; }
+        const FrontDesc &fd = h->S.fronts[h->S.root_front];
+        *d_ptr = h->d.ctx.Lval + fd.loff;
+        *count = pk_len(fd.lda, fd.ns);          // whole (packed) panel incl. the alignment rows (they stay zero)
+        return TLPK_OK;
+    }
+    *d_ptr = h->nlink ? h->d.ctx.xw + (which == 2 ? h->d.ctx.xw2 : 0) + h->first_link : nullptr;
+    *count = h->nlink;
+    return TLPK_OK;
+}
+int tlpk_root_panel(tlpk_handle *h, double **d_ptr, int64_t *count) { return root_buf(h, 0, d_ptr, count, "tlpk_root_panel", R_DENSE); }
+int tlpk_root_rhs(tlpk_handle *h, double **d_ptr, int64_t *count) { return root_buf(h, 1, d_ptr, count, "tlpk_root_rhs", R_DENSE); }
+int tlpk_root_rhs2(tlpk_handle *h, double **d_ptr, int64_t *count) { return root_buf(h, 2, d_ptr, count, "tlpk_root_rhs2", R_DENSE); }
+
 int tlpk_root_copy(tlpk_handle *h, int which, int dir, double *d_buf) {
-    if (int g = dense_no_split(h, "tlpk_root_copy")) return g;
-    if (!h || !d_buf || which < 0 || which > 2 || (dir != 0 && dir != 1)) return TLPK_BADARG;
-    if (!h->has_device) return TLPK_NO_DEVICE;
+    if (int g = refuse(h, d_buf && which >= 0 && which <= 2 && (dir == 0 || dir == 1), R_DENSE | R_DEVICE, "tlpk_root_copy")) return g;
     double *p = nullptr; int64_t n = 0;
-    int rc = which == 0 ? tlpk_root_panel(h, &p, &n) : (which == 1 ? tlpk_root_rhs(h, &p, &n) : tlpk_root_rhs2(h, &p, &n));
+    const int rc = root_buf(h, which, &p, &n);
     if (rc != TLPK_OK || n == 0) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(dir == 0 ? d_buf : p, dir == 0 ? p : d_buf, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -993,13 +1008,8 @@ static int update_finish_enqueue(tlpk_handle *h) {
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     return TLPK_OK;
 }
-static int update_finish_wait(tlpk_handle *h) {
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipGetLastError());
-    float ms = 0.f; hipEventElapsedTime(&ms, h->ev0, h->ev1); h->ms_update = ms;
-    prof_collect(h);
-    h->local_done = false;
+// the verdict of an update from the status words read back: h_info[0] = first non-positive pivot (INT_MAX: none), h_info[1] = a dependency-driven launch gave up waiting
+static int update_verdict(tlpk_handle *h) {
     if (h->d.n_chain_cnt > 0 && h->h_info[1] != 0) {
         if (std::getenv("TLPK_CHAIN_DEBUG")) {
             int dbg[16] = {0}; (void)hipMemcpy(dbg, h->d.ctx.info, sizeof(dbg), hipMemcpyDeviceToHost);
@@ -1016,16 +1026,26 @@ static int update_finish_wait(tlpk_handle *h) {
                 if (FILE *f = std::fopen(path.c_str(), "wb")) { std::fwrite(tr.data(), 8, tr.size(), f); std::fclose(f); std::fprintf(stderr, "[tlpk chain] time stamps of %zu items -> %s\n", h->S.chain_items.size(), path.c_str()); }
             }
         }
-        h->last_error = "the dependency-driven factorisation gave up waiting for a completion counter (internal scheduling error); the factor is invalid"; return TLPK_INTERNAL; }
+        h->last_error = "the dependency-driven factorisation gave up waiting for a completion counter (internal scheduling error); the factor is invalid";
+        return TLPK_INTERNAL;
+    }
     if (h->h_info[0] != INT_MAX) { h->fail_col = h->h_info[0]; return TLPK_NOT_POSDEF; }
-    h->factored = true;
     return TLPK_OK;
+}
+static int update_finish_wait(tlpk_handle *h) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    float ms = 0.f; hipEventElapsedTime(&ms, h->ev0, h->ev1); h->ms_update = ms;
+    prof_collect(h);
+    h->local_done = false;
+    const int rc = update_verdict(h);
+    if (rc == TLPK_OK) h->factored = true;               // (a failed update leaves `factored` as the update's first half set it: false)
+    return rc;
 }
 
 int tlpk_update_finish(tlpk_handle *h) {
-    if (int g = dense_no_split(h, "tlpk_update_finish")) return g;
-    if (!h) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
+    if (int g = refuse(h, true, R_DENSE | R_MULTI, "tlpk_update_finish")) return g;
     if (int rc = update_finish_enqueue(h)) return rc;
     return update_finish_wait(h);
 }
@@ -1056,19 +1076,16 @@ static int update_async_wait(tlpk_handle *h) {
     HIPCHK(h, hipGetLastError());
     float ms = 0.f; if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->ms_update = ms;
     h->root_pending = false; h->local_done = false;
-    if (h->d.n_chain_cnt > 0 && h->h_info[1] != 0) { h->factored = false; h->last_error = "the dependency-driven factorisation gave up waiting for a completion counter (internal scheduling error); the factor is invalid"; return TLPK_INTERNAL; }
-    if (h->h_info[0] != INT_MAX) { h->fail_col = h->h_info[0]; h->factored = false; return TLPK_NOT_POSDEF; }
-    h->factored = true;
-    return TLPK_OK;
+    const int rc = update_verdict(h);
+    h->factored = (rc == TLPK_OK);                       // (set tentatively when the update was enqueued)
+    return rc;
 }
 
 int tlpk_update_device_async(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
     if (int g = sharded_needs_split(h, "tlpk_update_device_async")) return g;
     if (!h || !h->sub.empty() || !h->has_device || h->profile || h->serial || graph_usable(h) || !h->rstream)
         return tlpk_update_device(h, d_theta, d_regP, d_regD);          // nothing to overlap / a mode that serialises anyway: the blocking call
-    h->update_whole = true;
-    int rc = tlpk_update_local(h, d_theta, d_regP, d_regD);             // argument checks, stored copies, ev0
-    h->update_whole = false;
+    int rc = update_begin(h, d_theta, d_regP, d_regD);
     if (rc != TLPK_OK) return rc;
     if ((rc = enq_update_local(h)) != TLPK_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev_blocks, h->stream));
@@ -1083,18 +1100,16 @@ int tlpk_update_device_async(tlpk_handle *h, const double *d_theta, const double
 }
 
 int tlpk_update_device(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
-    Composed composed(h);
     if (int g = sharded_needs_split(h, "tlpk_update_device")) return g;
-    if (!h || !h->sub.empty() || !h->has_device || !graph_usable(h)) {
-        int rc = tlpk_update_local(h, d_theta, d_regP, d_regD);
-        if (rc != TLPK_OK) return rc;
-        return tlpk_update_finish(h);
-    }
-    // unsharded handle: prologue (stored copies of the caller's vectors), then the WHOLE factorisation as one replayed graph
-    h->update_whole = true;
-    int rc = tlpk_update_local(h, d_theta, d_regP, d_regD);
-    h->update_whole = false;
+    int rc = update_begin(h, d_theta, d_regP, d_regD);
     if (rc != TLPK_OK) return rc;
+    if (!graph_usable(h)) {                              // the two halves back to back
+        if ((rc = enq_update_local(h)) != TLPK_OK) return rc;
+        h->local_done = true;
+        if ((rc = update_finish_enqueue(h)) != TLPK_OK) return rc;
+        return update_finish_wait(h);
+    }
+    // the WHOLE factorisation as one replayed graph
     const GraphKey key{1, {}};
     rc = graph_or_direct(h, key, [&]() { const int q = enq_update_local(h); return q != TLPK_OK ? q : enq_update_finish(h); }, graph_usable(h));
     if (rc != TLPK_OK) return rc;
@@ -1212,7 +1227,7 @@ static int update_once(tlpk_handle *h, const double *theta, const double *regP, 
     HIPCHK(h, hipStreamSynchronize(h->stream));          // the staging area may still feed an earlier call's copies
     const i64 un = user_n(h), um = user_m(h);
     const HostVec in[3] = {{h->d_theta, const_cast<double *>(theta), un}, {h->d_regP, const_cast<double *>(regP), un}, {h->d_regD, const_cast<double *>(regD), um}};
-    static const bool timing = [] { const char *e = std::getenv("TLPK_HOSTIO_TIMING"); return e && std::atoi(e) != 0; }();
+    const bool timing = hostio_timing();
     const double t0 = timing ? now_ms() : 0.0;
     if (int rc = stage_in(h, in, 3)) return rc;
     const double t1 = timing ? now_ms() : 0.0;
@@ -1242,134 +1257,165 @@ int tlpk_update(tlpk_handle *h, const double *theta, const double *regP, const d
 }
 
 // ---- solve ----
-// rhs_rank >= 0 overrides the rank the right-hand side kernel sees: rank 0 adds xi_p on the linking rows, and a refinement step on a
-// sharded handle passes every rank's PARTIAL residual of those rows (the all-reduce of the root right-hand side completes the sum)
-static int enq_solve_local(tlpk_handle *h, const double *d_xip, const double *d_xid, int rhs_rank = -1) {
+// The arguments of one solve (nrhs = 1; slot 1 then repeats slot 0) or of one pair of solves (nrhs = 2: two right-hand sides in ONE pass over L -- the
+// persistent sweeps are bound by the bytes of L, the pair costs little more than one solve).  Tulip's HSD step has such a pair in every iteration: the
+// h-system and the predictor (/root/reference/src/IPM/HSD/step.jl:63 and :79 -- neither right-hand side depends on the other solve).  A pair is
+// bit-identical to two solves.
+struct SolveIo {
+    int nrhs;
+    const double *xip[2], *xid[2];
+    double *dx[2], *dy[2];
+    // rank the right-hand-side kernel sees; -1: the handle's own.  Rank 0 adds xi_p on the linking rows: the device-resident loops on a multi-device handle
+    // and a refinement step on a sharded one pass every rank's PARTIAL residual of those rows (the all-reduce of the root right-hand side completes the sum)
+    int rhs_rank = -1;
+    // shards of a multi-device handle publishing straight into the lead device's job-wide vectors (P2P stores; nrhs = 1 only): dy gets the rows this rank
+    // owns as well, dx IS the job-wide vector and the other ranks' columns are left alone
+    double *shared_dy = nullptr; bool dx_local_only = false;
+};
+static SolveIo solve_io(double *dx, double *dy, const double *xip, const double *xid) { return SolveIo{1, {xip, xip}, {xid, xid}, {dx, dx}, {dy, dy}}; }
+using Pending = tlpk_handle::Pending;
+
+// the two halves of a solve, split at the reduction of the root right-hand side(s) (tlpk_root_rhs; of a pair also tlpk_root_rhs2)
+static int enq_solve_local(tlpk_handle *h, const SolveIo &io) {
+    const Symbolic &S = h->S;
+    const int nr = io.nrhs, rank = io.rhs_rank >= 0 ? io.rhs_rank : h->opt.rank;
     {
         ProfScope ps(h, TLPK_KC_SPMV);
         // tickets + hand-over words of both sweeps back to all ones: the data is its own flag, ticket + 1 = 0 is the first item
-        if (h->S.sweep && h->S.n_sweep_flags > 0) HIPCHK(h, hipMemsetAsync(h->d.sweep_tickets, 0xFF, (size_t)h->d.sweep_reset_bytes, h->stream));
+        // (a pair implies S.sweep: every entry point of a pair refuses, or falls back to two solves, without the persistent-sweep schedule)
+        if (S.sweep && S.n_sweep_flags > 0) HIPCHK(h, hipMemsetAsync(h->d.sweep_tickets, 0xFF, (size_t)(nr == 2 ? h->d.sweep_reset_bytes2 : h->d.sweep_reset_bytes), h->stream));
         // (the give-up flag of an EARLIER solve must not fail this one; while the root front of an asynchronous update is still being factorised on its own stream the
         //  flag may be that update's: it stays)
-        if (h->S.sweep && !h->root_pending) HIPCHK(h, hipMemsetAsync(h->d.ctx.info + 1, 0, sizeof(int), h->stream));
-        if (h->S.dense_matrix) { const double *q[1] = {d_xid}, *p[1] = {d_xip}; double *o[1] = {h->d.ctx.xw}; launch_dense_gemv_n(h->stream, h->d, h->d_D, q, p, o, 1); }   // xi_p + A (D .* xi_d); identity order
-        else if (h->S.system == 1) launch_k2_rhs(h->stream, h->d, h->S.k2_n, d_xip, d_xid, 0, rhs_rank >= 0 ? rhs_rank : h->opt.rank);        // [xi_d ; xi_p] permuted (sqd.jl:62-66)
-        else if (h->S.n_dense > 0) { const double *p[2] = {d_xip, d_xip}, *q[2] = {d_xid, d_xid}; launch_dense_rhs(h->stream, h->d, h->d_D, p, q, 1); }
-        else launch_rhs(h->stream, h->d, h->d_D, d_xip, d_xid, rhs_rank >= 0 ? rhs_rank : h->opt.rank);
-        launch_single_solve(h->stream, h->d);
+        // nrhs == 1 only: a pair has never cleared the flag (an earlier solve's give-up fails the tlpk_sync after a pair) -- kept as it was, see the follow-ups
+        if (nr == 1 && S.sweep && !h->root_pending) HIPCHK(h, hipMemsetAsync(h->d.ctx.info + 1, 0, sizeof(int), h->stream));
+        if (S.dense_matrix) { double *o[2] = {h->d.ctx.xw, h->d.ctx.xw + h->d.ctx.xw2}; launch_dense_gemv_n(h->stream, h->d, h->d_D, io.xid, io.xip, o, nr); }   // xi_p + A (D .* xi_d); identity order
+        else if (S.system == 1) launch_k2_rhs(h->stream, h->d, S.k2_n, io.xip, io.xid, rank, nr);        // [xi_d ; xi_p] permuted (sqd.jl:62-66)
+        else if (S.n_dense > 0) launch_dense_rhs(h->stream, h->d, h->d_D, io.xip, io.xid, nr);
+        else launch_rhs(h->stream, h->d, h->d_D, io.xip, io.xid, rank, nr);
+        launch_single_solve(h->stream, h->d, nr);
     }
-    run_launches(h, h->S.fwd_launches, 0, h->fwd_marker, 0);
+    run_launches(h, S.fwd_launches, 0, h->fwd_marker, 0, nr);
     HIPCHK(h, hipGetLastError());
     return TLPK_OK;
 }
-static int enq_solve_finish(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xid) {
+static int enq_solve_finish(tlpk_handle *h, const SolveIo &io) {
+    const Symbolic &S = h->S;
+    const int nr = io.nrhs;
     if (h->root_pending) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_root, 0));      // the root front is being factorised on its own stream
-    run_launches(h, h->S.fwd_launches, h->fwd_marker, h->S.fwd_launches.size(), 0);
-    if (h->S.system == 1 || h->S.n_dense > 0) { ProfScope ps(h, TLPK_KC_SPMV); launch_apply_signs(h->stream, h->d); }     // L S L' x = b: z = S y between the sweeps
-    run_launches(h, h->S.bwd_launches, 0, h->S.bwd_launches.size(), 1);
-    if (h->S.dense_matrix) {
-        // dy = the solution (identity order), dx = D .* (A' dy - xi_d)
-        ProfScope ps(h, TLPK_KC_SPMV);
-        HIPCHK(h, hipMemcpyAsync(d_dy, h->d.ctx.xw, (size_t)h->S.m * 8, hipMemcpyDeviceToDevice, h->stream));
-        const double *y[1] = {h->d.ctx.xw}, *q[1] = {d_xid}; double *o[1] = {d_dx};
-        launch_dense_gemv_t(h->stream, h->d, h->d_D, y, q, o, 1);
-    } else if (h->S.system == 1) {
-        // multi-device mode: every shard stores the nodes it owns straight into the lead device's job-wide dx / dy
-        ProfScope ps(h, TLPK_KC_SPMV);
-        launch_k2_out(h->stream, h->d, h->S.k2_n, d_dx, h->shared_dy ? h->shared_dy : d_dy, 0, h->opt.rank, h->dx_local_only ? 1 : 0);
-    } else if (h->S.n_dense > 0) {
-        ProfScope ps(h, TLPK_KC_SPMV);
-        double *y[2] = {d_dy, d_dy}, *x[2] = {d_dx, d_dx};
-        const double *q[2] = {d_xid, d_xid};
-        launch_dense_out(h->stream, h->d, h->d_D, y, q, x, 1);
-    } else {
-        { ProfScope ps(h, TLPK_KC_SPMV); launch_unpermute(h->stream, h->d, d_dy, h->shared_dy, h->opt.rank); }
-        { ProfScope ps(h, TLPK_KC_SPMV); launch_dx(h->stream, h->d, h->d_D, d_dy, d_xid, d_dx, h->dx_local_only ? 1 : 0); }
+    run_launches(h, S.fwd_launches, h->fwd_marker, S.fwd_launches.size(), 0, nr);
+    if (S.system == 1 || S.n_dense > 0) { ProfScope ps(h, TLPK_KC_SPMV); launch_apply_signs(h->stream, h->d, nr); }     // L S L' x = b: z = S y between the sweeps
+    run_launches(h, S.bwd_launches, 0, S.bwd_launches.size(), 1, nr);
+    {
+        std::optional<ProfScope> ps(std::in_place, h, TLPK_KC_SPMV);
+        if (S.dense_matrix) {
+            // dy = the solution (identity order), dx = D .* (A' dy - xi_d)
+            const double *y[2] = {h->d.ctx.xw, h->d.ctx.xw + h->d.ctx.xw2};
+            for (int r = 0; r < nr; ++r) HIPCHK(h, hipMemcpyAsync(io.dy[r], y[r], (size_t)S.m * 8, hipMemcpyDeviceToDevice, h->stream));
+            launch_dense_gemv_t(h->stream, h->d, h->d_D, y, io.xid, io.dx, nr);
+        } else if (S.system == 1) {
+            // multi-device mode: every shard stores the nodes it owns straight into the lead device's job-wide dx / dy
+            double *y[2] = {io.shared_dy ? io.shared_dy : io.dy[0], io.dy[1]};
+            launch_k2_out(h->stream, h->d, S.k2_n, io.dx, y, h->opt.rank, io.dx_local_only ? 1 : 0, nr);
+        } else if (S.n_dense > 0) {
+            launch_dense_out(h->stream, h->d, h->d_D, io.dy, io.xid, io.dx, nr);
+        } else {
+            launch_unpermute(h->stream, h->d, io.dy, io.shared_dy, h->opt.rank, nr);
+            if (nr == 1) ps.emplace(h, TLPK_KC_SPMV);      // profile mode has always timed the two kernels of ONE solve as two launches of the class, a pair's as one: kept
+            launch_dx(h->stream, h->d, h->d_D, io.dy, io.xid, io.dx, io.dx_local_only ? 1 : 0, nr);
+        }
     }
-    if (h->S.sweep) HIPCHK(h, hipMemcpyAsync(h->h_info + 1, h->d.ctx.info + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (S.sweep) HIPCHK(h, hipMemcpyAsync(h->h_info + 1, h->d.ctx.info + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     return TLPK_OK;
 }
 
-int tlpk_solve_local(tlpk_handle *h, const double *d_xip, const double *d_xid) {
-    if (int g = dense_no_split(h, "tlpk_solve_local")) return g;
-    if (!h || !d_xip || !d_xid) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
-    if (!h->factored) return TLPK_NOT_FACTORED;
+// prologue and epilogue of every solve: ev0 / ev1 bracket it for tlpk_sync's timer
+static int solve_begin(tlpk_handle *h) {
     HIPCHK(h, hipSetDevice(h->device));
     prof_begin(h, false);
     h->solve_timed = false;
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     h->solve_epoch += 1;
-    if (h->solve_whole) return TLPK_OK;                  // tlpk_solve_device: the caller enqueues both halves (graph)
-    if (int rc = enq_solve_local(h, d_xip, d_xid, h->rhs_all_ranks ? 0 : -1)) return rc;
-    h->solve_local_done = true;
     return TLPK_OK;
 }
-
-int tlpk_root_rhs(tlpk_handle *h, double **d_ptr, int64_t *count) {
-    if (int g = dense_no_split(h, "tlpk_root_rhs")) return g;
-    if (!h || !d_ptr || !count) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
-    *d_ptr = h->nlink ? h->d.ctx.xw + h->first_link : nullptr;
-    *count = h->nlink;
+static int solve_end(tlpk_handle *h) {
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipGetLastError());
+    h->solve_timed = true;
     return TLPK_OK;
 }
+static const char *solve_name(const SolveIo &io) { return io.nrhs == 2 ? "tlpk_solve2" : "tlpk_solve"; }
 
-int tlpk_solve_finish(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xid) {
-    if (int g = dense_no_split(h, "tlpk_solve_finish")) return g;
-    if (!h || !d_dx || !d_dy || !d_xid) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
-    if (!h->factored) return TLPK_NOT_FACTORED;
-    if (!h->solve_local_done || h->refine_pending || h->pair_pending) { h->last_error = "tlpk_solve_finish without a preceding tlpk_solve_local"; return TLPK_BADARG; }
-    h->solve_local_done = false;
+// The first half (everything up to the reduction of the root right-hand sides) and the second, as the split-phase entry points and the multi-device mode
+// (on its shards) run them
+static int solve_local(tlpk_handle *h, const SolveIo &io) {
+    const int l = io.nrhs - 1;
+    if (int g = refuse(h, io.xip[0] && io.xid[0] && io.xip[l] && io.xid[l], R_MULTI | R_DEVICE | R_FACTORED)) return g;
+    if (io.nrhs == 2) {
+        if (!h->S.sweep) { h->last_error = "tlpk_solve2_local needs the persistent-sweep schedule (TLPK_SWEEP=0 is set)"; return TLPK_BADARG; }
+        if (h->pending != Pending::None) { h->last_error = "tlpk_solve2_local inside an unfinished solve"; return TLPK_BADARG; }
+    }
+    if (int rc = solve_begin(h)) return rc;
+    if (int rc = enq_solve_local(h, io)) return rc;
+    // nrhs == 1: tlpk_solve_local has never refused an unfinished pair or refinement -- it starts over, and what is pending stays the kind it was (follow-ups)
+    if (io.nrhs == 2) h->pending = Pending::Pair;
+    else if (h->pending == Pending::None) h->pending = Pending::Solve;
+    return TLPK_OK;
+}
+static int solve_finish(tlpk_handle *h, const SolveIo &io) {
+    const int l = io.nrhs - 1;
+    // nrhs == 1 only: tlpk_solve2_finish has never asked for a factor (its first half did) -- kept, it decides between two refusals of a doubly wrong call
+    if (int g = refuse(h, io.dx[0] && io.dy[0] && io.xid[0] && io.dx[l] && io.dy[l] && io.xid[l], R_MULTI | R_DEVICE | (io.nrhs == 1 ? R_FACTORED : 0u))) return g;
+    if (h->pending != (io.nrhs == 2 ? Pending::Pair : Pending::Solve)) {
+        h->last_error = std::string(solve_name(io)) + "_finish without a preceding " + solve_name(io) + "_local";
+        return TLPK_BADARG;
+    }
+    h->pending = Pending::None;
     HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = enq_solve_finish(h, d_dx, d_dy, d_xid)) return rc;
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipGetLastError());
-    h->solve_timed = true;
-    return TLPK_OK;
+    if (int rc = enq_solve_finish(h, io)) return rc;
+    return solve_end(h);
+}
+// one whole solve or pair (both halves) through the graph cache, keyed by its pointers (kind 2: a solve, 3: a pair)
+static int solve_whole(tlpk_handle *h, const SolveIo &io) {
+    if (int rc = solve_begin(h)) return rc;
+    GraphKey key{io.nrhs == 2 ? 3 : 2, {io.dx[0], io.dy[0], io.xip[0], io.xid[0]}};
+    if (io.nrhs == 2) { key.p[4] = io.dx[1]; key.p[5] = io.dy[1]; key.p[6] = io.xip[1]; key.p[7] = io.xid[1]; }
+    const int rc = graph_or_direct(h, key, [&]() { const int q = enq_solve_local(h, io); return q != TLPK_OK ? q : enq_solve_finish(h, io); }, graph_usable_solve(h));
+    return rc != TLPK_OK ? rc : solve_end(h);
+}
+// one solve of tlpk_solve_device: through the graph cache where the handle can replay graphs, otherwise the two halves back to back
+static int solve_composed(tlpk_handle *h, const SolveIo &io, bool whole) {
+    if (!whole) { const int rc = solve_local(h, io); return rc != TLPK_OK ? rc : solve_finish(h, io); }
+    if (!io.dx[0] || !io.dy[0]) return TLPK_BADARG;
+    if (int g = refuse(h, io.xip[0] && io.xid[0], R_MULTI | R_DEVICE | R_FACTORED)) return g;
+    return solve_whole(h, io);
 }
 
-// one whole solve (both halves) from the graph cache, keyed by its four pointers
-static int solve_whole(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
-    if (!d_dx || !d_dy) return TLPK_BADARG;
-    h->solve_whole = true;
-    int rc = tlpk_solve_local(h, d_xip, d_xid);          // argument / state checks, ev0
-    h->solve_whole = false;
-    if (rc != TLPK_OK) return rc;
-    const GraphKey key{2, {d_dx, d_dy, d_xip, d_xid}};
-    rc = graph_or_direct(h, key, [&]() { const int q = enq_solve_local(h, d_xip, d_xid); return q != TLPK_OK ? q : enq_solve_finish(h, d_dx, d_dy, d_xid); }, graph_usable_solve(h));
-    if (rc != TLPK_OK) return rc;
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipGetLastError());
-    h->solve_timed = true;
-    return TLPK_OK;
+int tlpk_solve_local(tlpk_handle *h, const double *d_xip, const double *d_xid) {
+    if (int g = refuse(h, true, R_DENSE, "tlpk_solve_local")) return g;
+    return solve_local(h, solve_io(nullptr, nullptr, d_xip, d_xid));
+}
+int tlpk_solve_finish(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xid) {
+    if (int g = refuse(h, true, R_DENSE, "tlpk_solve_finish")) return g;
+    return solve_finish(h, solve_io(d_dx, d_dy, nullptr, d_xid));
 }
 
 int tlpk_solve_device(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
-    Composed composed(h);
     if (int g = sharded_needs_split(h, "tlpk_solve_device")) return g;
     const bool whole = h && h->sub.empty() && h->has_device && graph_usable_solve(h);
-    int rc = whole ? solve_whole(h, d_dx, d_dy, d_xip, d_xid) : tlpk_solve_local(h, d_xip, d_xid);
+    int rc = solve_composed(h, solve_io(d_dx, d_dy, d_xip, d_xid), whole);
     if (rc != TLPK_OK) return rc;
-    if (!whole) rc = tlpk_solve_finish(h, d_dx, d_dy, d_xid);
     // optional iterative refinement on the residuals of the augmented system (KKT.jl:70-75): each step is one more solve with
     // (r1, r2) as right-hand side.  Off by default = the reference (spd.jl:68).  GUARDED (round 5): the candidate x + c is kept only if
     // |r1|inf shrinks and |r2|inf stays within 16 x of the unrefined solve's (kernels.hip: k_refine_decide) -- decided on the device, no host synchronisation; a rejected step ends the refinement of this solve
     // (tlpk_stats.refine_rejected).  On the north-star LP's late iterations an unguarded second step grew the dual residual from 2e-8 to 0.6
     // (profiles/r04_mpc_levers.txt): an option that exists must not make a solve worse.
-    if (h->refine_steps > 0 && rc == TLPK_OK) {
+    if (h->refine_steps > 0) {
         HIPCHK(h, hipMemsetAsync(h->d_ref, 0, 8 * sizeof(unsigned long long), h->stream));
         launch_residuals(h->stream, h->d, d_xip, d_xid, h->d_theta, h->d_regP, h->d_regD, d_dx, d_dy, h->d_r1, h->d_r2, 0);
         launch_absmax2(h->stream, h->d, h->d_r1, h->d_r2, h->d_ref + 0);      // |r1| current, |r2| of the unrefined solve
     }
-    for (int it = 0; it < h->refine_steps && rc == TLPK_OK; ++it) {
-        rc = whole ? solve_whole(h, h->d_cx, h->d_cy, h->d_r1, h->d_r2) : tlpk_solve_local(h, h->d_r1, h->d_r2);
-        if (rc == TLPK_OK && !whole) rc = tlpk_solve_finish(h, h->d_cx, h->d_cy, h->d_r2);
-        if (rc != TLPK_OK) break;
+    for (int it = 0; it < h->refine_steps; ++it) {
+        if ((rc = solve_composed(h, solve_io(h->d_cx, h->d_cy, h->d_r1, h->d_r2), whole)) != TLPK_OK) return rc;
         launch_candidate(h->stream, h->S.n, d_dx, h->d_cx, user_m(h), d_dy, h->d_cy);
         // residuals of the candidate: the next step's right-hand side if the candidate is kept (after a rejection nothing is kept any more)
         launch_residuals(h->stream, h->d, d_xip, d_xid, h->d_theta, h->d_regP, h->d_regD, h->d_cx, h->d_cy, h->d_r1, h->d_r2, 0);
@@ -1378,9 +1424,9 @@ int tlpk_solve_device(tlpk_handle *h, double *d_dx, double *d_dy, const double *
         launch_refine_commit(h->stream, h->S.n, d_dx, h->d_cx, user_m(h), d_dy, h->d_cy, h->d_ref);
         HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     }
-    if (h->refine_steps > 0 && rc == TLPK_OK)
+    if (h->refine_steps > 0)
         HIPCHK(h, hipMemcpyAsync(h->h_info + 2, reinterpret_cast<int *>(h->d_ref + 4), sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return rc;
+    return TLPK_OK;
 }
 
 // Iterative refinement in two halves, for sharded handles (and any single-rank K1 handle): one step is one more solve, so it holds
@@ -1400,172 +1446,62 @@ static int refine_buffers(tlpk_handle *h) {
     if (!h->d_cy && (rc = dev_alloc(h, &h->d_cy, mm)) != TLPK_OK) return rc;
     return TLPK_OK;
 }
-int tlpk_refine_local(tlpk_handle *h, const double *d_dx, const double *d_dy, const double *d_xip, const double *d_xid) {
-    if (int g = dense_no_split(h, "tlpk_refine_local")) return g;
-    if (!h || !d_dx || !d_dy || !d_xip || !d_xid) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
+// xip_all: the device-resident loops' convention on a multi-device handle -- this shard's xi_p is its PARTIAL of the linking rows and counts whatever the rank
+static int refine_local(tlpk_handle *h, const double *d_dx, const double *d_dy, const double *d_xip, const double *d_xid, bool xip_all) {
+    if (int g = refuse(h, d_dx && d_dy && d_xip && d_xid, R_MULTI)) return g;
     if (h->S.system == 1) { h->last_error = "iterative refinement: K1 only"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
-    if (!h->factored) return TLPK_NOT_FACTORED;
-    if (h->solve_local_done) { h->last_error = "tlpk_refine_local inside an unfinished solve"; return TLPK_BADARG; }
+    if (int g = refuse(h, true, R_DEVICE | R_FACTORED)) return g;
+    if (h->pending != Pending::None) { h->last_error = "tlpk_refine_local inside an unfinished solve"; return TLPK_BADARG; }
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = refine_buffers(h)) return rc;
-    prof_begin(h, false);
-    h->solve_timed = false;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    h->solve_epoch += 1;
-    // (rhs_all_ranks: the device-resident loops' convention -- this shard's xi_p is its PARTIAL of the linking rows and counts whatever the rank)
-    launch_residuals(h->stream, h->d, d_xip, d_xid, h->d_theta, h->d_regP, h->d_regD, d_dx, d_dy, h->d_r1, h->d_r2, h->opt.rank, h->rhs_all_ranks ? 1 : 0);
-    if (int rc = enq_solve_local(h, h->d_r1, h->d_r2, 0)) return rc;
-    h->solve_local_done = true; h->refine_pending = true;
+    if (int rc = solve_begin(h)) return rc;
+    launch_residuals(h->stream, h->d, d_xip, d_xid, h->d_theta, h->d_regP, h->d_regD, d_dx, d_dy, h->d_r1, h->d_r2, h->opt.rank, xip_all ? 1 : 0);
+    SolveIo io = solve_io(h->d_cx, h->d_cy, h->d_r1, h->d_r2);
+    io.rhs_rank = 0;
+    if (int rc = enq_solve_local(h, io)) return rc;
+    h->pending = Pending::Refine;
     return TLPK_OK;
+}
+static int refine_finish(tlpk_handle *h, double *d_dx, double *d_dy) {
+    if (int g = refuse(h, d_dx && d_dy, R_MULTI | R_DEVICE)) return g;
+    if (h->pending != Pending::Refine) { h->last_error = "tlpk_refine_finish without a preceding tlpk_refine_local"; return TLPK_BADARG; }
+    h->pending = Pending::None;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = enq_solve_finish(h, solve_io(h->d_cx, h->d_cy, h->d_r1, h->d_r2))) return rc;      // the correction stays rank-local
+    launch_axpy2(h->stream, h->S.n, d_dx, h->d_cx, user_m(h), d_dy, h->d_cy);
+    return solve_end(h);
+}
+int tlpk_refine_local(tlpk_handle *h, const double *d_dx, const double *d_dy, const double *d_xip, const double *d_xid) {
+    if (int g = refuse(h, true, R_DENSE, "tlpk_refine_local")) return g;
+    return refine_local(h, d_dx, d_dy, d_xip, d_xid, false);
 }
 int tlpk_refine_finish(tlpk_handle *h, double *d_dx, double *d_dy) {
-    if (int g = dense_no_split(h, "tlpk_refine_finish")) return g;
-    if (!h || !d_dx || !d_dy) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
-    if (!h->solve_local_done || !h->refine_pending) { h->last_error = "tlpk_refine_finish without a preceding tlpk_refine_local"; return TLPK_BADARG; }
-    h->solve_local_done = false; h->refine_pending = false;
-    HIPCHK(h, hipSetDevice(h->device));
-    double *keep = h->shared_dy; const bool keep_lo = h->dx_local_only;
-    h->shared_dy = nullptr; h->dx_local_only = false;                     // the correction stays rank-local
-    const int rc = enq_solve_finish(h, h->d_cx, h->d_cy, h->d_r2);
-    h->shared_dy = keep; h->dx_local_only = keep_lo;
-    if (rc != TLPK_OK) return rc;
-    launch_axpy2(h->stream, h->S.n, d_dx, h->d_cx, user_m(h), d_dy, h->d_cy);
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipGetLastError());
-    h->solve_timed = true;
-    return TLPK_OK;
+    if (int g = refuse(h, true, R_DENSE, "tlpk_refine_finish")) return g;
+    return refine_finish(h, d_dx, d_dy);
 }
 
-// the two halves of a PAIR of solves (two right-hand sides in one pass over L), split like enq_solve_local / enq_solve_finish at the
-// reduction of the root right-hand sides (two of them: tlpk_root_rhs and tlpk_root_rhs2)
-static int enq_solve2_local(tlpk_handle *h, const double *const *xip, const double *const *xid, int rhs_rank) {
-    const bool k2 = h->S.system == 1;
-    const int rank = rhs_rank >= 0 ? rhs_rank : h->opt.rank;
-    {
-        ProfScope ps(h, TLPK_KC_SPMV);
-        if (h->S.n_sweep_flags > 0) HIPCHK(h, hipMemsetAsync(h->d.sweep_tickets, 0xFF, (size_t)h->d.sweep_reset_bytes2, h->stream));
-        if (h->S.dense_matrix) { double *o[2] = {h->d.ctx.xw, h->d.ctx.xw + h->d.ctx.xw2}; launch_dense_gemv_n(h->stream, h->d, h->d_D, xid, xip, o, 2); }
-        else if (k2) {
-            for (int r = 0; r < 2; ++r) launch_k2_rhs(h->stream, h->d, h->S.k2_n, xip[r], xid[r], r, rank);
-        } else if (h->S.n_dense > 0) launch_dense_rhs(h->stream, h->d, h->d_D, xip, xid, 2);
-        else launch_rhs2(h->stream, h->d, h->d_D, xip, xid, rank);          // both right-hand sides in one launch each (round 6)
-        launch_single_solve(h->stream, h->d, 2);
-    }
-    run_launches(h, h->S.fwd_launches, 0, h->fwd_marker, 0, 2);
-    HIPCHK(h, hipGetLastError());
-    return TLPK_OK;
-}
-static int enq_solve2_finish(tlpk_handle *h, double *const *dx, double *const *dy, const double *const *xid) {
-    const bool k2 = h->S.system == 1;
-    if (h->root_pending) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_root, 0));      // the root front is being factorised on its own stream
-    run_launches(h, h->S.fwd_launches, h->fwd_marker, h->S.fwd_launches.size(), 0, 2);
-    if (k2 || h->S.n_dense > 0) { ProfScope ps(h, TLPK_KC_SPMV); launch_apply_signs(h->stream, h->d, 0); launch_apply_signs(h->stream, h->d, 1); }
-    run_launches(h, h->S.bwd_launches, 0, h->S.bwd_launches.size(), 1, 2);
-    {
-        ProfScope ps(h, TLPK_KC_SPMV);
-        if (h->S.dense_matrix) {
-            const double *y[2] = {h->d.ctx.xw, h->d.ctx.xw + h->d.ctx.xw2};
-            for (int r = 0; r < 2; ++r) HIPCHK(h, hipMemcpyAsync(dy[r], y[r], (size_t)h->S.m * 8, hipMemcpyDeviceToDevice, h->stream));
-            launch_dense_gemv_t(h->stream, h->d, h->d_D, y, xid, dx, 2);
-        } else
-        if (k2) { for (int r = 0; r < 2; ++r) launch_k2_out(h->stream, h->d, h->S.k2_n, dx[r], dy[r], r, h->opt.rank, 0); }
-        else if (h->S.n_dense > 0) launch_dense_out(h->stream, h->d, h->d_D, dy, xid, dx, 2);
-        else if (h->shared_dy || h->dx_local_only) {                              // (shards of a multi-device handle publish into the lead's vectors: per right-hand side)
-            for (int r = 0; r < 2; ++r) {
-                launch_unpermute(h->stream, h->d, dy[r], nullptr, h->opt.rank, r);
-                launch_dx(h->stream, h->d, h->d_D, dy[r], xid[r], dx[r], 0);
-            }
-        } else {
-            launch_unpermute2(h->stream, h->d, dy, h->opt.rank);
-            launch_dx2(h->stream, h->d, h->d_D, dy, xid, dx);
-        }
-    }
-    HIPCHK(h, hipMemcpyAsync(h->h_info + 1, h->d.ctx.info + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return TLPK_OK;
-}
-
-// Two right-hand sides against the same factor in ONE pass over L (the persistent sweeps are bound by the bytes of L: the
-// pair costs little more than one solve).  Tulip's HSD step has such a pair in every iteration: the h-system and the predictor
-// (/root/reference/src/IPM/HSD/step.jl:63 and :79 -- neither right-hand side depends on the other solve).  Results are bit-identical
-// to two tlpk_solve_device calls.  Single-rank handles; with refine_steps > 0 the pair falls back to two refined solves.
+// Two right-hand sides against the same factor in ONE pass over L (SolveIo).  Single-rank handles; with refine_steps > 0 the pair falls back to two refined solves.
 int tlpk_solve2_device(tlpk_handle *h, double *d_dx0, double *d_dy0, const double *d_xip0, const double *d_xid0,
                        double *d_dx1, double *d_dy1, const double *d_xip1, const double *d_xid1) {
-    if (!h || !d_dx0 || !d_dy0 || !d_xip0 || !d_xid0 || !d_dx1 || !d_dy1 || !d_xip1 || !d_xid1) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
+    if (int g = refuse(h, d_dx0 && d_dy0 && d_xip0 && d_xid0 && d_dx1 && d_dy1 && d_xip1 && d_xid1, R_MULTI)) return g;
     if (int g = sharded_needs_split(h, "tlpk_solve2_device")) return g;
-    if (!h->has_device) return TLPK_NO_DEVICE;
-    if (!h->factored) return TLPK_NOT_FACTORED;
+    if (int g = refuse(h, true, R_DEVICE | R_FACTORED)) return g;
     if (h->refine_steps > 0 || !h->S.sweep) {            // refinement / launch-per-block schedule: two ordinary solves
         const int rc = tlpk_solve_device(h, d_dx0, d_dy0, d_xip0, d_xid0);
         return rc != TLPK_OK ? rc : tlpk_solve_device(h, d_dx1, d_dy1, d_xip1, d_xid1);
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    prof_begin(h, false);
-    h->solve_timed = false;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    const double *xip[2] = {d_xip0, d_xip1}, *xid[2] = {d_xid0, d_xid1};
-    double *dx[2] = {d_dx0, d_dx1}, *dy[2] = {d_dy0, d_dy1};
-    h->solve_epoch += 1;
-    const GraphKey key{3, {d_dx0, d_dy0, d_xip0, d_xid0, d_dx1, d_dy1, d_xip1, d_xid1}};
-    const int grc = graph_or_direct(h, key, [&]() -> int {
-        const int q = enq_solve2_local(h, xip, xid, -1);
-        return q != TLPK_OK ? q : enq_solve2_finish(h, dx, dy, xid);
-    }, graph_usable_solve(h));
-    if (grc != TLPK_OK) return grc;
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipGetLastError());
-    h->solve_timed = true;
-    return TLPK_OK;
+    return solve_whole(h, SolveIo{2, {d_xip0, d_xip1}, {d_xid0, d_xid1}, {d_dx0, d_dx1}, {d_dy0, d_dy1}});
 }
 
 // The pair in two halves, for sharded handles: tlpk_solve2_local -> all-reduce of tlpk_root_rhs AND tlpk_root_rhs2 (the root right-hand
 // sides of the two systems; one collective over both buffers if the communicator allows) -> tlpk_solve2_finish.
 int tlpk_solve2_local(tlpk_handle *h, const double *d_xip0, const double *d_xid0, const double *d_xip1, const double *d_xid1) {
-    if (int g = dense_no_split(h, "tlpk_solve2_local")) return g;
-    if (!h || !d_xip0 || !d_xid0 || !d_xip1 || !d_xid1) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
-    if (!h->factored) return TLPK_NOT_FACTORED;
-    if (!h->S.sweep) { h->last_error = "tlpk_solve2_local needs the persistent-sweep schedule (TLPK_SWEEP=0 is set)"; return TLPK_BADARG; }
-    if (h->solve_local_done) { h->last_error = "tlpk_solve2_local inside an unfinished solve"; return TLPK_BADARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    prof_begin(h, false);
-    h->solve_timed = false;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    h->solve_epoch += 1;
-    const double *xip[2] = {d_xip0, d_xip1}, *xid[2] = {d_xid0, d_xid1};
-    if (int rc = enq_solve2_local(h, xip, xid, h->rhs_all_ranks ? 0 : -1)) return rc;
-    h->solve_local_done = true; h->pair_pending = true;
-    return TLPK_OK;
-}
-int tlpk_root_rhs2(tlpk_handle *h, double **d_ptr, int64_t *count) {
-    if (int g = dense_no_split(h, "tlpk_root_rhs2")) return g;
-    if (!h || !d_ptr || !count) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
-    *d_ptr = h->nlink ? h->d.ctx.xw + h->d.ctx.xw2 + h->first_link : nullptr;
-    *count = h->nlink;
-    return TLPK_OK;
+    if (int g = refuse(h, true, R_DENSE, "tlpk_solve2_local")) return g;
+    return solve_local(h, SolveIo{2, {d_xip0, d_xip1}, {d_xid0, d_xid1}, {nullptr, nullptr}, {nullptr, nullptr}});
 }
 int tlpk_solve2_finish(tlpk_handle *h, double *d_dx0, double *d_dy0, const double *d_xid0, double *d_dx1, double *d_dy1, const double *d_xid1) {
-    if (int g = dense_no_split(h, "tlpk_solve2_finish")) return g;
-    if (!h || !d_dx0 || !d_dy0 || !d_xid0 || !d_dx1 || !d_dy1 || !d_xid1) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
-    if (!h->solve_local_done || !h->pair_pending) { h->last_error = "tlpk_solve2_finish without a preceding tlpk_solve2_local"; return TLPK_BADARG; }
-    h->solve_local_done = false; h->pair_pending = false;
-    HIPCHK(h, hipSetDevice(h->device));
-    double *dx[2] = {d_dx0, d_dx1}, *dy[2] = {d_dy0, d_dy1};
-    const double *xid[2] = {d_xid0, d_xid1};
-    if (int rc = enq_solve2_finish(h, dx, dy, xid)) return rc;
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipGetLastError());
-    h->solve_timed = true;
-    return TLPK_OK;
+    if (int g = refuse(h, true, R_DENSE, "tlpk_solve2_finish")) return g;
+    return solve_finish(h, SolveIo{2, {nullptr, nullptr}, {d_xid0, d_xid1}, {d_dx0, d_dx1}, {d_dy0, d_dy1}});
 }
 
 int tlpk_sync(tlpk_handle *h) {
@@ -1604,7 +1540,7 @@ int tlpk_solve(tlpk_handle *h, double *dx, double *dy, const double *xi_p, const
     if (int rc = ensure_pinned(h)) return rc;
     const i64 un = user_n(h), um = user_m(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    static const bool timing = [] { const char *e = std::getenv("TLPK_HOSTIO_TIMING"); return e && std::atoi(e) != 0; }();
+    const bool timing = hostio_timing();
     h->io_timing = timing;
     const double t0 = timing ? now_ms() : 0.0;
     const HostVec in[2] = {{h->d_xip, const_cast<double *>(xi_p), um}, {h->d_xid, const_cast<double *>(xi_d), un}};
@@ -1660,10 +1596,6 @@ struct Rccl {
 Rccl g_rccl;
 constexpr int NCCL_DOUBLE = 8, NCCL_SUM = 0;          // rccl.h: ncclFloat64 = 8, ncclSum = 0
 
-// which: 0 root panel, 1 root right-hand side, 2 root right-hand side of the second system of a pair
-int root_buf(tlpk_handle *c, int which, double **p, int64_t *cnt) {
-    return which == 0 ? tlpk_root_panel(c, p, cnt) : (which == 1 ? tlpk_root_rhs(c, p, cnt) : tlpk_root_rhs2(c, p, cnt));
-}
 int multi_allreduce_rccl(tlpk_handle *h, int which) {
     const int N = (int)h->sub.size();
     int rc = g_rccl.GroupStart();
@@ -1878,7 +1810,7 @@ int multi_update(tlpk_handle *h, const double *theta, const double *regP, const 
             HIPCHK(c, upload_range(c->d_regP, p1, c->col_lo, c->col_hi, c->stream));
             HIPCHK(c, upload_range(c->d_regD, p2, c->row_lo, c->row_hi, c->stream));
             HIPCHK(c, upload_range(c->d_regD, p2, c->link_lo, c->link_hi, c->stream));
-            return tlpk_update_local(c, c->d_theta, c->d_regP, c->d_regD);
+            return update_local(c, c->d_theta, c->d_regP, c->d_regD);
         })) return rc;
     return multi_update_tail(h, t_in);
 }
@@ -1896,7 +1828,7 @@ int multi_solve(tlpk_handle *h, double *dx, double *dy, const double *xi_p, cons
             HIPCHK(c, upload_range(c->d_xip, pi0, c->row_lo, c->row_hi, c->stream));
             HIPCHK(c, upload_range(c->d_xip, pi0, c->link_lo, c->link_hi, c->stream));
             HIPCHK(c, upload_range(c->d_xid, pi1, c->col_lo, c->col_hi, c->stream));
-            return tlpk_solve_local(c, c->d_xip, c->d_xid);
+            return solve_local(c, solve_io(nullptr, nullptr, c->d_xip, c->d_xid));
         })) return rc;
     if (int rc = multi_allreduce(h, 1)) return rc;
     if (h->refine_steps > 0) {
@@ -1904,8 +1836,7 @@ int multi_solve(tlpk_handle *h, double *dx, double *dy, const double *xi_p, cons
         // step is one more split solve on the residuals with the same reduction in the middle, and the owned slices are published
         // to the lead device's job-wide vectors at the end
         for (tlpk_handle *c : h->sub) {
-            c->shared_dy = nullptr; c->dx_local_only = false;
-            const int rc = tlpk_solve_finish(c, c->d_dx, c->d_dy, c->d_xid);
+            const int rc = solve_finish(c, solve_io(c->d_dx, c->d_dy, nullptr, c->d_xid));
             if (rc != TLPK_OK) { h->last_error = c->last_error; return rc; }
         }
         {
@@ -1918,12 +1849,12 @@ int multi_solve(tlpk_handle *h, double *dx, double *dy, const double *xi_p, cons
             for (int it = 0; it < h->refine_steps && !stop; ++it) {
                 if (int rc = multi_guarded_step(h, dxs, dys, xps, xds, false, norm, &stop, [&]() -> int {
                         for (tlpk_handle *c : h->sub) {
-                            const int q = tlpk_refine_local(c, c->d_dx, c->d_dy, c->d_xip, c->d_xid);
+                            const int q = refine_local(c, c->d_dx, c->d_dy, c->d_xip, c->d_xid, false);
                             if (q != TLPK_OK) { h->last_error = c->last_error; return q; }
                         }
                         if (int q = multi_allreduce(h, 1)) return q;
                         for (tlpk_handle *c : h->sub) {
-                            const int q = tlpk_refine_finish(c, c->d_dx, c->d_dy);
+                            const int q = refine_finish(c, c->d_dx, c->d_dy);
                             if (q != TLPK_OK) { h->last_error = c->last_error; return q; }
                         }
                         return TLPK_OK;
@@ -1942,8 +1873,9 @@ int multi_solve(tlpk_handle *h, double *dx, double *dy, const double *xi_p, cons
         }
     } else if (int rc = for_shards(h, [&](tlpk_handle *c, int r) -> int {
         // every rank fills its own entries of the lead device's dx / dy (P2P stores); its local dy feeds its k_dx
-        c->shared_dy = lead->d_dy; c->dx_local_only = true;
-        const int q = tlpk_solve_finish(c, lead->d_dx, (c->S.system == 1) ? lead->d_dy : (r == 0 ? h->multi_tmp + h->multi_dy0_off : c->d_dy), c->d_xid);
+        SolveIo io = solve_io(lead->d_dx, (c->S.system == 1) ? lead->d_dy : (r == 0 ? h->multi_tmp + h->multi_dy0_off : c->d_dy), nullptr, c->d_xid);
+        io.shared_dy = lead->d_dy; io.dx_local_only = true;
+        const int q = solve_finish(c, io);
         if (q != TLPK_OK) return q;
         if (r > 0) HIPCHK(c, hipEventRecord(h->multi_ev[r], c->stream));
         return TLPK_OK;
@@ -1994,22 +1926,16 @@ void shard_ranges(tlpk_handle *c) {
 extern "C++" {
 int multi_update_resident(tlpk_handle *h) {
     const double t_in = now_ms();
-    if (int rc = for_shards(h, [](tlpk_handle *c, int) { return tlpk_update_local(c, c->d_theta, c->d_regP, c->d_regD); })) return rc;
+    if (int rc = for_shards(h, [](tlpk_handle *c, int) { return update_local(c, c->d_theta, c->d_regP, c->d_regD); })) return rc;
     return multi_update_tail(h, t_in);
 }
 int multi_solve_resident(tlpk_handle *h, double *const *dx, double *const *dy, const double *const *xip, const double *const *xid) {
     if (!h->factored) return TLPK_NOT_FACTORED;
-    if (int rc = for_shards(h, [&](tlpk_handle *c, int r) {
-            c->rhs_all_ranks = true;                     // every shard's xi_p counts on the linking rows (partial residuals)
-            const int q = tlpk_solve_local(c, xip[r], xid[r]);
-            c->rhs_all_ranks = false;
-            return q;
-        })) return rc;
+    // every shard's xi_p counts on the linking rows (partial residuals: rhs_rank = 0); the solution stays shard-resident
+    auto io = [&](int r) { SolveIo s = solve_io(dx[r], dy[r], xip[r], xid[r]); s.rhs_rank = 0; return s; };
+    if (int rc = for_shards(h, [&](tlpk_handle *c, int r) { return solve_local(c, io(r)); })) return rc;
     if (int rc = multi_allreduce(h, 1)) return rc;
-    if (int rc = for_shards(h, [&](tlpk_handle *c, int r) {
-            c->shared_dy = nullptr; c->dx_local_only = false;              // the solution stays shard-resident
-            return tlpk_solve_finish(c, dx[r], dy[r], xid[r]);
-        })) return rc;
+    if (int rc = for_shards(h, [&](tlpk_handle *c, int r) { return solve_finish(c, io(r)); })) return rc;
     // iterative refinement (Backend(ngpus = N, refine = k) under the device-resident loops; round-3 advisor finding: only the host-pointer
     // tlpk_solve refined): one more split solve per step on the residuals every shard forms for the rows / columns it owns -- with the SAME
     // convention as the solve above, every shard's xi_p counting on the linking rows
@@ -2019,14 +1945,9 @@ int multi_solve_resident(tlpk_handle *h, double *const *dx, double *const *dy, c
         if (int rc = multi_resid_norm(h, dx, dy, xip, xid, true, norm)) return rc;
         for (int it = 0; it < h->refine_steps && !stop; ++it) {
             if (int rc = multi_guarded_step(h, dx, dy, xip, xid, true, norm, &stop, [&]() -> int {
-                    if (int q = for_shards(h, [&](tlpk_handle *c, int r) {
-                            c->rhs_all_ranks = true;
-                            const int q2 = tlpk_refine_local(c, dx[r], dy[r], xip[r], xid[r]);
-                            c->rhs_all_ranks = false;
-                            return q2;
-                        })) return q;
+                    if (int q = for_shards(h, [&](tlpk_handle *c, int r) { return refine_local(c, dx[r], dy[r], xip[r], xid[r], true); })) return q;
                     if (int q = multi_allreduce(h, 1)) return q;
-                    return for_shards(h, [&](tlpk_handle *c, int r) { return tlpk_refine_finish(c, dx[r], dy[r]); });
+                    return for_shards(h, [&](tlpk_handle *c, int r) { return refine_finish(c, dx[r], dy[r]); });
                 })) return rc;
         }
     }
@@ -2042,15 +1963,11 @@ int multi_solve2_resident(tlpk_handle *h, double *const *dx0, double *const *dy0
         if (int rc = multi_solve_resident(h, dx0, dy0, xip0, xid0)) return rc;
         return multi_solve_resident(h, dx1, dy1, xip1, xid1);
     }
-    if (int rc = for_shards(h, [&](tlpk_handle *c, int r) {
-            c->rhs_all_ranks = true;
-            const int q = tlpk_solve2_local(c, xip0[r], xid0[r], xip1[r], xid1[r]);
-            c->rhs_all_ranks = false;
-            return q;
-        })) return rc;
+    auto io = [&](int r) { SolveIo s{2, {xip0[r], xip1[r]}, {xid0[r], xid1[r]}, {dx0[r], dx1[r]}, {dy0[r], dy1[r]}}; s.rhs_rank = 0; return s; };
+    if (int rc = for_shards(h, [&](tlpk_handle *c, int r) { return solve_local(c, io(r)); })) return rc;
     if (int rc = multi_allreduce(h, 1)) return rc;
     if (int rc = multi_allreduce(h, 2)) return rc;
-    return for_shards(h, [&](tlpk_handle *c, int r) { return tlpk_solve2_finish(c, dx0[r], dy0[r], xid0[r], dx1[r], dy1[r], xid1[r]); });
+    return for_shards(h, [&](tlpk_handle *c, int r) { return solve_finish(c, io(r)); });
 }
 }  // extern "C++"
 
@@ -2363,9 +2280,7 @@ int64_t tlpk_symbolic_get_f64(const tlpk_handle *h, const char *what, double *bu
 }
 
 int tlpk_get_factor(tlpk_handle *h, double *lval, int64_t cap) {
-    if (!h || !lval) return TLPK_BADARG;
-    if (!h->sub.empty()) { h->last_error = "multi-device handle: only tlpk_update / tlpk_solve / tlpk_info / tlpk_destroy apply"; return TLPK_BADARG; }
-    if (!h->has_device) return TLPK_NO_DEVICE;
+    if (int g = refuse(h, lval != nullptr, R_MULTI | R_DEVICE)) return g;
     if (cap < h->S.lval_len) return TLPK_BADARG;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));

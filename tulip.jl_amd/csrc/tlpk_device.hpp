@@ -91,13 +91,12 @@ void launch_assemble(hipStream_t st, const DevArrays &a, const double *D, const 
 void launch_zero_panels(hipStream_t st, const DevArrays &a, int part = -1);
 void launch_tasks(hipStream_t st, const DevArrays &a, const Launch &L, const SweepArgs *sw = nullptr, int nrhs = 1);
 void launch_single_factor(hipStream_t st, const DevArrays &a);
-void launch_single_solve(hipStream_t st, const DevArrays &a, int rhs = 0);
-void launch_rhs(hipStream_t st, const DevArrays &a, const double *D, const double *xi_p, const double *xi_d, int rank, int rhs = 0);
-void launch_unpermute(hipStream_t st, const DevArrays &a, double *dy, double *dy_shared = nullptr, int rank = 0, int rhs = 0);
-// the pair's per-right-hand-side kernels, both right-hand sides in ONE launch each (grid y = right-hand side): single-rank handles
-void launch_rhs2(hipStream_t st, const DevArrays &a, const double *D, const double *const *xi_p, const double *const *xi_d, int rank);
-void launch_unpermute2(hipStream_t st, const DevArrays &a, double *const *dy, int rank);
-void launch_dx2(hipStream_t st, const DevArrays &a, const double *D, double *const *dy, const double *const *xi_d, double *const *dx);
+// The per-right-hand-side kernels of a solve: nrhs = 1, or 2 for a pair (ONE launch each where the kernel has a grid-y form, grid y = right-hand side; slots
+// 0 .. nrhs - 1 of xw); the pointer arrays hold nrhs entries.  dy_shared / local_only: shards of a multi-device handle publishing into the lead's vectors (nrhs = 1)
+void launch_single_solve(hipStream_t st, const DevArrays &a, int nrhs = 1);
+void launch_rhs(hipStream_t st, const DevArrays &a, const double *D, const double *const *xi_p, const double *const *xi_d, int rank, int nrhs);
+void launch_unpermute(hipStream_t st, const DevArrays &a, double *const *dy, double *dy_shared, int rank, int nrhs);
+void launch_dx(hipStream_t st, const DevArrays &a, const double *D, double *const *dy, const double *const *xi_d, double *const *dx, int local_only, int nrhs);
 void launch_residuals(hipStream_t st, const DevArrays &a, const double *xi_p, const double *xi_d, const double *theta, const double *regP,
                       const double *regD, const double *dx, const double *dy, double *r1, double *r2, int rank, int xip_all = 0);
 void launch_publish(hipStream_t st, const DevArrays &a, const double *dx, double *dx_job, const double *dy, double *dy_job);
@@ -107,13 +106,12 @@ void launch_absmax2(hipStream_t st, const DevArrays &a, const double *r1, const 
 void launch_refine_decide(hipStream_t st, unsigned long long *ref);
 void launch_candidate(hipStream_t st, i64 n, const double *x, double *cx, i64 m, const double *y, double *cy);
 void launch_refine_commit(hipStream_t st, i64 n, double *x, const double *cx, i64 m, double *y, const double *cy, const unsigned long long *ref);
-void launch_dx(hipStream_t st, const DevArrays &a, const double *D, const double *dy, const double *xi_d, double *dx, int local_only = 0);
 void launch_sum_to(hipStream_t st, i64 len, double *out, const double *own, const double *src, int nsrc, i64 stride);
 void launch_sum_ranked(hipStream_t st, i64 len, double *inout, const double *stage, int nranks, int own_rank, i64 stride);
 void launch_k2_diag(hipStream_t st, i64 n, const double *theta, const double *regP, double *D2);
-void launch_k2_rhs(hipStream_t st, const DevArrays &a, i64 n, const double *xi_p, const double *xi_d, int rhs = 0, int rank = 0);
-void launch_apply_signs(hipStream_t st, const DevArrays &a, int rhs = 0);
-void launch_k2_out(hipStream_t st, const DevArrays &a, i64 n, double *dx, double *dy, int rhs = 0, int rank = 0, int owned_only = 0);
+void launch_k2_rhs(hipStream_t st, const DevArrays &a, i64 n, const double *const *xi_p, const double *const *xi_d, int rank, int nrhs);
+void launch_apply_signs(hipStream_t st, const DevArrays &a, int nrhs);
+void launch_k2_out(hipStream_t st, const DevArrays &a, i64 n, double *const *dx, double *const *dy, int rank, int owned_only, int nrhs);
 // K1 with dense columns (kernels.hip: k_dense_*): D = [sparse j: 1 / (theta + regP), dense j: theta + regP ; 1]; the permuted right-hand side
 // [xi_p + A_s D_s xi_d_s ; xi_d_d]; [dy ; dx_d] = P' x and dx_s = D_s (A_s' dy - xi_d_s).  nrhs = 2: both right-hand sides of a pair in one
 // launch each (grid y), slots 0 / 1 of xw -- the same arithmetic per right-hand side as two single solves

@@ -57,7 +57,8 @@ struct tlpk_handle {
     double *pin_in = nullptr, *pin_out = nullptr;   // pinned staging of the host-pointer entry points (lazily allocated)
     bool io_timing = false; double io_t_first = 0, io_t_last = 0;   // TLPK_HOSTIO_TIMING: when the first / last device-to-host group had landed
     std::vector<hipEvent_t> io_events;              // one per device-to-host piece of tlpk_solve (tlpk_api.cpp: stage_out)
-    bool factored = false, local_done = false, solve_local_done = false, solve_timed = false, refine_pending = false, pair_pending = false;
+    bool factored = false, local_done = false, solve_timed = false;
+    enum class Pending { None, Solve, Pair, Refine } pending = Pending::None;   // which split-phase first half (tlpk_solve_local / tlpk_solve2_local / tlpk_refine_local) waits for its second
     i64 fail_col = -1;
     double ms_analyse = 0, ms_update = 0, ms_solve = 0;
     tlpk_kernel_times kt{};
@@ -79,19 +80,13 @@ struct tlpk_handle {
     void *shard_pool = nullptr;         // parent: one persistent host thread per shard (tlpk_api.cpp: ShardPool) -- the shards' launches are enqueued concurrently
     double ms_enqueue_update = 0;       // parent: host time from the entry of tlpk_update until every shard's work is enqueued
     i64 col_lo = 0, col_hi = 0, row_lo = 0, row_hi = 0, link_lo = 0, link_hi = 0;   // child: slices of the job-wide input vectors it reads
-    double *shared_dy = nullptr;        // child: job-wide dy on the lead device (P2P), filled with the rows this rank owns
-    bool dx_local_only = false;         // child: dx is the job-wide vector, leave the other ranks' columns alone
     bool stagger = false, stagger_armed = false; i64 stagger_min = 10000; hipEvent_t ev_stagger = nullptr;   // TLPK_STAGGER (experiment, tlpk_api.cpp: run_launches)
-    bool rhs_all_ranks = false;         // child, device-resident IPM: this solve adds the shard's xi_p on the linking rows whatever its rank
     // hipGraph replay of the static schedules (tlpk_api.cpp: graph_or_direct): instantiated graphs and their keys
     bool use_graph = true;              // TLPK_GRAPH=0 turns it off; switched off for good if capture fails on this system
     bool force_graph = false;           // TLPK_GRAPH=2: also for schedules with concurrent stream groups
-    bool update_whole = false, solve_whole = false;   // internal: the composed entry point enqueues both halves itself
     std::vector<hipGraphExec_t> graph_execs;
     std::vector<std::vector<char>> graph_keys;
     IpmState *ipm = nullptr;            // device-resident interior-point vectors (tlpk_ipm_load), freed by tlpk_destroy
-    bool composed = false;              // dense-matrix handles: a composed entry point (tlpk_update_device, tlpk_solve_device) is running its two halves -- the
-                                        // split-phase calls themselves are refused on such a handle (tlpk_api.cpp: dense_no_split)
     std::string last_error;
 };
 
