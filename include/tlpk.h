@@ -122,6 +122,9 @@ typedef struct tlpk_stats {
                                   m, n, nnzA are the caller's; nnzS, nnzL, n_pairs, fail_col, ... describe the factored matrix of order m + k */
     double  flops_syrk;        /* dense-matrix handles (tlpk_create_dense): n m (m + 1), the flops of the lower triangle of A*D*A' on the matrix cores
                                   (2 per product); 0 on sparse handles */
+    double  ms_last_set_values; /* device time of the last tlpk_set_values* (HIP events on the handle's stream; multi-device handles: the slowest shard);
+                                   host time on analyse-only handles */
+    int64_t set_values_bytes;  /* device memory held by the maps of tlpk_set_values (part of device_bytes); 0 before the first call */
 } tlpk_stats;
 
 /* per-kernel-class timing, filled when options.profile = 1 */
@@ -163,6 +166,25 @@ int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr,
  * states the bytes).  The split-phase calls (tlpk_*_local / tlpk_*_finish, tlpk_root_*, tlpk_refine_*) do not apply: TLPK_BADARG. */
 int tlpk_create_dense(tlpk_handle **out, int64_t m, int64_t n, const double *A, int64_t lda, const tlpk_options *opt);
 void tlpk_destroy(tlpk_handle *h);
+
+/* New numerical values on the analysed pattern: "analyse once, factorise many value sets" (branch-and-bound nodes, scenario re-solves, successive LPs,
+ * re-scaling).  nzval: the values of the matrix given to tlpk_create / tlpk_create_multi in the caller's CSC order, len == nnzA; explicit zeros are values.
+ * Nothing of the analysis is repeated and no array is reallocated: the products of the assembly lists and the value arrays of the copies of A are
+ * recomputed in place, on the device, from maps that the FIRST call builds (one walk of the lists on the host) and uploads -- tlpk_stats.device_bytes grows
+ * once by tlpk_stats.set_values_bytes.  The refreshed handle equals a fresh handle on the new values bit for bit.
+ * After TLPK_OK the handle is analysed but NOT factored (solves: TLPK_NOT_FACTORED until the next successful update); a pending asynchronous update, pair or
+ * refinement is completed / dropped as an update does.  TLPK_BADARG (NULL, len != nnzA, lda < m, a sparse call on a dense-matrix handle or the reverse)
+ * leaves the handle untouched and factored; tlpk_last_error has the sentence.  Every handle kind: K1, K2, dense_cols, refine_steps, sharded (every rank passes
+ * the full nzval), tlpk_create_multi (one call serves every shard), analyse-only (the host arrays are refreshed: tlpk_symbolic_get_f64(h, "pair_w")).
+ * The _device variants take a pointer on the handle's device and enqueue on tlpk_stream(h): the caller orders its producer before that stream and may reuse
+ * the buffer after tlpk_sync; single-device handles only (multi-device: TLPK_BADARG, analyse-only: TLPK_NO_DEVICE).
+ * A handle with device-resident loops (tlpk_ipm_load): every tlpk_ipm_* / tlpk_mpc_* call except tlpk_ipm_reload and tlpk_ipm_get then returns TLPK_BADARG
+ * until tlpk_ipm_reload has run. */
+int tlpk_set_values(tlpk_handle *h, const double *nzval, int64_t len);                 /* host pointer; blocks */
+int tlpk_set_values_device(tlpk_handle *h, const double *d_nzval, int64_t len);        /* device pointer; enqueued on tlpk_stream(h) */
+/* Dense-matrix handles (tlpk_create_dense): column-major m x n, lda >= m. */
+int tlpk_set_values_dense(tlpk_handle *h, const double *A, int64_t lda);
+int tlpk_set_values_dense_device(tlpk_handle *h, const double *d_A, int64_t lda);
 
 /* Host-pointer entry points (what the Julia glue calls). */
 int tlpk_update(tlpk_handle *h, const double *theta_inv /*n*/, const double *regP /*n*/,
@@ -285,6 +307,11 @@ int tlpk_get_factor(tlpk_handle *h, double *lval, int64_t cap);
  * (HSD.jl:238-247).  tlpk_ipm_reset restores the starting point. */
 int tlpk_ipm_load(tlpk_handle *h, const double *b, const double *c, const double *l, const double *u);
 int tlpk_ipm_reset(tlpk_handle *h);
+/* New LP data on a handle that has been tlpk_ipm_load'ed (typically after tlpk_set_values*): refreshes the copies of A the loops keep, takes the vectors
+ * that are not NULL (NULL = keep), recomputes the finite-bound flags -- bounds may change between finite and infinite -- and restores the HSD starting
+ * point.  The device vectors are reused: tlpk_stats.device_bytes does not grow.  All four NULL: same data, new A, start over.  A handle that was never
+ * loaded: TLPK_BADARG (call tlpk_ipm_load first). */
+int tlpk_ipm_reload(tlpk_handle *h, const double *b, const double *c, const double *l, const double *u);
 /* HSD.jl:77-128, 136-196.  out[13] = { |rp|inf, |rl|inf, |ru|inf, |rd|inf, c'x, b'y, lz'zl, uz'zu, xl'zl + xu'zu,
  *                                      |Ax|inf, |(x-xl) lflag|inf, |(x+xu) uflag|inf, |A'y + zl lflag - zu uflag|inf } */
 int tlpk_ipm_residuals(tlpk_handle *h, double tau, double *out);

@@ -22,7 +22,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from . import _lib  # noqa: F401,E402
 from .kkt import (K1, K2, Backend, DenseBackend, DimensionMismatch, HIPDenseNormalEquations, HIPNormalEquations, OutOfMemoryError,  # noqa: F401,E402
                   PosDefException, arithmetic, backend, linear_system, run_ls_tests, setup,
-                  solve, update)
+                  set_values, set_values_device, solve, update)
 from .model import Model  # noqa: F401,E402
 from .presolve import Presolve, PresolveOptions  # noqa: F401,E402
 from .problem import LP, read_free_mps, standard_form  # noqa: F401,E402

@@ -42,7 +42,8 @@ class Stats(C.Structure):
                 ("root_panel_len", C.c_int64), ("flops_update", C.c_double),
                 ("flops_update_alg", C.c_double), ("ms_enqueue_update", C.c_double), ("refine_rejected", C.c_int64),
                 ("flops_update_chain", C.c_double), ("flops_update_alg_chain", C.c_double), ("chain_launches", C.c_int64), ("chain_items", C.c_int64),
-                ("n_dense_cols", C.c_int64), ("flops_syrk", C.c_double)]
+                ("n_dense_cols", C.c_int64), ("flops_syrk", C.c_double),
+                ("ms_last_set_values", C.c_double), ("set_values_bytes", C.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -70,6 +71,7 @@ EXPORTS = [
     "tlpk_detect_blocks", "tlpk_solve2_device", "tlpk_ipm_hsolve_newton", "tlpk_update_device_async", "tlpk_ipm_factor_hsolve_newton",
     "tlpk_refine_local", "tlpk_refine_finish", "tlpk_solve2_local", "tlpk_root_rhs2", "tlpk_solve2_finish", "tlpk_last_create_error",
     "tlpk_host_copy_threads", "tlpk_create_dense",
+    "tlpk_set_values", "tlpk_set_values_device", "tlpk_set_values_dense", "tlpk_set_values_dense_device", "tlpk_ipm_reload",
 ]
 
 
@@ -91,6 +93,13 @@ def lib():
     L.tlpk_create_multi.restype = C.c_int
     L.tlpk_create_dense.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, pd, C.c_int64, C.POINTER(Options)]
     L.tlpk_create_dense.restype = C.c_int
+    L.tlpk_set_values.argtypes = [vp, pd, C.c_int64]
+    L.tlpk_set_values_device.argtypes = [vp, vp, C.c_int64]
+    L.tlpk_set_values_dense.argtypes = [vp, pd, C.c_int64]
+    L.tlpk_set_values_dense_device.argtypes = [vp, vp, C.c_int64]
+    L.tlpk_ipm_reload.argtypes = [vp, pd, pd, pd, pd]
+    for name in ("tlpk_set_values", "tlpk_set_values_device", "tlpk_set_values_dense", "tlpk_set_values_dense_device", "tlpk_ipm_reload"):
+        getattr(L, name).restype = C.c_int
     L.tlpk_destroy.argtypes = [vp]
     L.tlpk_destroy.restype = None
     L.tlpk_update.argtypes = [vp, pd, pd, pd]

@@ -837,6 +837,66 @@ int analyse_common(Symbolic &S, i64 m64, i64 n64, const i64 *colptr, const i64 *
     return TLPK_OK;
 }
 
+// ---- the products of the assembly lists (step 14 of analyse_rank; build_value_maps) ----
+// S[ii,kk] = sum_j A[i,j] D_j A[k,j]: walk_pairs visits the products of pivot column kk (permuted numbering) in the order of the lists -- rows of A' in
+// order, entries of the column of A in order -- and hands f(ii, pa, pb, j) the permuted row of the entry, the positions of the two factors in the value array
+// of the analysed matrix (the product is value[pa] * value[pb], in this order) and the column of D; pa = pb = -1: the constant -1 on the diagonal of a
+// variable node (K2) / a dense-column node.
+struct PairWalk {
+    const i64 *Ap; const i32 *Ai; const i64 *Tp; const i32 *Tj; const i32 *Tpos; const i32 *perm, *iperm; const char *col_local;
+    i32 system; i64 k2_n; i32 rank; i32 dense_m, dense_n; const i64 *dense_cols;
+};
+template <class F>
+static inline void walk_pairs(const PairWalk &W, i32 kk, bool is_root, F &&f) {
+    const i32 k = W.perm[kk];
+    if (W.system == 1) {
+        // Augmented system: the diagonal of a variable node is -(theta + regP) = -1 * D2[k]; an
+        // off-diagonal entry is the constant A[i,j] = A[i,j] * D2[k2_n] with D2[k2_n] = 1 (the columns
+        // of the incidence matrix carry (1, A[i,j]) on the variable / constraint node).
+        // Sharded runs: the assembled entries of the replicated root front (linking constraint nodes and the
+        // variable nodes of columns that touch linking rows only) belong to rank 0; the all-reduce of the root
+        // panel adds the ranks' extend-add contributions to them.
+        if (is_root && W.rank != 0) return;
+        if (k < W.k2_n) f(kk, (i64)-1, (i64)-1, k);
+        for (i64 q = W.Tp[k]; q < W.Tp[k + 1]; ++q) {
+            const i32 j = W.Tj[q];
+            const i64 pa = W.Tpos[q];
+            for (i64 p = W.Ap[j]; p < W.Ap[j + 1]; ++p) {
+                const i32 ii = W.iperm[W.Ai[p]];
+                if (ii <= kk) continue;
+                f(ii, pa, p, (i32)W.k2_n);
+            }
+        }
+    } else if (W.dense_m >= 0) {
+        // K1 with dense columns; D = [sparse j: 1 / (theta + regP), dense j: theta + regP ; 1] (kernels.hip: k_dense_diag).
+        //   constraint node: the products A[i,j] A[k,j] D_j of the SPARSE columns (columns [0, dense_n) of the incidence matrix; a dense
+        //   column is empty there) and the border entries A[i,j] = A[i,j] * D[dense_n] of the incidence columns (A[i,j] on row i, 1 on node
+        //   m + t); dense node m + t: -1 * D[dense_cols[t]] on the diagonal (its border entries come from the constraint nodes, ordered before it)
+        if (k >= W.dense_m) f(kk, (i64)-1, (i64)-1, (i32)W.dense_cols[(size_t)(k - W.dense_m)]);
+        for (i64 q = W.Tp[k]; q < W.Tp[k + 1]; ++q) {
+            const i32 j = W.Tj[q];
+            const i64 pa = W.Tpos[q];
+            const bool incidence = j >= W.dense_n;
+            for (i64 p = W.Ap[j]; p < W.Ap[j + 1]; ++p) {
+                const i32 ii = W.iperm[W.Ai[p]];
+                if (incidence ? ii <= kk : ii < kk) continue;
+                f(ii, pa, p, incidence ? W.dense_n : j);
+            }
+        }
+    } else {
+        for (i64 q = W.Tp[k]; q < W.Tp[k + 1]; ++q) {
+            const i32 j = W.Tj[q];
+            if (is_root && !W.col_local[j]) continue;          // sharded: a column of the root front's products belongs to the rank that owns it
+            const i64 pa = W.Tpos[q];
+            for (i64 p = W.Ap[j]; p < W.Ap[j + 1]; ++p) {
+                const i32 ii = W.iperm[W.Ai[p]];
+                if (ii < kk) continue;
+                f(ii, pa, p, j);
+            }
+        }
+    }
+}
+
 int analyse_rank(Symbolic &S, const Options &opt) {
     PhaseTimer pt;
     AnalysePoolScope pool_scope;
@@ -1209,11 +1269,6 @@ int analyse_rank(Symbolic &S, const Options &opt) {
                 })) return fail(S, TLPK_OOM, "out of memory while building the assembly lists");
         }
         pt.mark("assembly lists: traverse");
-        auto col_is_mine = [&](i32 j) -> bool {
-            if (opt.nranks == 1 || !have_blocks) return true;
-            const i32 b = col_block[j];
-            return (b < 0) ? (opt.rank == 0) : (block_owner[b] == opt.rank);
-        };
         // Round 6: ONE traversal of A per pivot column instead of two (count, then fill).  Fronts are independent (every stored entry of S belongs to exactly one
         // pivot column of exactly one front): handed out to the host threads.  A thread walks the products of a column once -- the order of the old fill pass:
         // rows of A' in order, entries of the column of A in order --, groups them by entry of S with a stable counting sort inside the column (a few hundred
@@ -1223,6 +1278,8 @@ int analyse_rank(Symbolic &S, const Options &opt) {
         // K1 with dense columns: constraint nodes [0, dense_m); the incidence matrix's columns [0, dense_n) are A's (the dense ones empty)
         const i32 dense_m = S.n_dense > 0 ? m - (i32)S.n_dense : -1;
         const i32 dense_n = (i32)S.dense_n;
+        const PairWalk W{S.Ap.data(), S.Ai.data(), S.Tp.data(), S.Tj.data(), S.Tpos.data(), S.perm.data(), S.iperm.data(), S.col_local.data(),
+                         opt.system, opt.k2_n, opt.rank, dense_m, dense_n, S.dense_cols.data()};
         struct Stream { std::vector<double> w; std::vector<i32> j; std::vector<i32> le, cj, start; std::vector<double> cw; std::vector<i32> pos_in_front; std::vector<i64> epos; };
         std::vector<Stream> st(nthreads);
         uvec<i64> col_off((size_t)m);                     // per pivot column: offset of its products in the stream of ...
@@ -1253,53 +1310,8 @@ int analyse_rank(Symbolic &S, const Options &opt) {
                     T.le.clear(); T.cw.clear(); T.cj.clear();
                     T.start.assign((size_t)ne + 1, 0);
                     auto emit = [&](i64 e, double wv, i32 j) { const i32 le = (i32)(e - e0); T.le.push_back(le); T.cw.push_back(wv); T.cj.push_back(j); ++T.start[(size_t)le + 1]; };
-                    if (opt.system == 1) {
-                        // Augmented system: the diagonal of a variable node is -(theta + regP) = -1 * D2[k]; an
-                        // off-diagonal entry is the constant A[i,j] = A[i,j] * D2[k2_n] with D2[k2_n] = 1 (the columns
-                        // of the incidence matrix carry (1, A[i,j]) on the variable / constraint node).
-                        // Sharded runs: the assembled entries of the replicated root front (linking constraint nodes and the
-                        // variable nodes of columns that touch linking rows only) belong to rank 0; the all-reduce of the root
-                        // panel adds the ranks' extend-add contributions to them.
-                        if (!(is_root && opt.rank != 0)) {
-                            if (k < opt.k2_n) emit(e0, -1.0, k);
-                            for (i64 q = S.Tp[k]; q < S.Tp[k + 1]; ++q) {
-                                const i32 j = S.Tj[q];
-                                const double akj = S.Ax[S.Tpos[q]];
-                                for (i64 p = S.Ap[j]; p < S.Ap[j + 1]; ++p) {
-                                    const i32 ii = S.iperm[S.Ai[p]];
-                                    if (ii <= kk) continue;
-                                    emit(epos[ii], akj * S.Ax[p], (i32)opt.k2_n);
-                                }
-                            }
-                        }
-                    } else if (dense_m >= 0) {
-                        // K1 with dense columns; D = [sparse j: 1 / (theta + regP), dense j: theta + regP ; 1] (kernels.hip: k_dense_diag).
-                        //   constraint node: the products A[i,j] A[k,j] D_j of the SPARSE columns (columns [0, dense_n) of the incidence matrix; a dense
-                        //   column is empty there) and the border entries A[i,j] = A[i,j] * D[dense_n] of the incidence columns (A[i,j] on row i, 1 on node
-                        //   m + t); dense node m + t: -1 * D[dense_cols[t]] on the diagonal (its border entries come from the constraint nodes, ordered before it)
-                        if (k >= dense_m) emit(e0, -1.0, (i32)S.dense_cols[(size_t)(k - dense_m)]);
-                        for (i64 q = S.Tp[k]; q < S.Tp[k + 1]; ++q) {
-                            const i32 j = S.Tj[q];
-                            const double akj = S.Ax[S.Tpos[q]];
-                            const bool incidence = j >= dense_n;
-                            for (i64 p = S.Ap[j]; p < S.Ap[j + 1]; ++p) {
-                                const i32 ii = S.iperm[S.Ai[p]];
-                                if (incidence ? ii <= kk : ii < kk) continue;
-                                emit(epos[ii], akj * S.Ax[p], incidence ? dense_n : j);
-                            }
-                        }
-                    } else {
-                        for (i64 q = S.Tp[k]; q < S.Tp[k + 1]; ++q) {
-                            const i32 j = S.Tj[q];
-                            if (is_root && !col_is_mine(j)) continue;
-                            const double akj = S.Ax[S.Tpos[q]];
-                            for (i64 p = S.Ap[j]; p < S.Ap[j + 1]; ++p) {
-                                const i32 ii = S.iperm[S.Ai[p]];
-                                if (ii < kk) continue;
-                                emit(epos[ii], akj * S.Ax[p], j);
-                            }
-                        }
-                    }
+                    // (the walk is shared with build_value_maps: the same products in the same order, the factors in the same order)
+                    walk_pairs(W, kk, is_root, [&](i32 ii, i64 pa, i64 pb, i32 j) { emit(epos[ii], pa < 0 ? -1.0 : S.Ax[(size_t)pa] * S.Ax[(size_t)pb], j); });
                     // counts -> pair_ptr (prefix-summed below); stable counting sort of the column's products by entry into the thread's stream
                     const size_t np = T.le.size(), base = T.w.size();
                     for (i64 q = 0; q < ne; ++q) { S.pair_ptr[(size_t)(e0 + q) + 1] = T.start[(size_t)q + 1]; T.start[(size_t)q + 1] += T.start[(size_t)q]; }
@@ -2705,6 +2717,115 @@ static void build_schedule(Symbolic &S) {
     for (; cur_g < (solve_one_group ? 0 : S.ngroups); ++cur_g)
         for (i32 d = 1; d < S.nlevels; ++d) bwd_level(d);
     spt.mark(nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// New values on an analysed pattern (tlpk_set_values).  Nothing of the analysis depends on the values; what does is pair_w and the
+// value arrays of A (Ax, the CSR copies Tx / Px).  build_value_maps re-walks the products of this rank's fronts with walk_pairs -- the
+// traversal of step 14 -- and records, for product t of the lists, the positions of its two factors in the CALLER's nzval
+// (VM_ONE: the unit entry of an incidence column of K2 / a dense column; (VM_MINUS, VM_ONE): the constant -1 of a diagonal), and for
+// every entry of the value arrays the position it copies.  Built on the first tlpk_set_values of a handle, not at create.
+// ---------------------------------------------------------------------------------------------
+int build_value_maps(const Symbolic &S, i32 rank, ValueMaps &M) {
+    if (S.dense_matrix) return TLPK_OK;
+    const i32 m = (i32)S.m;
+    const i64 np = S.pair_ptr.empty() ? 0 : S.pair_ptr[(size_t)S.nnzS];
+    // the incidence matrix the lists were built on, with the caller's position of every value: K1 -- A itself; K2 -- the columns
+    // (1 on the variable node, A[i,j] on the constraint node) S still holds; dense columns -- rebuilt as analyse_dense builds it
+    std::vector<i64> bp, tp; std::vector<i32> bi, tj, tpos, src;
+    const i64 *Ap = S.Ap.data(), *Tp = S.Tp.data(); const i32 *Ai = S.Ai.data(), *Tj = S.Tj.data(), *Tpos = S.Tpos.data();
+    i32 dense_m = -1;
+    try {
+        if (S.system == 1) {
+            src.resize(S.Ax.size());
+            for (size_t q = 0; q < src.size(); ++q) src[q] = (q & 1) ? (i32)(q >> 1) : VM_ONE;
+            M.ax_src = src;
+        } else if (S.n_dense > 0) {
+            const i64 n = S.n, k = S.n_dense, mu = S.m - S.n_dense;
+            dense_m = (i32)mu;
+            std::vector<char> isd((size_t)n, 0);
+            for (i64 j : S.dense_cols) isd[(size_t)j] = 1;
+            bp.reserve((size_t)n + 1);
+            for (i64 j = 0; j < n; ++j) {
+                bp.push_back((i64)bi.size());
+                if (isd[(size_t)j]) continue;
+                for (i64 p = S.Ap[(size_t)j]; p < S.Ap[(size_t)j + 1]; ++p) { bi.push_back(S.Ai[(size_t)p]); src.push_back((i32)p); }
+            }
+            for (i64 t = 0; t < k; ++t) {
+                const i64 j = S.dense_cols[(size_t)t];
+                for (i64 p = S.Ap[(size_t)j]; p < S.Ap[(size_t)j + 1]; ++p) {
+                    bp.push_back((i64)bi.size());
+                    bi.push_back(S.Ai[(size_t)p]); src.push_back((i32)p);          // constraint node
+                    bi.push_back((i32)(mu + t)); src.push_back(VM_ONE);           // dense node
+                }
+            }
+            bp.push_back((i64)bi.size());
+            const i64 nb = (i64)bp.size() - 1, nz = (i64)bi.size();
+            tp.assign((size_t)m + 1, 0); tj.resize((size_t)nz); tpos.resize((size_t)nz);
+            for (i64 p = 0; p < nz; ++p) tp[(size_t)bi[(size_t)p] + 1]++;
+            for (i32 i = 0; i < m; ++i) tp[(size_t)i + 1] += tp[(size_t)i];
+            std::vector<i64> cur(tp.begin(), tp.end() - 1);
+            for (i64 j = 0; j < nb; ++j)
+                for (i64 p = bp[(size_t)j]; p < bp[(size_t)j + 1]; ++p) { const i64 q = cur[(size_t)bi[(size_t)p]]++; tj[(size_t)q] = (i32)j; tpos[(size_t)q] = (i32)p; }
+            Ap = bp.data(); Ai = bi.data(); Tp = tp.data(); Tj = tj.data(); Tpos = tpos.data();
+        }
+        M.pair_a.resize((size_t)np); M.pair_b.resize((size_t)np);
+        const PairWalk W{Ap, Ai, Tp, Tj, Tpos, S.perm.data(), S.iperm.data(), S.col_local.data(), S.system, S.k2_n, rank, dense_m, (i32)S.dense_n, S.dense_cols.data()};
+        const i32 *sv = src.empty() ? nullptr : src.data();
+        const unsigned nthreads = host_threads(S.nsuper);
+        struct Scratch { std::vector<i64> cur; };
+        std::vector<Scratch> sc(nthreads);
+        std::atomic<int> bad{0};
+        const bool ok = parallel_for(S.nsuper, nthreads, [&](unsigned tid, i64 s64) {
+            const i32 s = (i32)s64;
+            if (!S.front_local[(size_t)s]) return;
+            const FrontDesc &w = S.fronts[(size_t)s];
+            std::vector<i64> &cur = sc[tid].cur;                      // per permuted row: the next free slot of its entry in the current column
+            if (cur.empty()) cur.assign((size_t)m, -1);
+            const bool is_root = (s == S.root_front);
+            for (i32 kk = w.col0; kk < w.col0 + w.ns; ++kk) {
+                for (i64 e = S.Sp[(size_t)kk]; e < S.Sp[(size_t)kk + 1]; ++e) cur[(size_t)S.Si[(size_t)e]] = S.pair_ptr[(size_t)e];
+                walk_pairs(W, kk, is_root, [&](i32 ii, i64 pa, i64 pb, i32) {
+                    const i64 t = cur[(size_t)ii]++;
+                    if (t < 0 || t >= np) { bad = 1; return; }
+                    if (pa < 0) { M.pair_a[(size_t)t] = VM_MINUS; M.pair_b[(size_t)t] = VM_ONE; }
+                    else { M.pair_a[(size_t)t] = sv ? sv[pa] : (i32)pa; M.pair_b[(size_t)t] = sv ? sv[pb] : (i32)pb; }
+                });
+                for (i64 e = S.Sp[(size_t)kk]; e < S.Sp[(size_t)kk + 1]; ++e)
+                    if (cur[(size_t)S.Si[(size_t)e]] != S.pair_ptr[(size_t)e + 1]) bad = 1;       // the walk must fill every entry's range exactly
+            }
+        }, 64);
+        if (!ok) return TLPK_OOM;
+        if (bad) return TLPK_INTERNAL;
+        // the CSR copies: Tx[q] = value[Tpos[q]]; Px = the same rows in permuted order (K1; tlpk_api.cpp: upload_all)
+        M.tx_src.resize(S.Tpos.size());
+        for (size_t q = 0; q < S.Tpos.size(); ++q) M.tx_src[q] = (S.system == 1) ? M.ax_src[(size_t)S.Tpos[q]] : S.Tpos[q];
+        if (S.system == 0) {
+            const i64 mu = S.m - S.n_dense;
+            M.px_src.reserve(S.Tpos.size());
+            for (i64 ii = 0; ii < S.m; ++ii) {
+                const i32 i = S.perm[(size_t)ii];
+                if (i >= mu) continue;
+                for (i64 q = S.Tp[(size_t)i]; q < S.Tp[(size_t)i + 1]; ++q) M.px_src.push_back(S.Tpos[(size_t)q]);
+            }
+        }
+    } catch (const std::bad_alloc &) { return TLPK_OOM; }
+    M.built = true;
+    return TLPK_OK;
+}
+
+// the host side of a refresh: the value array of the analysed matrix and -- where the host still holds them (analyse-only handles) -- the products
+void host_set_values(Symbolic &S, const ValueMaps &M, const double *nz) {
+    if (S.system == 1) { for (size_t q = 1; q < S.Ax.size(); q += 2) S.Ax[q] = nz[q >> 1]; }
+    else std::memcpy(S.Ax.data(), nz, S.Ax.size() * sizeof(double));
+    if (S.pair_w.empty()) return;
+    const i64 np = (i64)S.pair_w.size();
+    constexpr i64 CH = (i64)1 << 16;
+    const i64 nch = (np + CH - 1) / CH;
+    auto val = [&](i32 p) { return p >= 0 ? nz[p] : (p == VM_ONE ? 1.0 : -1.0); };
+    (void)parallel_for(nch, host_threads(nch), [&](unsigned, i64 ch) {
+        for (i64 t = ch * CH, t1 = std::min(np, t + CH); t < t1; ++t) S.pair_w[(size_t)t] = val(M.pair_a[(size_t)t]) * val(M.pair_b[(size_t)t]);
+    });
 }
 
 }  // namespace tlpk

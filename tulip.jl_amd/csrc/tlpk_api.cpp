@@ -832,6 +832,8 @@ void tlpk_destroy(tlpk_handle *h) {
         for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
         if (h->ev0) hipEventDestroy(h->ev0);
         if (h->ev1) hipEventDestroy(h->ev1);
+        if (h->sv_ev0) hipEventDestroy(h->sv_ev0);
+        if (h->sv_ev1) hipEventDestroy(h->sv_ev1);
         if (h->ev_fork) hipEventDestroy(h->ev_fork);
         if (h->zstream) { hipStreamSynchronize(h->zstream); hipStreamDestroy(h->zstream); }
         if (h->ev_zfork) hipEventDestroy(h->ev_zfork);
@@ -2119,6 +2121,167 @@ int tlpk_create_multi(tlpk_handle **out, int64_t m, int64_t n, const int64_t *co
     return TLPK_OK;
 }
 
+// ---- new values on the analysed pattern (tlpk_set_values*; DESIGN.md section 1b''') ----
+namespace {
+
+i64 caller_nnz(const tlpk_handle *h) { const tlpk_handle *c = h->sub.empty() ? h : h->sub[0]; return (c->S.system == 1) ? c->S.n : c->S.nnzA; }
+
+// first call on a handle: the maps (one host walk of the lists) and their device copies
+int ensure_value_maps(tlpk_handle *h) {
+    if (h->vmaps.built || h->S.dense_matrix) return TLPK_OK;
+    const int rc = build_value_maps(h->S, h->opt.rank, h->vmaps);
+    if (rc != TLPK_OK) { h->vmaps = ValueMaps{}; h->last_error = "tlpk_set_values: building the value maps failed"; return rc; }
+    if (!h->has_device) return TLPK_OK;
+    const i64 before = h->device_bytes;
+    int q;
+    if ((q = dev_upload(h, &h->d_pair_a, h->vmaps.pair_a)) != TLPK_OK) return q;
+    if ((q = dev_upload(h, &h->d_pair_b, h->vmaps.pair_b)) != TLPK_OK) return q;
+    if ((q = dev_upload(h, &h->d_tx_src, h->vmaps.tx_src)) != TLPK_OK) return q;
+    if (h->d.Px && (q = dev_upload(h, &h->d_px_src, h->vmaps.px_src)) != TLPK_OK) return q;
+    h->n_px_src = h->d.Px ? (i64)h->vmaps.px_src.size() : 0;
+    if (h->S.system == 1) {
+        if ((q = dev_upload(h, &h->d_ax_src, h->vmaps.ax_src)) != TLPK_OK) return q;
+        if ((q = dev_alloc(h, &h->d_nz, h->S.n)) != TLPK_OK) return q;
+    } else h->d_nz = h->d.Ax;
+    h->set_values_bytes = h->device_bytes - before;
+    uvec<i32>().swap(h->vmaps.pair_a); uvec<i32>().swap(h->vmaps.pair_b);         // (the device applies them from now on)
+    std::vector<i32>().swap(h->vmaps.tx_src); std::vector<i32>().swap(h->vmaps.px_src);
+    if (!h->sv_ev0) HIPCHK(h, hipEventCreate(&h->sv_ev0));
+    if (!h->sv_ev1) HIPCHK(h, hipEventCreate(&h->sv_ev1));
+    return TLPK_OK;
+}
+
+// the state an update leaves behind when it starts: analysed, not factored, nothing pending
+void values_reset_state(tlpk_handle *h) {
+    if (h->root_pending) (void)update_async_wait(h);
+    h->factored = false; h->local_done = false; h->pending = tlpk_handle::Pending::None; h->fail_col = -1; h->solve_timed = false;
+    h->values_set = true;
+}
+
+void sv_time_take(tlpk_handle *h) {
+    if (!h->sv_pending) return;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->sv_ev0, h->sv_ev1) == hipSuccess) { h->ms_set_values = ms; h->sv_pending = false; }
+    else (void)hipGetLastError();
+}
+
+void host_ax_take(tlpk_handle *h, const double *src, i64 nnz) {
+    if (h->S.system == 1) { for (size_t q = 1; q < h->S.Ax.size(); q += 2) h->S.Ax[q] = src[q >> 1]; }
+    else if (nnz > 0) std::memcpy(h->S.Ax.data(), src, (size_t)nnz * 8);
+    h->host_ax_stale = false;
+}
+
+// one handle (single-device, a rank of a sharded job, a shard of a multi-device handle), enqueued on its stream; src: host or device pointer
+int set_values_enqueue(tlpk_handle *h, const double *src, bool from_device) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = ensure_value_maps(h)) return rc;
+    values_reset_state(h);
+    const Symbolic &S = h->S;
+    const i64 nnz = caller_nnz(h);
+    hipStream_t st = h->stream;
+    HIPCHK(h, hipEventRecord(h->sv_ev0, st));
+    if (src != h->d_nz && nnz > 0) HIPCHK(h, hipMemcpyAsync(h->d_nz, src, (size_t)nnz * 8, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    if (S.system == 1) launch_refresh_gather(st, (i64)S.Ax.size(), h->d_ax_src, h->d_nz, h->d.Ax);
+    launch_refresh_gather(st, (i64)S.Tpos.size(), h->d_tx_src, h->d_nz, h->d.Tx);
+    if (h->d.Px) launch_refresh_gather(st, h->n_px_src, h->d_px_src, h->d_nz, h->d.Px);
+    launch_refresh_pairs(st, S.pair_ptr.empty() ? 0 : S.pair_ptr.back(), h->d_pair_a, h->d_pair_b, h->d_nz, h->d.pair_w);
+    HIPCHK(h, hipEventRecord(h->sv_ev1, st));
+    HIPCHK(h, hipGetLastError());
+    h->sv_pending = true;
+    h->host_ax_stale = true;
+    return TLPK_OK;
+}
+int set_values_wait(tlpk_handle *h, const double *src) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    sv_time_take(h);
+    host_ax_take(h, src, caller_nnz(h));
+    return TLPK_OK;
+}
+
+int set_values_host_only(tlpk_handle *h, const double *src) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = ensure_value_maps(h)) return rc;
+    host_set_values(h->S, h->vmaps, src);
+    h->ms_set_values = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->values_set = true; h->factored = false;
+    return TLPK_OK;
+}
+
+int set_values_dense_one(tlpk_handle *h, const double *A, i64 lda, bool from_device) {
+    const i64 m = h->S.m, n = h->S.n;
+    if (!h->has_device) { h->values_set = true; h->factored = false; h->ms_set_values = 0; return TLPK_OK; }      // nothing of a dense A stays on the host
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->sv_ev0) HIPCHK(h, hipEventCreate(&h->sv_ev0));
+    if (!h->sv_ev1) HIPCHK(h, hipEventCreate(&h->sv_ev1));
+    values_reset_state(h);
+    double *dA = const_cast<double *>(h->d.dA);
+    HIPCHK(h, hipEventRecord(h->sv_ev0, h->stream));
+    if (from_device) launch_refresh_dense(h->stream, m, n, A, lda, dA, h->d.dlda);
+    else if (n > 0) HIPCHK(h, hipMemcpy2DAsync(dA, (size_t)h->d.dlda * 8, A, (size_t)lda * 8, (size_t)m * 8, (size_t)n, hipMemcpyHostToDevice, h->stream));   // (the padding rows keep their zeros)
+    HIPCHK(h, hipEventRecord(h->sv_ev1, h->stream));
+    HIPCHK(h, hipGetLastError());
+    h->sv_pending = true;
+    if (!from_device) { HIPCHK(h, hipStreamSynchronize(h->stream)); sv_time_take(h); }
+    return TLPK_OK;
+}
+
+int set_values_common(tlpk_handle *h, const double *nzval, int64_t len, bool from_device, const char *what) {
+    if (!h) return TLPK_BADARG;
+    const tlpk_handle *k = h->sub.empty() ? h : h->sub[0];
+    if (k->S.dense_matrix) { h->last_error = std::string(what) + ": a dense-matrix handle takes tlpk_set_values_dense"; return TLPK_BADARG; }
+    if (!nzval) { h->last_error = std::string(what) + ": nzval is NULL"; return TLPK_BADARG; }
+    if (len != caller_nnz(h)) { h->last_error = std::string(what) + ": len = " + std::to_string(len) + ", the analysed matrix has " + std::to_string(caller_nnz(h)) + " entries"; return TLPK_BADARG; }
+    if (from_device) {
+        if (!h->sub.empty()) { h->last_error = std::string(what) + ": single-device handles only (a multi-device handle takes the host pointer)"; return TLPK_BADARG; }
+        if (!h->has_device) return TLPK_NO_DEVICE;
+    }
+    int rc = TLPK_OK;
+    try {
+        if (!h->sub.empty()) {
+            // one call serves every shard: every refresh is enqueued before anybody waits
+            for (tlpk_handle *c : h->sub) { rc = set_values_enqueue(c, nzval, false); if (rc != TLPK_OK) { h->last_error = c->last_error; break; } }
+            for (tlpk_handle *c : h->sub) { const int q = set_values_wait(c, nzval); if (q != TLPK_OK && rc == TLPK_OK) { rc = q; h->last_error = c->last_error; } }
+            h->factored = false; h->fail_col = -1; h->values_set = true;
+            h->ms_set_values = 0; h->set_values_bytes = 0;
+            for (tlpk_handle *c : h->sub) { h->ms_set_values = std::max(h->ms_set_values, c->ms_set_values); h->set_values_bytes += c->set_values_bytes; }
+        } else if (!h->has_device) rc = set_values_host_only(h, nzval);
+        else {
+            rc = set_values_enqueue(h, nzval, from_device);
+            if (rc == TLPK_OK && !from_device) rc = set_values_wait(h, nzval);
+        }
+    } catch (const std::bad_alloc &) { rc = TLPK_OOM; h->last_error = std::string(what) + ": host out of memory"; }
+    if (rc == TLPK_OK && h->ipm) h->ipm_stale = true;
+    return rc;
+}
+
+}  // namespace
+
+extern "C++" int sync_host_values(tlpk_handle *h) {
+    if (!h->host_ax_stale || !h->has_device || !h->sub.empty()) return TLPK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!h->S.Ax.empty()) HIPCHK(h, hipMemcpy(h->S.Ax.data(), h->d.Ax, h->S.Ax.size() * 8, hipMemcpyDeviceToHost));
+    h->host_ax_stale = false;
+    return TLPK_OK;
+}
+
+int tlpk_set_values(tlpk_handle *h, const double *nzval, int64_t len) { return set_values_common(h, nzval, len, false, "tlpk_set_values"); }
+int tlpk_set_values_device(tlpk_handle *h, const double *d_nzval, int64_t len) { return set_values_common(h, d_nzval, len, true, "tlpk_set_values_device"); }
+
+static int set_values_dense_common(tlpk_handle *h, const double *A, int64_t lda, bool from_device, const char *what) {
+    if (!h) return TLPK_BADARG;
+    if (!h->sub.empty() || !h->S.dense_matrix) { h->last_error = std::string(what) + ": not a dense-matrix handle (tlpk_create_dense); sparse handles take tlpk_set_values"; return TLPK_BADARG; }
+    if (!A && h->S.n > 0) { h->last_error = std::string(what) + ": A is NULL"; return TLPK_BADARG; }
+    if (lda < h->S.m) { h->last_error = std::string(what) + ": lda < m"; return TLPK_BADARG; }
+    if (from_device && !h->has_device) return TLPK_NO_DEVICE;
+    const int rc = set_values_dense_one(h, A, lda, from_device);
+    if (rc == TLPK_OK && h->ipm) h->ipm_stale = true;
+    return rc;
+}
+int tlpk_set_values_dense(tlpk_handle *h, const double *A, int64_t lda) { return set_values_dense_common(h, A, lda, false, "tlpk_set_values_dense"); }
+int tlpk_set_values_dense_device(tlpk_handle *h, const double *d_A, int64_t lda) { return set_values_dense_common(h, d_A, lda, true, "tlpk_set_values_dense_device"); }
+
 // ---- introspection ----
 int tlpk_info(const tlpk_handle *h, tlpk_stats *out) {
     if (!h || !out) return TLPK_BADARG;
@@ -2130,6 +2293,7 @@ int tlpk_info(const tlpk_handle *h, tlpk_stats *out) {
         out->device_bytes = bytes; out->n_local_blocks = nloc;
         out->ms_analyse = h->ms_analyse; out->ms_last_update = h->ms_update; out->ms_enqueue_update = h->ms_enqueue_update;
         out->refine_rejected = h->refine_rejected;
+        out->ms_last_set_values = h->ms_set_values; out->set_values_bytes = h->set_values_bytes;
         return rc;
     }
     const Symbolic &S = h->S;
@@ -2154,6 +2318,8 @@ int tlpk_info(const tlpk_handle *h, tlpk_stats *out) {
     out->root_panel_len = (S.root_front >= 0) ? pk_len(S.fronts[S.root_front].lda, S.fronts[S.root_front].ns) : 0;
     out->n_dense_cols = S.n_dense;
     out->flops_syrk = S.flops_syrk;
+    if (h->sv_pending && h->has_device && hipSetDevice(h->device) == hipSuccess) sv_time_take(const_cast<tlpk_handle *>(h));      // an enqueued refresh: its time once the events have completed
+    out->ms_last_set_values = h->ms_set_values; out->set_values_bytes = h->set_values_bytes;
     return TLPK_OK;
 }
 
@@ -2274,7 +2440,16 @@ int64_t tlpk_symbolic_get_f64(const tlpk_handle *h, const char *what, double *bu
     const std::string w(what);
     if (w != "pair_w") return -1;
     const auto &v = h->S.pair_w;
-    const i64 len = (i64)v.size();
+    i64 len = (i64)v.size();
+    if (len == 0 && h->values_set && h->sub.empty() && h->has_device && h->d.pair_w && !h->S.pair_ptr.empty()) {
+        // a device handle keeps the products on the device only; after tlpk_set_values* they are copied back on request
+        len = h->S.pair_ptr.back();
+        if (buf && cap > 0) {
+            if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+                hipMemcpy(buf, h->d.pair_w, (size_t)std::min(len, cap) * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        }
+        return len;
+    }
     if (buf) std::copy(v.begin(), v.begin() + std::min(len, cap), buf);
     return len;
 }

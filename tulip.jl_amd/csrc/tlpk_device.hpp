@@ -125,4 +125,9 @@ void launch_dense_gemv_n(hipStream_t st, const DevArrays &a, const double *D, co
 // out[r] = D .* (A' y[r] - xi_d[r])  (D null: A' y[r]), r < nrhs <= 2: one pass over A
 void launch_dense_gemv_t(hipStream_t st, const DevArrays &a, const double *D, const double *const *y, const double *const *xi_d, double *const *out, int nrhs);
 
+// new values on an analysed pattern (refresh_kernels.hip): w[t] = value(a[t]) * value(b[t]); out[q] = value(src[q]); the strided copy of a dense A
+void launch_refresh_pairs(hipStream_t st, i64 np, const i32 *a, const i32 *b, const double *nz, double *w);
+void launch_refresh_gather(hipStream_t st, i64 n, const i32 *src, const double *nz, double *out);
+void launch_refresh_dense(hipStream_t st, i64 m, i64 n, const double *A, i64 lda, double *dA, i64 dlda);
+
 }  // namespace tlpk

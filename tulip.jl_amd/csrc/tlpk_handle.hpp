@@ -87,10 +87,22 @@ struct tlpk_handle {
     std::vector<hipGraphExec_t> graph_execs;
     std::vector<std::vector<char>> graph_keys;
     IpmState *ipm = nullptr;            // device-resident interior-point vectors (tlpk_ipm_load), freed by tlpk_destroy
+    // tlpk_set_values: the maps from the caller's nzval to the value-dependent arrays (symbolic.cpp: build_value_maps), built and uploaded by the FIRST call
+    ValueMaps vmaps;                    // host copy (analyse-only handles keep it; device handles drop the product maps once they are uploaded)
+    i32 *d_pair_a = nullptr, *d_pair_b = nullptr, *d_ax_src = nullptr, *d_tx_src = nullptr, *d_px_src = nullptr;
+    i64 n_px_src = 0;                   // entries of Px
+    double *d_nz = nullptr;             // the caller's nzval on the device: d.Ax itself, or (K2: Ax holds the incidence matrix) a staging array
+    bool values_set = false;            // tlpk_set_values* has run on this handle
+    bool host_ax_stale = false;         // the last values came through a device pointer: S.Ax is copied back when a host consumer asks (sync_host_values)
+    bool ipm_stale = false;             // new values since tlpk_ipm_load / tlpk_ipm_reload: the loops are refused until tlpk_ipm_reload
+    i64 set_values_bytes = 0;           // device memory of the maps (tlpk_stats.set_values_bytes)
+    double ms_set_values = 0;           // tlpk_stats.ms_last_set_values
+    hipEvent_t sv_ev0 = nullptr, sv_ev1 = nullptr; bool sv_pending = false;   // ... of an enqueued refresh: read when the events have completed
     std::string last_error;
 };
 
 void ipm_free(tlpk_handle *h);          // tlpk_ipm.cpp
+int sync_host_values(tlpk_handle *h);   // tlpk_api.cpp: S.Ax <- the device copy after a tlpk_set_values*_device
 // tlpk_api.cpp, for the device-resident interior-point loops on a multi-device handle: KKT.update! from the theta / regP / regD every
 // shard holds on its device, and KKT.solve! with shard-resident vectors in the rank-local layout (every shard adds ITS xi_p on the
 // linking rows -- partial residuals --, the library's reduction completes them; nothing is gathered)

@@ -268,6 +268,18 @@ int analyse_dense(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowva
 // matrix without zeros, without forming the m (m + 1) / 2 entries of the pattern or the n m (m + 1) / 2 products of the assembly lists.  The
 // factorisation and solve schedules are those of build_schedule for that front; host memory O(m + schedule).  Needs only the shape of A.
 int analyse_dense_matrix(Symbolic &S, i64 m, i64 n);
+// New values on an analysed pattern (tlpk_set_values; symbolic.cpp: build_value_maps).  pair_a / pair_b: for product t of this rank's assembly lists the
+// positions in the caller's nzval of its two factors, pair_w[t] = value(pair_a[t]) * value(pair_b[t]) in this order; VM_ONE stands for the unit entry of an
+// incidence column (K2, dense columns), (VM_MINUS, VM_ONE) for the constant -1 of a variable / dense node's diagonal.  ax_src (K2 only: elsewhere Ax IS the
+// caller's nzval), tx_src, px_src: the position every entry of Ax / Tx / Px copies (VM_ONE: stays 1).
+constexpr i32 VM_ONE = -1, VM_MINUS = -2;
+struct ValueMaps {
+    bool built = false;
+    uvec<i32> pair_a, pair_b;
+    std::vector<i32> ax_src, tx_src, px_src;
+};
+int build_value_maps(const Symbolic &S, i32 rank, ValueMaps &M);
+void host_set_values(Symbolic &S, const ValueMaps &M, const double *nz);
 // launch geometry of the dense kernels (shared by analyse_dense_matrix and dense_kernels.hip)
 constexpr int DGEMV_ROWS = 512;    // rows per k_dense_gemv_n workgroup (256 threads x 2 rows)
 inline i64 dense_lda(i64 m) { return (m + 15) / 16 * 16; }     // leading dimension of the device copy of A: columns start on 128-byte lines, padding rows are zero

@@ -47,7 +47,7 @@ namespace {
 
 struct Shards { tlpk_handle *c[MAX_DEVICES]; int n = 0; bool multi = false; };
 
-int ipm_shards(tlpk_handle *h, Shards &sh, bool need_loaded = true) {
+int ipm_shards(tlpk_handle *h, Shards &sh, bool need_loaded = true, bool allow_stale = false) {
     if (!h) return TLPK_BADARG;
     if (!h->has_device) return TLPK_NO_DEVICE;
     if (h->opt.nranks > 1) { h->last_error = "the device-resident IPM vectors need a single-rank or a tlpk_create_multi handle (a sharded handle's reductions belong to its caller)"; return TLPK_BADARG; }
@@ -56,6 +56,10 @@ int ipm_shards(tlpk_handle *h, Shards &sh, bool need_loaded = true) {
         for (int r = 0; r < sh.n; ++r) sh.c[r] = h->sub[(size_t)r];
     } else { sh.multi = false; sh.n = 1; sh.c[0] = h; }
     if (need_loaded && !h->ipm) { h->last_error = "tlpk_ipm_load has not been called"; return TLPK_BADARG; }
+    if (need_loaded && h->ipm_stale && !allow_stale) {
+        h->last_error = "the matrix values changed (tlpk_set_values) after the LP was loaded: call tlpk_ipm_reload before the device-resident loops";
+        return TLPK_BADARG;
+    }
     return TLPK_OK;
 }
 int fail_from(tlpk_handle *h, tlpk_handle *c, int rc) { if (c != h) h->last_error = c->last_error; return rc; }
@@ -185,6 +189,47 @@ int tlpk_ipm_load(tlpk_handle *h, const double *b, const double *c, const double
     return rc;
 }
 
+// The copy of A the loops of handle h read where they cannot share the handle's own (a shard's sub-LP; K2, whose handle holds the incidence matrix of the
+// augmented system): host copy of A, column-major: K1 -- the analyse phase's copy; K2 -- rebuilt from the incidence matrix
+// (column p = entry p of A: 1 on variable node j, A[i,j] on constraint node n + i, in A's column-major entry order).
+// A shard keeps the columns it owns (the others are empty).  Then the row-major copy.  tlpk_ipm_load uploads all six arrays, tlpk_ipm_reload the two value arrays.
+static int ipm_sub_matrix(tlpk_handle *h, bool shard, std::vector<i64> &ap, std::vector<i32> &ai, std::vector<double> &ax,
+                          std::vector<i64> &tp, std::vector<i32> &tj, std::vector<double> &tx) {
+    if (int rc = sync_host_values(h)) return rc;
+    const Symbolic &S = h->S;
+    const bool k2 = S.system == 1;
+    const i64 m = k2 ? S.k2_m : S.m - S.n_dense, n = k2 ? S.k2_n : S.n;
+    auto own_col = [&](i64 j) { if (!shard) return true; if (!k2) return S.col_local[(size_t)j] != 0; const char nl = S.row_local[(size_t)j]; return nl == 1 || (nl == 2 && h->opt.rank == 0); };
+    ap.assign((size_t)n + 1, 0); tp.assign((size_t)m + 1, 0);
+    ai.clear(); tj.clear(); ax.clear(); tx.clear();
+    if (!k2) {
+        for (i64 j = 0; j < n; ++j) {
+            if (own_col(j)) for (i64 q = S.Ap[(size_t)j]; q < S.Ap[(size_t)j + 1]; ++q) { ai.push_back(S.Ai[(size_t)q]); ax.push_back(S.Ax[(size_t)q]); }
+            ap[(size_t)j + 1] = (i64)ai.size();
+        }
+    } else {
+        const i64 nnz = S.n;
+        i64 jprev = 0;
+        for (i64 p = 0; p < nnz; ++p) {
+            if (S.Ap[(size_t)p + 1] - S.Ap[(size_t)p] != 2) { h->last_error = "K2 incidence matrix: unexpected column"; return TLPK_INTERNAL; }
+            const i64 q = S.Ap[(size_t)p];
+            const i32 a = S.Ai[(size_t)q], b2 = S.Ai[(size_t)q + 1];
+            const bool afirst = a < (i32)n;                   // the variable node is the smaller index
+            const i64 j = afirst ? a : b2; const i32 i = (afirst ? b2 : a) - (i32)n;
+            if (j < jprev) { h->last_error = "K2 incidence matrix: columns out of order"; return TLPK_INTERNAL; }
+            for (; jprev < j; ++jprev) ap[(size_t)jprev + 1] = (i64)ai.size();
+            if (own_col(j)) { ai.push_back(i); ax.push_back(S.Ax[(size_t)q + (afirst ? 1 : 0)]); }
+        }
+        for (; jprev < n; ++jprev) ap[(size_t)jprev + 1] = (i64)ai.size();
+    }
+    for (size_t q = 0; q < ai.size(); ++q) ++tp[(size_t)ai[q] + 1];
+    for (i64 i = 0; i < m; ++i) tp[(size_t)i + 1] += tp[(size_t)i];
+    tj.resize(ai.size()); tx.resize(ai.size());
+    { std::vector<i64> cur(tp.begin(), tp.end() - 1);
+      for (i64 j = 0; j < n; ++j) for (i64 q = ap[(size_t)j]; q < ap[(size_t)j + 1]; ++q) { const i64 c2 = cur[(size_t)ai[(size_t)q]]++; tj[(size_t)c2] = (i32)j; tx[(size_t)c2] = ax[(size_t)q]; } }
+    return TLPK_OK;
+}
+
 static int ipm_load_impl(tlpk_handle *h, const double *b, const double *c, const double *l, const double *u, bool shard) {
     HIPCHK(h, hipSetDevice(h->device));
     const bool k2 = h->S.system == 1;
@@ -213,33 +258,8 @@ static int ipm_load_impl(tlpk_handle *h, const double *b, const double *c, const
         // host copy of A, column-major: K1 -- the analyse phase's copy; K2 -- rebuilt from the incidence matrix of the augmented system
         // it holds (column p = entry p of A: 1 on variable node j, A[i,j] on constraint node n + i, in A's column-major entry order).
         // A shard keeps the columns it owns (the others are empty).  Then the row-major copy.
-        std::vector<i64> ap((size_t)n + 1, 0), tp((size_t)m + 1, 0);
-        std::vector<i32> ai, tj; std::vector<double> ax, tx;
-        if (!k2) {
-            for (i64 j = 0; j < n; ++j) {
-                if (own_col(j)) for (i64 q = S.Ap[(size_t)j]; q < S.Ap[(size_t)j + 1]; ++q) { ai.push_back(S.Ai[(size_t)q]); ax.push_back(S.Ax[(size_t)q]); }
-                ap[(size_t)j + 1] = (i64)ai.size();
-            }
-        } else {
-            const i64 nnz = S.n;
-            i64 jprev = 0;
-            for (i64 p = 0; p < nnz; ++p) {
-                if (S.Ap[(size_t)p + 1] - S.Ap[(size_t)p] != 2) { h->last_error = "K2 incidence matrix: unexpected column"; return TLPK_INTERNAL; }
-                const i64 q = S.Ap[(size_t)p];
-                const i32 a = S.Ai[(size_t)q], b2 = S.Ai[(size_t)q + 1];
-                const bool afirst = a < (i32)n;                   // the variable node is the smaller index
-                const i64 j = afirst ? a : b2; const i32 i = (afirst ? b2 : a) - (i32)n;
-                if (j < jprev) { h->last_error = "K2 incidence matrix: columns out of order"; return TLPK_INTERNAL; }
-                for (; jprev < j; ++jprev) ap[(size_t)jprev + 1] = (i64)ai.size();
-                if (own_col(j)) { ai.push_back(i); ax.push_back(S.Ax[(size_t)q + (afirst ? 1 : 0)]); }
-            }
-            for (; jprev < n; ++jprev) ap[(size_t)jprev + 1] = (i64)ai.size();
-        }
-        for (size_t q = 0; q < ai.size(); ++q) ++tp[(size_t)ai[q] + 1];
-        for (i64 i = 0; i < m; ++i) tp[(size_t)i + 1] += tp[(size_t)i];
-        tj.resize(ai.size()); tx.resize(ai.size());
-        { std::vector<i64> cur(tp.begin(), tp.end() - 1);
-          for (i64 j = 0; j < n; ++j) for (i64 q = ap[(size_t)j]; q < ap[(size_t)j + 1]; ++q) { const i64 c2 = cur[(size_t)ai[(size_t)q]]++; tj[(size_t)c2] = (i32)j; tx[(size_t)c2] = ax[(size_t)q]; } }
+        std::vector<i64> ap, tp; std::vector<i32> ai, tj; std::vector<double> ax, tx;
+        if ((rc = ipm_sub_matrix(h, shard, ap, ai, ax, tp, tj, tx)) != TLPK_OK) return rc;
         i64 *dp; i32 *di; double *dxv;
         if ((rc = dev_upload(h, &dp, ap)) != TLPK_OK) return rc; v.Ap = dp;
         if ((rc = dev_upload(h, &di, ai)) != TLPK_OK) return rc; v.Ai = di;
@@ -285,6 +305,82 @@ static int ipm_load_impl(tlpk_handle *h, const double *b, const double *c, const
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     return TLPK_OK;
+}
+
+// tlpk_ipm_reload on one handle (shard = a shard of a multi-device handle: its sub-LP).  Everything is written into the vectors tlpk_ipm_load allocated.
+static int ipm_reload_impl(tlpk_handle *h, const double *b, const double *c, const double *l, const double *u, bool shard) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));              // nothing of the previous run reads the vectors any more
+    IpmState &s = *h->ipm;
+    IpmVecs &v = s.v;
+    const Symbolic &S = h->S;
+    const bool k2 = S.system == 1;
+    const i64 m = v.m, n = v.n;
+    auto own_col = [&](i64 j) { if (!shard) return true; if (!k2) return S.col_local[(size_t)j] != 0; const char nl = S.row_local[(size_t)j]; return nl == 1 || (nl == 2 && h->opt.rank == 0); };
+    auto row_kind = [&](i64 i) -> char { return k2 ? S.row_local[(size_t)(n + i)] : S.row_local[(size_t)i]; };
+    if (!S.dense_matrix && (shard || k2)) {
+        // the loops' own copy of A: same pattern, new values, in place
+        std::vector<i64> ap, tp; std::vector<i32> ai, tj; std::vector<double> ax, tx;
+        if (int rc = ipm_sub_matrix(h, shard, ap, ai, ax, tp, tj, tx)) return rc;
+        if (!ax.empty()) {
+            HIPCHK(h, hipMemcpy(const_cast<double *>(v.Ax), ax.data(), ax.size() * 8, hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(const_cast<double *>(v.Tx), tx.data(), tx.size() * 8, hipMemcpyHostToDevice));
+        }
+    }
+    std::vector<double> w0, w1;
+    auto put = [&](const double *dst, const std::vector<double> &src) -> int {
+        if (!src.empty()) HIPCHK(h, hipMemcpy(const_cast<double *>(dst), src.data(), src.size() * 8, hipMemcpyHostToDevice));
+        return TLPK_OK;
+    };
+    if (b) {
+        w0.assign((size_t)m, 0.0);
+        for (i64 i = 0; i < m; ++i) { const char rl = shard ? row_kind(i) : 1; if (rl == 1 || (rl == 2 && h->opt.rank == 0)) w0[(size_t)i] = b[i]; }
+        if (int rc = put(v.b, w0)) return rc;
+    }
+    if (c) {
+        w0.assign((size_t)n, 0.0);
+        for (i64 j = 0; j < n; ++j) if (own_col(j)) w0[(size_t)j] = c[j];
+        if (int rc = put(v.c, w0)) return rc;
+    }
+    for (int side = 0; side < 2; ++side) {
+        const double *bd = side ? u : l;
+        if (!bd) continue;
+        w0.assign((size_t)n, 0.0); w1.assign((size_t)n, 0.0);          // flag, bound .* flag (ipmdata.jl:46-47)
+        for (i64 j = 0; j < n; ++j) if (own_col(j) && std::isfinite(bd[j])) { w0[(size_t)j] = 1.0; w1[(size_t)j] = bd[j]; }
+        if (int rc = put(side ? v.uflag : v.lflag, w0)) return rc;
+        if (int rc = put(side ? v.uz : v.lz, w1)) return rc;
+    }
+    // the state of a fresh load: every work vector zero, then the starting point (HSD.jl:238-247)
+    double *nv[] = {v.x, v.xl, v.xu, v.zl, v.zu, v.rl, v.ru, v.rd, v.thl, v.thu, v.hx, v.hxid, v.xil, v.xiu, v.xzl, v.xzu, v.xid,
+                    s.D[0].x, s.D[0].xl, s.D[0].xu, s.D[0].zl, s.D[0].zu, s.D[1].x, s.D[1].xl, s.D[1].xu, s.D[1].zl, s.D[1].zu};
+    double *mv[] = {v.y, v.rp, v.hy, v.xip, s.D[0].y, s.D[1].y};
+    for (double *p : nv) HIPCHK(h, hipMemsetAsync(p, 0, (size_t)std::max<i64>(n, 1) * 8, h->stream));
+    for (double *p : mv) HIPCHK(h, hipMemsetAsync(p, 0, (size_t)std::max<i64>(m, 1) * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(s.partials[0], 0, (size_t)IPM_BLOCKS * IPM_SLOTS * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(s.partials[1], 0, (size_t)IPM_BLOCKS * IPM_SLOTS * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(s.d_out, 0, 2 * IPM_SLOTS * 8, h->stream));
+    s.cur = 0;
+    ipm_launch_init(h->stream, v);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    return TLPK_OK;
+}
+
+int tlpk_ipm_reload(tlpk_handle *h, const double *b, const double *c, const double *l, const double *u) {
+    Shards sh;
+    if (int rc = ipm_shards(h, sh, false)) return rc;
+    if (!h->ipm) { h->last_error = "tlpk_ipm_reload: no LP is loaded on this handle (call tlpk_ipm_load first)"; return TLPK_BADARG; }
+    int rc = TLPK_OK;
+    if (!sh.multi) rc = ipm_reload_impl(h, b, c, l, u, false);
+    else {
+        for (int r = 0; r < sh.n && rc == TLPK_OK; ++r) {
+            rc = ipm_reload_impl(sh.c[r], b, c, l, u, true);
+            if (rc != TLPK_OK) h->last_error = sh.c[r]->last_error;
+        }
+        if (rc == TLPK_OK && b) { IpmState &ps = *h->ipm; for (size_t k = 0; k < ps.link_rows.size(); ++k) ps.b_link[k] = b[ps.link_rows[k]]; }
+    }
+    if (rc == TLPK_OK) h->ipm_stale = false;
+    return rc;
 }
 
 int tlpk_ipm_reset(tlpk_handle *h) {
@@ -542,7 +638,7 @@ int tlpk_ipm_advance(tlpk_handle *h, double alpha, double *out) { return advance
 /* download one vector of the iterate: what = 0 x, 1 xl, 2 xu, 3 zl, 4 zu (length n), 5 y (length m) */
 int tlpk_ipm_get(tlpk_handle *h, int what, double *host, int64_t len) {
     Shards sh;
-    if (int rc = ipm_shards(h, sh)) return rc;
+    if (int rc = ipm_shards(h, sh, true, true)) return rc;
     if (!host || what < 0 || what > 5) return TLPK_BADARG;
     const IpmVecs &v0 = sh.c[0]->ipm->v;
     const int64_t need = (what == 5) ? v0.m : v0.n;

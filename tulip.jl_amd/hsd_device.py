@@ -64,12 +64,9 @@ class DeviceHSD:
             raise DimensionMismatch("b, c, l, u do not match A")
         self.c0, self.objsense = float(c0), bool(objsense_min)
         self.L = _lib.lib()
+        self._l, self._u = l, u
         self._call(self.L.tlpk_ipm_load(self.kkt._h, _lib.as_pd(self._b), _lib.as_pd(self._c), _lib.as_pd(l), _lib.as_pd(u)))
-        lf, uf = np.isfinite(l), np.isfinite(u)
-        self.p = int(lf.sum() + uf.sum())                                    # HSD.jl:39
-        nrm = lambda v: float(np.abs(v).max(initial=0.0))                    # noqa: E731
-        self.nb, self.nc = nrm(self._b), nrm(self._c)
-        self.nlz, self.nuz = nrm(np.where(lf, l, 0.0)), nrm(np.where(uf, u, 0.0))
+        self._host_norms()
         self.regP = self.regD = self.regG = 1.0                              # HSD.jl:50-52 (uniform vectors)
         self.tau = self.kappa = 1.0
         self.mu = 1.0
@@ -79,6 +76,42 @@ class DeviceHSD:
         self.timers = {"n_update": 0, "n_solve": 0, "n_bump": 0}
         self._out = np.zeros(16)
         self._sc = np.zeros(8)
+
+    def _host_norms(self):
+        l, u = self._l, self._u
+        lf, uf = np.isfinite(l), np.isfinite(u)
+        self.p = int(lf.sum() + uf.sum())                                    # HSD.jl:39
+        nrm = lambda v: float(np.abs(v).max(initial=0.0))                    # noqa: E731
+        self.nb, self.nc = nrm(self._b), nrm(self._c)
+        self.nlz, self.nuz = nrm(np.where(lf, l, 0.0)), nrm(np.where(uf, u, 0.0))
+
+    def reload(self, A=None, b=None, c=None, l=None, u=None, c0=None):
+        """A new LP on the analysed handle: `A` (same pattern; scipy matrix, 1-D values, or a 2-D array on a dense handle) goes through
+        set_values, the vectors that are given replace the stored ones (None = keep; bounds may change between finite and infinite),
+        tlpk_ipm_reload refreshes the device copies and restores the starting point.  `optimize()` then solves the new LP."""
+        from .kkt import set_values
+        if A is not None:
+            set_values(self.kkt, A)
+        new = {}
+        for name, v, length in (("b", b, self.m), ("c", c, self.n), ("l", l, self.n), ("u", u, self.n)):
+            if v is None:
+                continue
+            a = np.array(v, dtype=np.float64, order="C", copy=True)
+            if a.shape != (length,):
+                raise DimensionMismatch(f"reload: {name} does not match A")
+            new[name] = a
+        ptr = lambda name: _lib.as_pd(new[name]) if name in new else None    # noqa: E731
+        self._call(self.L.tlpk_ipm_reload(self.kkt._h, ptr("b"), ptr("c"), ptr("l"), ptr("u")))
+        self._b, self._c = new.get("b", self._b), new.get("c", self._c)
+        self._l, self._u = new.get("l", self._l), new.get("u", self._u)
+        if c0 is not None:
+            self.c0 = float(c0)
+        self._host_norms()
+        self.niter = 0
+        self.status = "Trm_Unknown"
+        self.primal_status = self.dual_status = "Sln_Unknown"
+        self.timers = {"n_update": 0, "n_solve": 0, "n_bump": 0}
+        return self
 
     def _call(self, rc):
         if rc == _lib.NOT_POSDEF:

@@ -194,6 +194,29 @@ end
 setup(A::AbstractMatrix, system::K1, b::DenseBackend) = setup(Matrix{Float64}(A), system, b)
 setup(::AbstractMatrix, ::K2, ::DenseBackend) = throw(ArgumentError("TlpHIP.DenseBackend solves the normal equations (K1) only"))
 
+"""
+    set_values!(kkt, A)
+
+New numerical values on the analysed pattern (`tlpk_set_values`): `A` must have the `colptr` / `rowval` of the matrix given to
+`setup` (a dense handle: the same size).  The analysis -- ordering, supernodes, schedules, device allocations -- is kept, `kkt.A` is
+replaced, and the next `update!` factorises the new matrix.
+"""
+function set_values!(kkt::HIPNormalEquations, A::SparseMatrixCSC{Float64,Int})
+    kkt.A isa SparseMatrixCSC || throw(DimensionMismatch("set_values!: a dense handle takes a Matrix{Float64}"))
+    (size(A) == size(kkt.A) && A.colptr == kkt.A.colptr && A.rowval == kkt.A.rowval) ||
+        throw(DimensionMismatch("set_values!: A does not have the pattern the handle was analysed on"))
+    _check(LibTLPK.set_values!(kkt.handle, A.nzval), kkt.handle, "set_values!")
+    kkt.A = A
+    return nothing
+end
+function set_values!(kkt::HIPNormalEquations, A::Matrix{Float64})
+    kkt.A isa Matrix || throw(DimensionMismatch("set_values!: a sparse handle takes a SparseMatrixCSC{Float64,Int}"))
+    size(A) == size(kkt.A) || throw(DimensionMismatch("set_values!: size(A)=$(size(A)) but the handle has $(size(kkt.A))"))
+    _check(LibTLPK.set_values!(kkt.handle, A), kkt.handle, "set_values!")
+    kkt.A = A
+    return nothing
+end
+
 function update!(kkt::HIPNormalEquations, θ::Vector{Float64}, regP::Vector{Float64}, regD::Vector{Float64})
     m, n = kkt.m, kkt.n
     # Sanity checks, same messages as spd.jl:26-34

@@ -149,6 +149,29 @@ function detect_blocks(m::Int, n::Int, colptr::Vector{Int}, rowval::Vector{Int};
     return resize!(rb, m), Int(nb[]), Int(nl[])
 end
 
+"""
+    set_values!(h, nzval) / set_values!(h, A::Matrix{Float64})
+
+`tlpk_set_values` / `tlpk_set_values_dense`: new numerical values on the pattern the handle was analysed on (`nzval` in the order of
+the `SparseMatrixCSC` given to `create`).  The analysis is kept; the handle is not factored afterwards.
+"""
+set_values!(h::Ptr{Cvoid}, nzval::Vector{Float64}) =
+    GC.@preserve nzval ccall((:tlpk_set_values, libtlpk[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h, nzval, length(nzval))
+set_values!(h::Ptr{Cvoid}, A::Matrix{Float64}) =
+    GC.@preserve A ccall((:tlpk_set_values_dense, libtlpk[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), h, A, max(size(A, 1), 1))
+
+"""
+    ipm_reload!(h; b, c, l, u)
+
+`tlpk_ipm_reload`: new LP data for the device-resident loops of a handle that has been loaded (`nothing` = keep the vector).
+"""
+function ipm_reload!(h::Ptr{Cvoid}; b::Union{Nothing,Vector{Float64}}=nothing, c::Union{Nothing,Vector{Float64}}=nothing,
+                     l::Union{Nothing,Vector{Float64}}=nothing, u::Union{Nothing,Vector{Float64}}=nothing)
+    p(v) = v === nothing ? Ptr{Float64}(C_NULL) : pointer(v)
+    return GC.@preserve b c l u ccall((:tlpk_ipm_reload, libtlpk[]), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, p(b), p(c), p(l), p(u))
+end
+
 update(h::Ptr{Cvoid}, θinv::Vector{Float64}, regP::Vector{Float64}, regD::Vector{Float64}) =
     GC.@preserve θinv regP regD ccall((:tlpk_update, libtlpk[]), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, θinv, regP, regD)

@@ -408,6 +408,46 @@ def solve(dx, dy, kkt, xi_p, xi_d):
     return None
 
 
+def set_values(kkt, A_or_data):
+    """New numerical values on the analysed pattern (tlpk_set_values / tlpk_set_values_dense): the handle keeps its analysis and is
+    NOT factored afterwards -- `update` before the next `solve`.  Sparse handles take a scipy matrix whose sorted CSC pattern
+    equals the handle's (otherwise DimensionMismatch) or a 1-D array of nnz(A) values in that order; dense-matrix handles a 2-D
+    array of the handle's shape.  `kkt.A` is replaced by a matrix with the new values (the caller's old matrix is not modified)."""
+    import scipy.sparse as sp
+    L = _lib.lib()
+    if isinstance(kkt, HIPDenseNormalEquations):
+        if sp.issparse(A_or_data):
+            raise DimensionMismatch("set_values: a dense-matrix handle takes a 2-D array")
+        A = np.asarray(A_or_data)
+        if A.ndim != 2 or A.shape != (kkt.m, kkt.n):
+            raise DimensionMismatch(f"set_values: array of shape {A.shape} but the handle has a {kkt.m} x {kkt.n} matrix")
+        A = np.asfortranarray(A, dtype=np.float64)
+        _raise_for(L.tlpk_set_values_dense(kkt._h, A.ctypes.data_as(_lib.pd), max(kkt.m, 1)), kkt._h, "set_values: ")
+        kkt.A = A
+        return None
+    if sp.issparse(A_or_data):
+        B = A_or_data.tocsc()
+        if B is A_or_data:
+            B = B.copy()
+        B.sort_indices()
+        if B.shape != kkt.A.shape or not np.array_equal(B.indptr, kkt.A.indptr) or not np.array_equal(B.indices, kkt.A.indices):
+            raise DimensionMismatch("set_values: the matrix does not have the pattern the handle was analysed on")
+        data = np.ascontiguousarray(B.data, dtype=np.float64)
+    else:
+        data = np.ascontiguousarray(A_or_data, dtype=np.float64)
+        if data.ndim != 1:
+            raise DimensionMismatch("set_values: a sparse handle takes a scipy matrix or a 1-D array of nnz(A) values")
+    _raise_for(L.tlpk_set_values(kkt._h, _lib.as_pd(data), data.shape[0]), kkt._h, "set_values: ")
+    kkt.A = sp.csc_matrix((data.copy(), kkt.A.indices, kkt.A.indptr), shape=kkt.A.shape)
+    return None
+
+
+def set_values_device(kkt, d_nzval, length):
+    """tlpk_set_values_device: the values are in device memory (integer address), the refresh is enqueued on the handle's stream.
+    `kkt.A` is NOT updated (the values never reach the host)."""
+    _raise_for(_lib.lib().tlpk_set_values_device(kkt._h, d_nzval, int(length)), kkt._h, "set_values: ")
+
+
 def arithmetic(kkt):
     """KKT.arithmetic (KKT.jl:107)."""
     return np.float64
