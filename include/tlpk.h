@@ -44,6 +44,12 @@ typedef struct tlpk_handle tlpk_handle;
                                 row_block gives per-block ordering, stream groups and a root front; sharded / multi-device handles
                                 replicate the root front (pivots of both signs), its assembled entries come from rank 0 */
 
+/* tlpk_options.krylov */
+#define TLPK_KRYLOV_NONE 0
+#define TLPK_KRYLOV_CG 1
+#define TLPK_PRECOND_NONE 0
+#define TLPK_PRECOND_JACOBI 1
+
 /* ordering selector */
 #define TLPK_ORDER_AMD 0
 #define TLPK_ORDER_NATURAL 1
@@ -84,6 +90,12 @@ typedef struct tlpk_options {
     int64_t dense_col_min;     /* a column with MORE than this many entries qualifies; 0 = 1000 */
     const int64_t *col_dense;  /* optional, length n: nonzero = this column qualifies whatever its count (e.g. first-stage variables);
                                   like row_block, only meaningful on the matrix the caller analyses (no presolve in between) */
+    /* Matrix-free handle (the reference's Krylov family, src/KKT/Krylov/spd.jl): no analysis, no factor, O(nnz(A) + m + n) device memory.  See tlpk_create. */
+    int32_t krylov;            /* TLPK_KRYLOV_NONE 0 (default: analyse + factorise) | TLPK_KRYLOV_CG 1: K1, conjugate gradients on
+                                  (A D A' + Rd) dy = xi_p + A D xi_d, matrix-free (src/KKT/Krylov/spd.jl) */
+    int32_t krylov_precond;    /* 0 = none (the reference) | 1 = Jacobi: M = diag(A D A' + Rd), rebuilt by every update */
+    int64_t krylov_itmax;      /* 0 = 2 m (Krylov.jl's default) */
+    double  krylov_atol, krylov_rtol;   /* 0 = sqrt(eps) (spd.jl:66-67); < 0 or non-finite: TLPK_BADARG */
 } tlpk_options;
 
 typedef struct tlpk_stats {
@@ -122,6 +134,14 @@ typedef struct tlpk_stats {
                                   m, n, nnzA are the caller's; nnzS, nnzL, n_pairs, fail_col, ... describe the factored matrix of order m + k */
     double  flops_syrk;        /* dense-matrix handles (tlpk_create_dense): n m (m + 1), the flops of the lower triangle of A*D*A' on the matrix cores
                                   (2 per product); 0 on sparse handles */
+    /* matrix-free handles (tlpk_options.krylov); 0 on every other handle.  (Placed in front of the tlpk_set_values pair, which stays the tail of the struct;
+       tlpk_stats carries no size field, so any new field means a rebuild of the callers wherever it goes.) */
+    int64_t krylov_iters;        /* CG iterations of the last solve */
+    int64_t krylov_iters_total;  /* since the last update */
+    int64_t krylov_converged;    /* 1 = the last solve met the stopping rule; 0 = it stopped at itmax or broke down */
+    double  krylov_resid0, krylov_resid;   /* sqrt(r' M^-1 r) at x = 0 and at exit of the last solve */
+                                 /* tlpk_symbolic_get(h, "krylov_unsolved"): one entry, the number of solves since create that did NOT meet the stopping
+                                    rule (what a loop of many solves checks once at its end instead of reading krylov_converged after every solve) */
     double  ms_last_set_values; /* device time of the last tlpk_set_values* (HIP events on the handle's stream; multi-device handles: the slowest shard);
                                    host time on analyse-only handles */
     int64_t set_values_bytes;  /* device memory held by the maps of tlpk_set_values (part of device_bytes); 0 before the first call */
@@ -155,6 +175,26 @@ void tlpk_default_options(tlpk_options *opt);
 int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr,
                 const int64_t *rowval, const double *nzval, int index_base,
                 const tlpk_options *opt);
+/* Matrix-free handle: opt->krylov = TLPK_KRYLOV_CG (K1; the reference's src/KKT/Krylov/spd.jl).  tlpk_create then skips ordering, the pattern of S,
+ * supernodes, lists and schedules and keeps only the CSC and the row-wise copy of A in the caller's order: tlpk_stats nnzS = nnzL = nnzL_stored = n_pairs =
+ * n_supernodes = 0, flops_* = 0, tlpk_get_perm = the identity, every symbolic array empty, tlpk_get_factor: TLPK_BADARG.  The memory gate counts the copies of A
+ * and the vectors.  TLPK_BADARG (sentence in tlpk_last_create_error()): system = K2, nranks > 1, dense_cols, refine_steps > 0, user_perm, an unknown krylov /
+ * krylov_precond value, krylov_itmax < 0, a negative or non-finite tolerance; tlpk_create_multi and tlpk_create_dense refuse the option.  row_block,
+ * detect_blocks, ordering, relax and streams are ignored.  device = -1: an analyse-only handle (numeric calls: TLPK_NO_DEVICE).  The split-phase calls
+ * (tlpk_*_local / tlpk_*_finish, tlpk_root_*, tlpk_refine_*) do not apply: TLPK_BADARG.
+ *   update : D = 1 / (theta^-1 + Rp), Rd is kept; Jacobi: M_i = sum_j A_ij^2 D_j + Rd_i in one pass over the rows (an empty row with Rd_i = 0 has
+ *            M_i = 0 and is left unscaled, M^-1_i = 1).  Never TLPK_NOT_POSDEF.
+ *            tlpk_update_device_async is the blocking call.
+ *   solve  : b = xi_p + A (D .* xi_d); conjugate gradients from x = 0 with z = M^-1 r, gamma = r'z: SOLVED when sqrt(gamma) <= atol + rtol sqrt(gamma at x = 0)
+ *            (a zero right-hand side: in 0 iterations), NOT solved after krylov_itmax iterations, or when p'Sp <= 0 or a scalar is not finite (Krylov.jl's cg);
+ *            then dy = x, dx = D .* (A' dy - xi_d).  A solve that is NOT solved still writes its last iterate and returns TLPK_OK, as the reference does
+ *            (spd.jl:100-101 does not look at the outcome): tlpk_stats.krylov_converged / krylov_iters / krylov_resid say what happened -- a caller that
+ *            needs a solved system must read them.  The number of launches depends on the data, so tlpk_solve_device on such a handle BLOCKS until the outcome
+ *            is known (iterations are enqueued in chunks, the host reads the outcome word between chunks); dx / dy are complete after tlpk_sync as usual.
+ *            tlpk_solve2_device is two solves.  Two solves of the same data are bit-identical (no atomics, ordered reductions).
+ *   tlpk_set_values* refreshes the copies of A; the device-resident loops (tlpk_ipm_*, tlpk_mpc_*) run through the same solve path.
+ * What to expect: conjugate gradients without a preconditioner (the reference: spd.jl:26 "TODO: preconditioner") or with Jacobi solve the early, well-conditioned
+ * systems of an interior-point run in tens of iterations and stall on the late ones (DESIGN.md section 1b has the measured limits). */
 /* Dense constraint matrix (the reference's dense backend, src/KKT/Dense/lapack.jl; K1 only).  A: m x n, column-major, leading dimension
  * lda >= m (a Julia Matrix{Float64}); copied, nothing retained.  The handle then behaves like any single-device K1 handle: natural order,
  * ONE dense front of m columns, A*D*A' + Rd formed on the fp64 matrix cores (timed as TLPK_KC_ASSEMBLE) straight into the front's panel,
@@ -279,7 +319,7 @@ int tlpk_set_profile(tlpk_handle *h, int on);   /* toggle per-launch HIP-event t
 int tlpk_get_perm(const tlpk_handle *h, int64_t *perm /*m, 0-based, perm[new] = old*/);   /* dense_cols: the constraint nodes in their order
                                                    (the whole order-(m + k) permutation: tlpk_symbolic_get(h, "perm"), node m + t = dense column t) */
 /* Symbolic structures, for tests and tools.  `what` selects an array; returns its length and,
- * if buf != NULL, copies min(len, cap) int64 entries. */
+ * if buf != NULL, copies min(len, cap) int64 entries.  One key is a counter, not a structure: "krylov_unsolved" (matrix-free handles; see tlpk_stats). */
 int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, int64_t cap);
 int64_t tlpk_symbolic_get_f64(const tlpk_handle *h, const char *what, double *buf, int64_t cap);
 /* Copy the numeric factor panels (device -> host), nnzL_stored doubles.  Layout: front s (symbolic arrays front_f, front_ns, front_loff,

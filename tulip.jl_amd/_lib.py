@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("TLPK_LIB") or os.path.join(HERE, "libtlpk.so")      #
 OK, NOT_POSDEF, BADARG, OOM, HIPERR, NO_DEVICE, TOO_LARGE, NOT_FACTORED, INTERNAL = range(9)
 ORDER_AMD, ORDER_NATURAL, ORDER_USER = 0, 1, 2
 SYSTEM_K1, SYSTEM_K2 = 0, 1
+KRYLOV_NONE, KRYLOV_CG = 0, 1
+PRECOND_NONE, PRECOND_JACOBI = 0, 1
 KC_NAMES = ["assemble", "extend_add", "potrf", "trsm", "update", "solve_fwd", "solve_bwd", "spmv", "update_reduce", "chain"]
 
 p64 = C.POINTER(C.c_int64)
@@ -28,7 +30,9 @@ class Options(C.Structure):
                 ("user_perm", p64), ("row_block", p64), ("mem_budget_bytes", C.c_int64),
                 ("system", C.c_int32), ("refine_steps", C.c_int32),
                 ("detect_blocks", C.c_int32), ("keep_on_too_large", C.c_int32), ("max_link_rows", C.c_int64),
-                ("dense_cols", C.c_int32), ("max_dense_cols", C.c_int32), ("dense_col_min", C.c_int64), ("col_dense", p64)]
+                ("dense_cols", C.c_int32), ("max_dense_cols", C.c_int32), ("dense_col_min", C.c_int64), ("col_dense", p64),
+                ("krylov", C.c_int32), ("krylov_precond", C.c_int32), ("krylov_itmax", C.c_int64),
+                ("krylov_atol", C.c_double), ("krylov_rtol", C.c_double)]
 
 
 class Stats(C.Structure):
@@ -43,6 +47,8 @@ class Stats(C.Structure):
                 ("flops_update_alg", C.c_double), ("ms_enqueue_update", C.c_double), ("refine_rejected", C.c_int64),
                 ("flops_update_chain", C.c_double), ("flops_update_alg_chain", C.c_double), ("chain_launches", C.c_int64), ("chain_items", C.c_int64),
                 ("n_dense_cols", C.c_int64), ("flops_syrk", C.c_double),
+                ("krylov_iters", C.c_int64), ("krylov_iters_total", C.c_int64), ("krylov_converged", C.c_int64),
+                ("krylov_resid0", C.c_double), ("krylov_resid", C.c_double),
                 ("ms_last_set_values", C.c_double), ("set_values_bytes", C.c_int64)]
 
     def as_dict(self):

@@ -2814,6 +2814,48 @@ int build_value_maps(const Symbolic &S, i32 rank, ValueMaps &M) {
     return TLPK_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Matrix-free handle (tlpk_options.krylov): the CSC copy of A and its row-wise copy in the caller's order, identity "permutation", and
+// nothing else -- no ordering, no pattern of S, no fronts, lists or schedules.  Host time and memory O(nnz(A) + m + n).
+// ---------------------------------------------------------------------------------------------
+int analyse_krylov(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowval, const double *nzval, int base) {
+    if (m < 0 || n < 0 || (base != 0 && base != 1) || !colptr) return fail(S, TLPK_BADARG, "bad dimensions or index base");
+    if (m >= (i64)1 << 31 || n >= (i64)1 << 31) return fail(S, TLPK_TOO_LARGE, "m or n exceeds int32");
+    const i64 nnz = colptr[n] - base;
+    if (nnz < 0 || nnz >= (i64)1 << 31) return fail(S, TLPK_TOO_LARGE, "nnz(A) exceeds int32");
+    if (nnz > 0 && (!rowval || !nzval)) return fail(S, TLPK_BADARG, "null rowval/nzval");
+    S.m = m; S.n = n; S.nnzA = nnz; S.system = 0;
+    S.Ap.resize((size_t)n + 1); S.Ai.resize((size_t)nnz); S.Ax.resize((size_t)nnz);
+    S.Tp.assign((size_t)m + 1, 0); S.Tj.resize((size_t)nnz); S.Tpos.resize((size_t)nnz);
+    for (i64 j = 0; j <= n; ++j) {
+        S.Ap[(size_t)j] = colptr[j] - base;
+        if (S.Ap[(size_t)j] < 0 || S.Ap[(size_t)j] > nnz || (j > 0 && S.Ap[(size_t)j] < S.Ap[(size_t)j - 1])) return fail(S, TLPK_BADARG, "colptr not monotone");
+    }
+    if (n > 0 && S.Ap[0] != 0) return fail(S, TLPK_BADARG, "colptr does not start at index_base");
+    for (i64 p = 0; p < nnz; ++p) {
+        const i64 r = rowval[p] - base;
+        if (r < 0 || r >= m) return fail(S, TLPK_BADARG, "row index out of range");
+        S.Ai[(size_t)p] = (i32)r; S.Ax[(size_t)p] = nzval[p];
+        S.Tp[(size_t)r + 1]++;
+    }
+    for (i64 i = 0; i < m; ++i) S.Tp[(size_t)i + 1] += S.Tp[(size_t)i];
+    {
+        std::vector<i64> cur(S.Tp.begin(), S.Tp.end() - 1);
+        for (i64 j = 0; j < n; ++j)
+            for (i64 p = S.Ap[(size_t)j]; p < S.Ap[(size_t)j + 1]; ++p) {         // column order inside a row: the order the direct handles' row-wise copy has
+                const i64 q = cur[(size_t)S.Ai[(size_t)p]]++;
+                S.Tj[(size_t)q] = (i32)j; S.Tpos[(size_t)q] = (i32)p;
+            }
+    }
+    S.perm.resize((size_t)m); S.iperm.resize((size_t)m);
+    for (i64 i = 0; i < m; ++i) S.perm[(size_t)i] = S.iperm[(size_t)i] = (i32)i;
+    S.row_local.assign((size_t)m, 1); S.col_local.assign((size_t)n, 1);
+    S.pair_ptr.assign(1, 0);                       // (no entry of S, no product)
+    S.nsuper = 0; S.nlevels = 0; S.nblocks = 0; S.root_front = -1; S.ngroups = 1; S.n_local_blocks = 0;
+    S.error.clear();
+    return TLPK_OK;
+}
+
 // the host side of a refresh: the value array of the analysed matrix and -- where the host still holds them (analyse-only handles) -- the products
 void host_set_values(Symbolic &S, const ValueMaps &M, const double *nz) {
     if (S.system == 1) { for (size_t q = 1; q < S.Ax.size(); q += 2) S.Ax[q] = nz[q >> 1]; }

@@ -12,6 +12,8 @@
 #include <atomic>
 #include <chrono>
 #include <climits>
+#include <cmath>
+#include <limits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -523,6 +525,62 @@ int tlpk_device_count(void) {
 
 int tlpk_host_copy_threads(void) { return host_copy_threads(); }
 
+// ---- matrix-free K1 (tlpk_options.krylov): set-up ----
+// device memory of such a handle: the CSC copy of A and two row-wise copies (36 nnz), the vectors of every handle and of the iteration
+static double krylov_bytes(const tlpk_handle *h) { return 36.0 * (double)h->S.nnzA + 80.0 * (double)h->S.n + 136.0 * (double)h->S.m + 65536.0; }
+// the options of a matrix-free handle: nullptr, or the sentence that says what is wrong
+// the memory gate of a matrix-free handle, with or without a device
+static int krylov_gate(tlpk_handle *h, double budget) {
+    const double need = krylov_bytes(h);
+    if (need <= budget) return TLPK_OK;
+    h->last_error = "matrix-free handle: the copies of A and the vectors need " + std::to_string((long long)need) + " bytes, budget " +
+                    std::to_string((long long)budget) + " bytes";
+    return TLPK_TOO_LARGE;
+}
+
+static const char *krylov_check(const tlpk_options &def) {
+    if (def.krylov != TLPK_KRYLOV_CG) return "krylov: TLPK_KRYLOV_NONE (0) or TLPK_KRYLOV_CG (1)";
+    if (def.krylov_precond != TLPK_PRECOND_NONE && def.krylov_precond != TLPK_PRECOND_JACOBI) return "krylov_precond: 0 (none) or 1 (Jacobi)";
+    if (def.krylov_itmax < 0) return "krylov_itmax: >= 0 (0 = 2 m)";
+    if (!(def.krylov_atol >= 0.0) || !std::isfinite(def.krylov_atol) || !(def.krylov_rtol >= 0.0) || !std::isfinite(def.krylov_rtol))
+        return "krylov_atol, krylov_rtol: finite and >= 0 (0 = sqrt(eps))";
+    if (def.system != TLPK_SYSTEM_K1) return "krylov: K1 only (conjugate gradients need the positive definite normal equations; MINRES / TriCG on K2 are not implemented)";
+    if (def.nranks > 1 || def.rank != 0) return "krylov: one rank only (nranks = 1)";
+    if (def.dense_cols) return "krylov: dense_cols does not apply (A*D*A' is never formed)";
+    if (def.refine_steps != 0) return "krylov: refine_steps > 0 is not supported";
+    if (def.user_perm) return "krylov: user_perm does not apply (there is no factor to order)";
+    return nullptr;
+}
+// the vectors and scalars of the iteration, the lists of the long rows / columns, the launch geometry
+static int krylov_upload(tlpk_handle *h) {
+    const Symbolic &S = h->S;
+    CgArrays &c = h->cg;
+    const i64 m = S.m, n = S.n;
+    std::vector<i32> lr, lc;
+    for (i64 i = 0; i < m; ++i) if (S.Tp[(size_t)i + 1] - S.Tp[(size_t)i] > CG_LONG) lr.push_back((i32)i);
+    for (i64 j = 0; j < n; ++j) if (S.Ap[(size_t)j + 1] - S.Ap[(size_t)j] > CG_LONG) lc.push_back((i32)j);
+    c.n_long_rows = (i64)lr.size(); c.n_long_cols = (i64)lc.size();
+    int rc;
+    if ((rc = dev_upload(h, &c.long_rows, lr)) != TLPK_OK) return rc;
+    if ((rc = dev_upload(h, &c.long_cols, lc)) != TLPK_OK) return rc;
+    c.g_rows = (int)std::max<i64>(1, std::min<i64>((m * 8 + 1023) / 1024, CG_MAX_SLOTS));      // (k_cg_rows: 1024 threads, 8 lanes per row)
+    c.g_long = (int)std::min<i64>(c.n_long_rows, CG_MAX_LONG);
+    c.g_vec = (int)std::max<i64>(1, std::min<i64>((m + 255) / 256, CG_MAX_SLOTS));
+    if ((rc = dev_alloc(h, &c.x, m)) != TLPK_OK || (rc = dev_alloc(h, &c.p, m)) != TLPK_OK || (rc = dev_alloc(h, &c.q, m)) != TLPK_OK ||
+        (rc = dev_alloc(h, &c.t, n)) != TLPK_OK || (rc = dev_alloc(h, &c.slots_r, c.g_rows + c.g_long)) != TLPK_OK ||
+        (rc = dev_alloc(h, &c.slots_v, c.g_vec)) != TLPK_OK || (rc = dev_alloc(h, &c.sc, 1)) != TLPK_OK) return rc;
+    if (h->krylov_precond == TLPK_PRECOND_JACOBI && (rc = dev_alloc(h, &c.Minv, m)) != TLPK_OK) return rc;
+    HIPCHK(h, hipMemset(c.sc, 0, sizeof(CgScalars)));
+    HIPCHK(h, hipHostMalloc((void **)&h->cg_pin, sizeof(CgScalars), hipHostMallocDefault));
+    std::memset(h->cg_pin, 0, sizeof(CgScalars));
+    HIPCHK(h, hipEventCreateWithFlags(&h->cg_ev, hipEventDisableTiming));
+    if (const char *e = std::getenv("TLPK_CG_CHUNK")) {
+        long long a = 0, b = 0;
+        if (std::sscanf(e, "%lld,%lld", &a, &b) == 2 && a >= 1 && b >= a) { h->cg_chunk0 = a; h->cg_chunk_max = b; }
+    }
+    return TLPK_OK;
+}
+
 // tlpk_create in two steps (tlpk_create_multi runs the first one once for all shards and the second per device):
 //   create_host   : options -> handle, block detection, host analyse (or: copy of an analysed Symbolic + this rank's part)
 //   create_device : streams / events, memory gate, upload
@@ -600,6 +658,7 @@ static int create_host(tlpk_handle *h, const tlpk_options &def, int64_t m, int64
     const auto t0 = std::chrono::steady_clock::now();
     if (rc == TLPK_OK) {
         if (common) { h->S = *common; h->opt.k2_n = common->k2_n; rc = analyse_rank(h->S, h->opt); }
+        else if (h->krylov) rc = analyse_krylov(h->S, m, n, colptr, rowval, nzval, index_base);
         else if (!dense.empty()) rc = analyse_dense(h->S, m, n, colptr, rowval, nzval, index_base, h->opt, dense);
         else rc = (h->opt.system == 1) ? analyse_k2(h->S, m, n, colptr, rowval, nzval, index_base, h->opt)
                                        : analyse(h->S, m, n, colptr, rowval, nzval, index_base, h->opt);
@@ -667,7 +726,9 @@ static int create_device(tlpk_handle *h, const tlpk_options &def) {
                                 (double)sizeof(UpdateTask) * (double)(h->S.update_tasks.size() + h->S.reduce_tasks.size()) +
                                 (double)sizeof(EaTask) * (double)h->S.ea_tasks.size() + (double)sizeof(TrsmTask) * (double)h->S.trsm_tasks.size() +
                                 4.0 * (double)h->S.upd_seg.size() + 32.0 * (double)h->S.m;
-            if (h->S.dense_matrix) {
+            if (h->krylov) {
+                rc = krylov_gate(h, budget);
+            } else if (h->S.dense_matrix) {
                 // the device copy of A, the panel, the workspace of the factorisation and of the two dense kernels
                 const double need_d = 8.0 * ((double)h->S.n * (double)dense_lda(h->S.m) + (double)h->S.lval_len + (double)h->S.spart_len + (double)h->S.dinv_len +
                                              2.0 * (double)h->S.gemv_chunks * (double)dense_lda(h->S.m) + 8.0 * (double)h->S.n + 12.0 * (double)h->S.m) +
@@ -679,8 +740,7 @@ static int create_device(tlpk_handle *h, const tlpk_options &def) {
                                     " bytes, budget " + std::to_string((long long)budget) + " bytes";
                     rc = TLPK_TOO_LARGE;
                 }
-            } else
-            if (need > budget) {
+            } else if (need > budget) {
                 h->last_error = "factor needs " + std::to_string(need / 1e9) + " GB, budget " + std::to_string(budget / 1e9) + " GB";
                 if (h->S.system == 0 && !h->S.Ap.empty()) {
                     // K1 forms A D A': one column of A with c entries makes a c x c dense block of S ("dense columns")
@@ -695,7 +755,10 @@ static int create_device(tlpk_handle *h, const tlpk_options &def) {
             }
         }
         if (rc == TLPK_OK) rc = upload_all(h);
+        if (rc == TLPK_OK && h->krylov) rc = krylov_upload(h);
         if (rc == TLPK_OK) h->has_device = true;
+    } else if (def.mem_budget_bytes > 0 && h->krylov) {
+        rc = krylov_gate(h, (double)def.mem_budget_bytes);
     } else if (def.mem_budget_bytes > 0) {
         const double need = 8.0 * ((double)h->S.lval_len + (double)h->S.ubuf_len[0] + (double)h->S.ubuf_len[1] +
                                    (h->S.dense_matrix ? (double)h->S.n * (double)dense_lda(h->S.m) + (double)h->S.spart_len : 0.0));
@@ -718,9 +781,21 @@ int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr, 
         if (uopt->struct_size != (int32_t)sizeof(tlpk_options)) return TLPK_BADARG;
         def = *uopt;
     }
+    if (def.krylov != TLPK_KRYLOV_NONE) {
+        if (const char *bad = krylov_check(def)) { g_create_error = std::string("tlpk_create: ") + bad; return TLPK_BADARG; }
+        // no factor: nothing to order, no block structure to exploit, one stream
+        def.row_block = nullptr; def.detect_blocks = 0; def.ordering = TLPK_ORDER_NATURAL; def.streams = 1;
+    }
     tlpk_handle *h = new (std::nothrow) tlpk_handle();
     if (!h) return TLPK_OOM;
     int rc = TLPK_OK;
+    if (def.krylov != TLPK_KRYLOV_NONE) {
+        h->krylov = def.krylov; h->krylov_precond = def.krylov_precond;
+        h->krylov_itmax = def.krylov_itmax > 0 ? def.krylov_itmax : 2 * std::max<int64_t>(m, 0);
+        const double se = std::sqrt(std::numeric_limits<double>::epsilon());
+        h->krylov_atol = def.krylov_atol > 0.0 ? def.krylov_atol : se;
+        h->krylov_rtol = def.krylov_rtol > 0.0 ? def.krylov_rtol : se;
+    }
     try {
         rc = create_host(h, def, m, n, colptr, rowval, nzval, index_base, nullptr);
         if (rc == TLPK_OK) rc = create_device(h, def);
@@ -760,6 +835,7 @@ int tlpk_create_dense(tlpk_handle **out, int64_t m, int64_t n, const double *A, 
     else if (def.user_perm) bad = "user_perm does not apply (the order is natural: a dense matrix has no fill to reduce)";
     else if (def.dense_cols) bad = "dense_cols does not apply (every column is dense; the product is formed on the matrix cores)";
     else if (def.refine_steps != 0) bad = "refine_steps > 0 is not supported (the refinement kernels read a sparse A)";
+    else if (def.krylov != TLPK_KRYLOV_NONE) bad = "krylov does not apply (the matrix-free handle takes a sparse A: tlpk_create)";
     if (bad) { g_create_error = std::string("tlpk_create_dense: ") + bad; return TLPK_BADARG; }
     tlpk_handle *h = new (std::nothrow) tlpk_handle();
     if (!h) return TLPK_OOM;
@@ -828,6 +904,8 @@ void tlpk_destroy(tlpk_handle *h) {
         if (h->h_info) hipHostFree(h->h_info);
         if (h->pin_in) hipHostFree(h->pin_in);
         if (h->pin_out) hipHostFree(h->pin_out);
+        if (h->cg_pin) hipHostFree(h->cg_pin);
+        if (h->cg_ev) hipEventDestroy(h->cg_ev);
         for (hipEvent_t e : h->io_events) hipEventDestroy(e);
         for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
         if (h->ev0) hipEventDestroy(h->ev0);
@@ -866,6 +944,10 @@ enum : unsigned { R_DENSE = 1, R_MULTI = 2, R_DEVICE = 4, R_FACTORED = 8 };
 static int refuse(tlpk_handle *h, bool args_ok, unsigned checks, const char *what = "") {
     if ((checks & R_DENSE) && h && h->S.dense_matrix) {
         h->last_error = std::string(what) + ": the split-phase calls do not apply to a dense-matrix handle (tlpk_create_dense)";
+        return TLPK_BADARG;
+    }
+    if ((checks & R_DENSE) && h && h->krylov) {
+        h->last_error = std::string(what) + ": the split-phase calls do not apply to a matrix-free handle (tlpk_options.krylov): there is no root front to reduce";
         return TLPK_BADARG;
     }
     if (!h || !args_ok) return TLPK_BADARG;
@@ -1083,7 +1165,23 @@ static int update_async_wait(tlpk_handle *h) {
     return rc;
 }
 
+// ---- matrix-free K1 (tlpk_options.krylov): update and solve ----
+// update: D = 1 / (theta^-1 + Rp) and, with Jacobi, the inverted diagonal of S; there is no factor that could fail
+static int krylov_update(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
+    if (int rc = update_begin(h, d_theta, d_regP, d_regD)) return rc;
+    { ProfScope ps(h, TLPK_KC_ASSEMBLE); launch_compute_d(h->stream, h->S.n, h->d_theta, h->d_regP, h->d_D); }
+    if (h->cg.Minv) { ProfScope ps(h, TLPK_KC_SPMV); launch_cg_jacobi(h->stream, h->d, h->cg, h->d_D, h->d_regD); }
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    float ms = 0.f; hipEventElapsedTime(&ms, h->ev0, h->ev1); h->ms_update = ms;
+    prof_collect(h);
+    h->factored = true;
+    h->cg_iters_total = 0;
+    return TLPK_OK;
+}
 int tlpk_update_device_async(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
+    if (h && h->krylov) return krylov_update(h, d_theta, d_regP, d_regD);
     if (int g = sharded_needs_split(h, "tlpk_update_device_async")) return g;
     if (!h || !h->sub.empty() || !h->has_device || h->profile || h->serial || graph_usable(h) || !h->rstream)
         return tlpk_update_device(h, d_theta, d_regP, d_regD);          // nothing to overlap / a mode that serialises anyway: the blocking call
@@ -1102,6 +1200,7 @@ int tlpk_update_device_async(tlpk_handle *h, const double *d_theta, const double
 }
 
 int tlpk_update_device(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
+    if (h && h->krylov) return krylov_update(h, d_theta, d_regP, d_regD);
     if (int g = sharded_needs_split(h, "tlpk_update_device")) return g;
     int rc = update_begin(h, d_theta, d_regP, d_regD);
     if (rc != TLPK_OK) return rc;
@@ -1392,6 +1491,57 @@ static int solve_composed(tlpk_handle *h, const SolveIo &io, bool whole) {
     return solve_whole(h, io);
 }
 
+// ---- matrix-free K1 (tlpk_options.krylov) ----
+// solve: b into xw, conjugate gradients from x = 0 in chunks of iterations -- after each chunk the scalar block comes back through pinned memory and the
+// host decides whether another chunk is needed (the kernels of a chunk enqueued past the end of the solve return at once) --, then dy = x and dx.
+// BLOCKS until the outcome is known; dy / dx are enqueued behind it.
+static int krylov_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
+    if (!d_dx || !d_dy) return TLPK_BADARG;
+    if (int g = refuse(h, d_xip && d_xid, R_MULTI | R_DEVICE | R_FACTORED)) return g;
+    if (int rc = solve_begin(h)) return rc;
+    const double *xp[2] = {d_xip, d_xip}, *xd[2] = {d_xid, d_xid};
+    double *dy[2] = {d_dy, d_dy}, *dx[2] = {d_dx, d_dx};
+    const i64 m = h->S.m, itmax = h->krylov_itmax;
+    i64 launches = 4;
+    {
+        ProfScope ps(h, TLPK_KC_SPMV);
+        launch_rhs(h->stream, h->d, h->d_D, xp, xd, 0, 1);
+        launch_cg_init(h->stream, h->d, h->cg, h->krylov_atol, h->krylov_rtol, itmax);
+    }
+    // enqueue a chunk, copy the scalars, wait: the first chunk goes out before the first look (a zero right-hand side is settled by cg_init, and the
+    // chunk behind it returns at once), so a solve that fits the first chunk costs one host round trip
+    i64 enq = 0, chunk = h->cg_chunk0;
+    for (;;) {
+        const i64 cnt = m > 0 ? std::min(chunk, itmax - enq) : 0;
+        {
+            ProfScope ps(h, TLPK_KC_SPMV);
+            for (i64 k = enq; k < enq + cnt; ++k) launches += launch_cg_iter(h->stream, h->d, h->cg, h->d_D, h->d_regD, k);
+        }
+        HIPCHK(h, hipGetLastError());
+        enq += cnt;
+        chunk = std::min(chunk * 2, h->cg_chunk_max);
+        HIPCHK(h, hipMemcpyAsync(h->cg_pin, h->cg.sc, sizeof(CgScalars), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipEventRecord(h->cg_ev, h->stream));
+        HIPCHK(h, hipEventSynchronize(h->cg_ev));
+        if (h->cg_pin->outcome != CG_RUNNING || enq >= itmax || m <= 0) break;
+    }
+    const CgScalars &sc = *h->cg_pin;
+    h->cg_iters = sc.iters; h->cg_iters_total += sc.iters; h->cg_converged = sc.outcome == CG_SOLVED ? 1 : 0;
+    if (!h->cg_converged) ++h->cg_unsolved;
+    h->cg_resid0 = sc.resid0; h->cg_resid = sc.resid; h->cg_launches = launches + 1;
+    if (sc.outcome == CG_RUNNING) {
+        solve_end(h);
+        h->last_error = "conjugate gradients: every iteration was enqueued and the outcome word is still unset";
+        return TLPK_INTERNAL;
+    }
+    {
+        ProfScope ps(h, TLPK_KC_SPMV);
+        if (m > 0) HIPCHK(h, hipMemcpyAsync(d_dy, h->cg.x, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
+        launch_dx(h->stream, h->d, h->d_D, dy, xd, dx, 0, 1);
+    }
+    return solve_end(h);
+}
+
 int tlpk_solve_local(tlpk_handle *h, const double *d_xip, const double *d_xid) {
     if (int g = refuse(h, true, R_DENSE, "tlpk_solve_local")) return g;
     return solve_local(h, solve_io(nullptr, nullptr, d_xip, d_xid));
@@ -1402,6 +1552,7 @@ int tlpk_solve_finish(tlpk_handle *h, double *d_dx, double *d_dy, const double *
 }
 
 int tlpk_solve_device(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
+    if (h && h->krylov) return krylov_solve(h, d_dx, d_dy, d_xip, d_xid);
     if (int g = sharded_needs_split(h, "tlpk_solve_device")) return g;
     const bool whole = h && h->sub.empty() && h->has_device && graph_usable_solve(h);
     int rc = solve_composed(h, solve_io(d_dx, d_dy, d_xip, d_xid), whole);
@@ -1488,7 +1639,7 @@ int tlpk_solve2_device(tlpk_handle *h, double *d_dx0, double *d_dy0, const doubl
     if (int g = refuse(h, d_dx0 && d_dy0 && d_xip0 && d_xid0 && d_dx1 && d_dy1 && d_xip1 && d_xid1, R_MULTI)) return g;
     if (int g = sharded_needs_split(h, "tlpk_solve2_device")) return g;
     if (int g = refuse(h, true, R_DEVICE | R_FACTORED)) return g;
-    if (h->refine_steps > 0 || !h->S.sweep) {            // refinement / launch-per-block schedule: two ordinary solves
+    if (h->refine_steps > 0 || !h->S.sweep || h->krylov) {            // refinement / launch-per-block schedule / matrix-free handle: two ordinary solves
         const int rc = tlpk_solve_device(h, d_dx0, d_dy0, d_xip0, d_xid0);
         return rc != TLPK_OK ? rc : tlpk_solve_device(h, d_dx1, d_dy1, d_xip1, d_xid1);
     }
@@ -1983,6 +2134,10 @@ int tlpk_create_multi(tlpk_handle **out, int64_t m, int64_t n, const int64_t *co
         g_create_error = "dense_cols: not on tlpk_create_multi handles";
         return TLPK_BADARG;
     }
+    if (uopt && uopt->struct_size == (int32_t)sizeof(tlpk_options) && uopt->krylov != TLPK_KRYLOV_NONE) {
+        g_create_error = "krylov: not on tlpk_create_multi handles (the matrix-free handle runs on one device)";
+        return TLPK_BADARG;
+    }
     if (!uopt || uopt->struct_size != (int32_t)sizeof(tlpk_options) || ngpus < 1 || ngpus > MAX_DEVICES ||
         (!uopt->row_block && !uopt->detect_blocks))
         return TLPK_BADARG;                              // block-angular LPs only (general sparse LPs stay single-GPU)
@@ -2320,6 +2475,12 @@ int tlpk_info(const tlpk_handle *h, tlpk_stats *out) {
     out->flops_syrk = S.flops_syrk;
     if (h->sv_pending && h->has_device && hipSetDevice(h->device) == hipSuccess) sv_time_take(const_cast<tlpk_handle *>(h));      // an enqueued refresh: its time once the events have completed
     out->ms_last_set_values = h->ms_set_values; out->set_values_bytes = h->set_values_bytes;
+    if (h->krylov) {
+        out->launches_update = 1 + (h->krylov_precond == TLPK_PRECOND_JACOBI ? 1 : 0);
+        out->launches_solve = h->cg_launches;                   // of the last solve: the number depends on the data
+        out->krylov_iters = h->cg_iters; out->krylov_iters_total = h->cg_iters_total; out->krylov_converged = h->cg_converged;
+        out->krylov_resid0 = h->cg_resid0; out->krylov_resid = h->cg_resid;
+    }
     return TLPK_OK;
 }
 
@@ -2401,6 +2562,7 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
     else if (w == "reduce_tasks") { for (auto &t : S.reduce_tasks) { tmp.push_back(t.front); tmp.push_back(t.k0); tmp.push_back(t.kw); tmp.push_back(t.i0); tmp.push_back(t.j0); tmp.push_back(t.jlim); tmp.push_back(t.beta0); tmp.push_back(t.pad1); } }
     else if (w == "chain_items") { for (auto &t : S.chain_items) { for (i32 v : {t.role, t.task, t.sub, t.w0, t.n0, t.need0, t.w1, t.n1, t.need1, t.w2, t.need2, t.sig}) tmp.push_back(v); } }
     else if (w == "chain_counters") tmp.assign(1, S.chain_counters);
+    else if (w == "krylov_unsolved") tmp.assign(1, h->cg_unsolved);         // matrix-free handles: solves since create that did NOT meet the stopping rule
     else if (w == "chain_retries") tmp.assign(1, h->chain_retries);           // updates of this handle that were replayed after a dependency-driven launch gave up waiting (tlpk_update)
     else if (w == "chain_trace") {                               // diagnostics: the time stamps of the last update (the caller has synchronised)
         if (!h->d.chain_trace) return -1;
@@ -2455,6 +2617,7 @@ int64_t tlpk_symbolic_get_f64(const tlpk_handle *h, const char *what, double *bu
 }
 
 int tlpk_get_factor(tlpk_handle *h, double *lval, int64_t cap) {
+    if (h && h->krylov) { h->last_error = "tlpk_get_factor: a matrix-free handle (tlpk_options.krylov) has no factor"; return TLPK_BADARG; }
     if (int g = refuse(h, lval != nullptr, R_MULTI | R_DEVICE)) return g;
     if (cap < h->S.lval_len) return TLPK_BADARG;
     HIPCHK(h, hipSetDevice(h->device));

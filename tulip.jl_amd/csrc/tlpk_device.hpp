@@ -125,6 +125,38 @@ void launch_dense_gemv_n(hipStream_t st, const DevArrays &a, const double *D, co
 // out[r] = D .* (A' y[r] - xi_d[r])  (D null: A' y[r]), r < nrhs <= 2: one pass over A
 void launch_dense_gemv_t(hipStream_t st, const DevArrays &a, const double *D, const double *const *y, const double *const *xi_d, double *const *out, int nrhs);
 
+// ---- matrix-free K1: conjugate gradients on (A D A' + Rd) dy = b (krylov_kernels.hip; DESIGN.md section 1b'''') ----
+// The scalars of a solve, in device memory: read by every kernel, written by ONE thread of the kernel that owns the field.  The host copies the block to
+// pinned memory after every chunk of iterations.
+struct CgScalars {
+    double gamma[2];      // r' M^-1 r, by parity of the iteration that READS it (iteration k reads gamma[k & 1] and writes gamma[(k + 1) & 1])
+    double tol;           // atol + rtol sqrt(gamma at x = 0)
+    double resid0, resid; // sqrt(gamma) at x = 0 / after the last completed iteration
+    double pq;            // the last p' S p
+    long long outcome;    // CG_RUNNING until a kernel decides; every kernel returns at once when it is set
+    long long iters;      // completed iterations
+    long long itmax;
+    long long pad[7];
+};
+static_assert(sizeof(CgScalars) == 128, "CgScalars layout");
+enum : long long { CG_RUNNING = 0, CG_SOLVED = 1, CG_ITMAX = 2, CG_BREAKDOWN = 3 };
+constexpr int CG_LONG = 512;        // a row / column with more entries gets a workgroup of its own (binned at create); shorter ones 8 / 4 lanes
+constexpr int CG_MAX_SLOTS = 256;   // workgroups (= partial sums) of the short rows / of the vector kernels
+constexpr int CG_MAX_LONG = 64;     // workgroups that share the long rows
+struct CgArrays {
+    CgScalars *sc = nullptr;
+    double *x = nullptr, *p = nullptr, *q = nullptr, *t = nullptr;
+    double *Minv = nullptr;                       // Jacobi: 1 / diag(A D A' + Rd); nullptr = no preconditioner
+    double *slots_r = nullptr, *slots_v = nullptr;   // partial sums of p'q (row kernel) and of r'z (vector kernels), one per workgroup, added in slot order by the consumer
+    i32 *long_rows = nullptr, *long_cols = nullptr; i64 n_long_rows = 0, n_long_cols = 0;
+    int g_rows = 0, g_long = 0, g_vec = 0;        // workgroups of the short rows, of the long rows, of the vector kernels
+};
+void launch_cg_jacobi(hipStream_t st, const DevArrays &a, const CgArrays &c, const double *D, const double *regD);
+// r (= a.ctx.xw) holds b: x = 0, p = M^-1 r, gamma, tolerance, outcome (a zero right-hand side is solved at once)
+void launch_cg_init(hipStream_t st, const DevArrays &a, const CgArrays &c, double atol, double rtol, i64 itmax);
+// iteration k (0-based) of the solve: four launches; returns their number
+int launch_cg_iter(hipStream_t st, const DevArrays &a, const CgArrays &c, const double *D, const double *regD, i64 k);
+
 // new values on an analysed pattern (refresh_kernels.hip): w[t] = value(a[t]) * value(b[t]); out[q] = value(src[q]); the strided copy of a dense A
 void launch_refresh_pairs(hipStream_t st, i64 np, const i32 *a, const i32 *b, const double *nz, double *w);
 void launch_refresh_gather(hipStream_t st, i64 n, const i32 *src, const double *nz, double *out);

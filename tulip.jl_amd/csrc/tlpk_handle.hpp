@@ -98,6 +98,15 @@ struct tlpk_handle {
     i64 set_values_bytes = 0;           // device memory of the maps (tlpk_stats.set_values_bytes)
     double ms_set_values = 0;           // tlpk_stats.ms_last_set_values
     hipEvent_t sv_ev0 = nullptr, sv_ev1 = nullptr; bool sv_pending = false;   // ... of an enqueued refresh: read when the events have completed
+    // matrix-free K1 (tlpk_options.krylov = TLPK_KRYLOV_CG; tlpk_api.cpp: krylov_*, krylov_kernels.hip): no factor, conjugate gradients per solve
+    int krylov = 0, krylov_precond = 0;
+    i64 krylov_itmax = 0; double krylov_atol = 0, krylov_rtol = 0;      // as resolved at create (0 -> 2 m, sqrt(eps))
+    CgArrays cg;
+    CgScalars *cg_pin = nullptr;        // pinned copy of the scalar block, read after every chunk of iterations
+    hipEvent_t cg_ev = nullptr;
+    i64 cg_chunk0 = 4, cg_chunk_max = 32;   // iterations enqueued before the first look at the outcome / at most between two looks (TLPK_CG_CHUNK=first,max)
+    i64 cg_iters = 0, cg_iters_total = 0, cg_converged = 0, cg_launches = 0, cg_unsolved = 0;
+    double cg_resid0 = 0, cg_resid = 0;
     std::string last_error;
 };
 

@@ -268,6 +268,9 @@ int analyse_dense(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowva
 // matrix without zeros, without forming the m (m + 1) / 2 entries of the pattern or the n m (m + 1) / 2 products of the assembly lists.  The
 // factorisation and solve schedules are those of build_schedule for that front; host memory O(m + schedule).  Needs only the shape of A.
 int analyse_dense_matrix(Symbolic &S, i64 m, i64 n);
+// Matrix-free handle (tlpk_options.krylov): the CSC and the row-wise copy of A in the caller's order, the identity as perm; no pattern of S,
+// no fronts, no lists, no schedules (every symbolic array stays empty, nnzS = nnzL = 0)
+int analyse_krylov(Symbolic &S, i64 m, i64 n, const i64 *colptr, const i64 *rowval, const double *nzval, int index_base);
 // New values on an analysed pattern (tlpk_set_values; symbolic.cpp: build_value_maps).  pair_a / pair_b: for product t of this rank's assembly lists the
 // positions in the caller's nzval of its two factors, pair_w[t] = value(pair_a[t]) * value(pair_b[t]) in this order; VM_ONE stands for the unit entry of an
 // incidence column (K2, dense columns), (VM_MINUS, VM_ONE) for the constant -1 of a variable / dense node's diagonal.  ax_src (K2 only: elsewhere Ax IS the

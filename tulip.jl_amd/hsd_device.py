@@ -10,6 +10,7 @@ lengths go in.  Tulip's defaults (/root/reference/src/IPM/options.jl:1-25); no p
     opt.optimize()
     opt.status, opt.niter, opt.primal_objective, opt.x(), opt.y()
 """
+import copy
 import ctypes as C
 import math
 import time
@@ -17,7 +18,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .kkt import K1, K2, Backend, DenseBackend, DimensionMismatch, OutOfMemoryError, PosDefException, _raise_for, setup
+from .kkt import K1, K2, Backend, DenseBackend, KrylovBackend, DimensionMismatch, OutOfMemoryError, PosDefException, _raise_for, setup
 
 SQRT_EPS = float(np.sqrt(np.finfo(np.float64).eps))
 INF = float("inf")
@@ -50,7 +51,20 @@ class DeviceHSD:
         if int(backend_kw.get("nranks", 1)) > 1:
             raise ValueError("the device-resident interior-point loops need one handle for the whole LP: nranks must be 1 "
                              "(ngpus > 1 is fine; sharded handles serve the split-phase KKT.update! / KKT.solve!)")
-        if dense:
+        # backend = KrylovBackend(...): the matrix-free handle (K1, one device) -- every KKT.solve! of the loop is a conjugate-gradient solve.
+        # device / profile / mem_budget_bytes beside it are the object's own fields and override them (Model(..., backend=..., device=1))
+        krylov = backend_kw.pop("backend", None)
+        if krylov is not None:
+            if not isinstance(krylov, KrylovBackend) or dense or set(backend_kw) - {"device", "profile", "mem_budget_bytes"}:
+                raise TypeError("backend=: a KrylovBackend; beside it only device, profile and mem_budget_bytes (its own fields)")
+            if backend_kw:
+                krylov = copy.copy(krylov)
+                for key, value in backend_kw.items():
+                    setattr(krylov, key, type(getattr(krylov, key))(value))
+            if str(system).upper() == "K2":
+                raise TypeError("the Krylov backend solves the normal equations (K1) only")
+            self.kkt = setup(A, K1(), krylov)
+        elif dense:
             if str(system).upper() == "K2":
                 raise TypeError("the dense backend solves the normal equations (K1) only")
             self.kkt = setup(A, K1(), DenseBackend(**backend_kw))

@@ -80,6 +80,31 @@ end
 DenseBackend(; device::Int=0, profile::Bool=false, mem_budget_bytes::Int=0) = DenseBackend(device, profile, mem_budget_bytes)
 
 """
+    KrylovBackend(; device=0, precond=:none, itmax=0, atol=0.0, rtol=0.0, profile=false, mem_budget_bytes=0)
+
+The matrix-free counterpart of `TlpKrylov.Backend(Krylov.CgSolver, ...)` with `KKT_System = K1()`
+(the reference's `src/KKT/Krylov/spd.jl`): nothing is analysed or factorised, every `solve!` runs conjugate gradients on
+`A·D·Aᵀ + Rd` on the device.  `precond`: `:none` (the reference) or `:jacobi`; `itmax = 0`: 2 m; `atol = rtol = 0`: `sqrt(eps)`.
+As in the reference (`spd.jl:100-101`), a solve that stops at `itmax` returns its last iterate without an error.
+
+    set_parameter(model, "KKT_Backend", Tulip.KKT.TlpHIP.KrylovBackend(precond=:jacobi))
+    set_parameter(model, "KKT_System",  Tulip.KKT.K1())
+"""
+struct KrylovBackend <: AbstractKKTBackend
+    device::Int
+    precond::Symbol
+    itmax::Int
+    atol::Float64
+    rtol::Float64
+    profile::Bool
+    mem_budget_bytes::Int
+end
+function KrylovBackend(; device::Int=0, precond::Symbol=:none, itmax::Int=0, atol::Real=0.0, rtol::Real=0.0, profile::Bool=false, mem_budget_bytes::Int=0)
+    precond in (:none, :jacobi) || throw(ArgumentError("precond: :none or :jacobi"))
+    return KrylovBackend(device, precond, itmax, Float64(atol), Float64(rtol), profile, mem_budget_bytes)
+end
+
+"""
     BlockAngularMatrix(A, row_block)
 
 Tulip's structured-matrix hook (`/root/reference/src/parameters.jl:11` `MatrixFactory`,
@@ -135,15 +160,16 @@ mutable struct HIPNormalEquations <: AbstractKKTSolver{Float64}
     n::Int
     A::Union{SparseMatrixCSC{Float64,Int},Matrix{Float64}}   # kept by reference like cholmod.jl:50 / lapack.jl:47; never mutated
     handle::Ptr{Cvoid}
+    method::String                 # "" (direct) | " CG" | " CG, Jacobi": appended to the backend name
 
     function HIPNormalEquations(m, n, A, handle)
-        kkt = new(m, n, A, handle)
+        kkt = new(m, n, A, handle, "")
         finalizer(k -> (k.handle == C_NULL || (LibTLPK.destroy(k.handle); k.handle = C_NULL)), kkt)
         return kkt
     end
 end
 
-backend(::HIPNormalEquations) = LibTLPK.backend_name()        # "HIP (gfx950)"
+backend(kkt::HIPNormalEquations) = LibTLPK.backend_name() * kkt.method        # "HIP (gfx950)", "HIP (gfx950) CG"
 linear_system(kkt::HIPNormalEquations) = LibTLPK.linear_system(kkt.handle)   # "Normal equations (K1)" | "Augmented system (K2)"
 
 # error-code -> exception mapping (SURVEY.md section 5, "Failure detection")
@@ -183,6 +209,19 @@ function setup(A::SparseMatrixCSC{Float64,Int}, system::Union{K1,K2}, b::Backend
     rc == LibTLPK.TLPK_OK || (h == C_NULL || LibTLPK.destroy(h); _check(rc, C_NULL, "KKT.setup"))
     return HIPNormalEquations(m, n, A, h)
 end
+
+# Matrix-free conjugate gradients (Krylov/spd.jl:52-63): K1 only
+function setup(A::SparseMatrixCSC{Float64,Int}, ::K1, b::KrylovBackend)
+    m, n = size(A)
+    rc, h = LibTLPK.create_krylov(m, n, A.colptr, A.rowval, A.nzval; device=b.device, precond=b.precond, itmax=b.itmax, atol=b.atol,
+                                  rtol=b.rtol, profile=b.profile, mem_budget_bytes=b.mem_budget_bytes)
+    rc == LibTLPK.TLPK_OK || (h == C_NULL || LibTLPK.destroy(h); _check(rc, C_NULL, "KKT.setup"))
+    kkt = HIPNormalEquations(m, n, A, h)
+    kkt.method = b.precond === :jacobi ? " CG, Jacobi" : " CG"
+    return kkt
+end
+setup(A::AbstractMatrix, system::K1, b::KrylovBackend) = setup(convert(SparseMatrixCSC{Float64,Int}, A), system, b)
+setup(::AbstractMatrix, ::K2, ::KrylovBackend) = throw(ArgumentError("TlpHIP.KrylovBackend solves the normal equations (K1) only"))
 
 # Dense constraint matrix (lapack.jl:52-63): the handle of tlpk_create_dense behaves like any single-device K1 handle
 function setup(A::Matrix{Float64}, ::K1, b::DenseBackend)

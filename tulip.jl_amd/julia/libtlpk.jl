@@ -24,6 +24,8 @@ end
 
 const TLPK_SYSTEM_K1 = Int32(0)
 const TLPK_SYSTEM_K2 = Int32(1)
+const TLPK_KRYLOV_NONE = Int32(0)
+const TLPK_KRYLOV_CG = Int32(1)
 
 # return codes (include/tlpk.h)
 const TLPK_OK = Cint(0)
@@ -57,6 +59,11 @@ Base.@kwdef mutable struct Options
     max_dense_cols::Int32 = 0    # cap on their number; 0 = 1024
     dense_col_min::Int64 = 0     # 0 = 1000
     col_dense::Ptr{Int64} = C_NULL
+    krylov::Int32 = 0            # TLPK_KRYLOV_NONE | TLPK_KRYLOV_CG: matrix-free conjugate gradients on the normal equations (K1)
+    krylov_precond::Int32 = 0    # 0 = none | 1 = Jacobi
+    krylov_itmax::Int64 = 0      # 0 = 2 m
+    krylov_atol::Float64 = 0.0   # 0 = sqrt(eps)
+    krylov_rtol::Float64 = 0.0
 end
 
 strerror(code::Integer) = unsafe_string(ccall((:tlpk_strerror, libtlpk[]), Cstring, (Cint,), code))
@@ -129,6 +136,32 @@ function create_dense(A::Matrix{Float64}; device::Integer=0, profile::Bool=false
     rc = GC.@preserve A opt ccall((:tlpk_create_dense, libtlpk[]), Cint,
         (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Float64}, Int64, Ref{Options}),
         h, m, n, A, max(m, 1), opt)
+    return rc, h[]
+end
+
+"""
+    create_krylov(m, n, colptr, rowval, nzval; device, precond, itmax, atol, rtol, profile, mem_budget_bytes) -> (rc, Ptr{Cvoid})
+
+`tlpk_create` with `krylov = TLPK_KRYLOV_CG`: no analysis, no factor; every solve runs conjugate gradients on the device.
+`precond`: `:none` or `:jacobi`.
+"""
+function create_krylov(m::Int, n::Int, colptr::Vector{Int}, rowval::Vector{Int}, nzval::Vector{Float64};
+                       device::Integer=0, precond::Symbol=:none, itmax::Integer=0, atol::Real=0.0, rtol::Real=0.0,
+                       profile::Bool=false, mem_budget_bytes::Integer=0)
+    opt = Options()
+    opt.struct_size = Int32(sizeof(Options))
+    opt.device = Int32(device)
+    opt.profile = Int32(profile)
+    opt.mem_budget_bytes = Int64(mem_budget_bytes)
+    opt.krylov = TLPK_KRYLOV_CG
+    opt.krylov_precond = Int32(precond === :jacobi)
+    opt.krylov_itmax = Int64(itmax)
+    opt.krylov_atol = Float64(atol)
+    opt.krylov_rtol = Float64(rtol)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = GC.@preserve colptr rowval nzval opt ccall((:tlpk_create, libtlpk[]), Cint,
+        (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint, Ref{Options}),
+        h, m, n, colptr, rowval, nzval, 1, opt)
     return rc, h[]
 end
 

@@ -42,7 +42,23 @@ class OutOfMemoryError(MemoryError):
     """Julia's OutOfMemoryError -> Trm_MemoryLimit (/root/reference/src/IPM/HSD/HSD.jl:327-329)."""
 
 
-class Backend:
+class _BackendOptions:
+    """What the shared code of the solver objects (HIPNormalEquations, HIPDenseNormalEquations) and the test tools read from any
+    backend object, with the value that means "not used".  A backend class sets what it offers; a field that one of them grows gets
+    its default here, so that the others keep working."""
+
+    device = 0
+    profile = False
+    mem_budget_bytes = 0
+    ordering, relax = _lib.ORDER_AMD, True
+    rank, nranks, ngpus, devices = 0, 1, 1, None
+    streams, refine = 0, 0
+    row_block = user_perm = None
+    detect_blocks, max_link_rows = False, 0
+    dense_cols, max_dense_cols, dense_col_min = None, 0, 0
+
+
+class Backend(_BackendOptions):
     """`TlpHIP.Backend`: selects the HIP solver, the analogue of `TlpCholmod.Backend`
     (/root/reference/src/KKT/Cholmod/cholmod.jl:18).
 
@@ -86,7 +102,7 @@ class Backend:
         self.dense_col_min = int(dense_col_min)
 
 
-class DenseBackend:
+class DenseBackend(_BackendOptions):
     """`TlpHIP.DenseBackend`: the analogue of `TlpDense.Backend` (/root/reference/src/KKT/Dense/lapack.jl:17) -- `A` is a dense
     matrix, `A*D*A' + Rd` is formed on the fp64 matrix cores into one dense front and factorised by the blocked dense
     Cholesky of the sparse handles.  K1 only, one GPU; no pattern of `A*D*A'` and no assembly lists are built."""
@@ -95,9 +111,23 @@ class DenseBackend:
         self.device = int(device)
         self.profile = bool(profile)
         self.mem_budget_bytes = int(mem_budget_bytes)
-        # what the shared code of HIPNormalEquations and the test tools read from a backend object
-        self.rank, self.nranks, self.ngpus = 0, 1, 1
-        self.refine = 0
+
+
+class KrylovBackend(_BackendOptions):
+    """`TlpHIP.KrylovBackend`: the analogue of `TlpKrylov.Backend` with `Krylov.CgSolver` (the reference's src/KKT/Krylov/spd.jl) --
+    no analysis and no factor: every solve runs conjugate gradients on `A*D*A' + Rd` on the device, matrix-free.  K1 only, one GPU.
+    precond: None (the reference) or "jacobi" (the diagonal of `A*D*A' + Rd`, rebuilt by every update); itmax = 0: 2 m; atol = rtol = 0:
+    sqrt(eps).  A solve that stops at `itmax` still returns its last iterate, as the reference does: `stats()["krylov_converged"]` tells."""
+
+    def __init__(self, device=0, precond=None, itmax=0, atol=0.0, rtol=0.0, profile=False, mem_budget_bytes=0):
+        if precond not in (None, "none", "jacobi"):
+            raise ValueError("precond: None or 'jacobi'")
+        self.device = int(device)
+        self.precond = _lib.PRECOND_JACOBI if precond == "jacobi" else _lib.PRECOND_NONE
+        self.itmax = int(itmax)
+        self.atol, self.rtol = float(atol), float(rtol)
+        self.profile = bool(profile)
+        self.mem_budget_bytes = int(mem_budget_bytes)
 
 
 def detect_blocks(A, max_link_rows=0):
@@ -154,8 +184,8 @@ class HIPNormalEquations:
         opt.mem_budget_bytes = backend_.mem_budget_bytes
         opt.streams = backend_.streams
         opt.refine_steps = backend_.refine
-        opt.detect_blocks = int(getattr(backend_, "detect_blocks", False))
-        opt.max_link_rows = int(getattr(backend_, "max_link_rows", 0))
+        opt.detect_blocks = int(backend_.detect_blocks)
+        opt.max_link_rows = int(backend_.max_link_rows)
         opt.system = system
         self.system = system
         self._keep = []
@@ -167,7 +197,14 @@ class HIPNormalEquations:
         if backend_.user_perm is not None:
             opt.user_perm = _lib.as_p64(backend_.user_perm)
             self._keep.append(backend_.user_perm)
-        dense = getattr(backend_, "dense_cols", None)
+        if isinstance(backend_, KrylovBackend):
+            if system != _lib.SYSTEM_K1:
+                raise TypeError("the Krylov backend solves the normal equations (K1) only")
+            opt.krylov = _lib.KRYLOV_CG
+            opt.krylov_precond = backend_.precond
+            opt.krylov_itmax = backend_.itmax
+            opt.krylov_atol, opt.krylov_rtol = backend_.atol, backend_.rtol
+        dense = backend_.dense_cols
         if dense is not None:
             opt.dense_cols = 1
             opt.max_dense_cols = backend_.max_dense_cols
@@ -455,7 +492,11 @@ def arithmetic(kkt):
 
 def backend(kkt):
     """KKT.backend (KKT.jl:114) -- printed in the IPM log banner (HSD.jl:227-229)."""
-    return _lib.lib().tlpk_backend_name().decode()
+    name = _lib.lib().tlpk_backend_name().decode()
+    be = getattr(kkt, "backend_options", None)
+    if isinstance(be, KrylovBackend):                  # the method, as Krylov's `backend` names its solver type (src/KKT/Krylov/spd.jl:48)
+        name += " CG" + (", Jacobi" if be.precond == _lib.PRECOND_JACOBI else "")
+    return name
 
 
 def linear_system(kkt):
