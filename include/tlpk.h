@@ -46,7 +46,8 @@ typedef struct tlpk_handle tlpk_handle;
 
 /* tlpk_options.krylov */
 #define TLPK_KRYLOV_NONE 0
-#define TLPK_KRYLOV_CG 1
+#define TLPK_KRYLOV_CG 1        /* K1: conjugate gradients on the normal equations */
+#define TLPK_KRYLOV_MINRES 16   /* K2: MINRES on the augmented system.  The K2 methods start at 16; 2 - 15 and every other value: TLPK_BADARG */
 #define TLPK_PRECOND_NONE 0
 #define TLPK_PRECOND_JACOBI 1
 
@@ -92,9 +93,11 @@ typedef struct tlpk_options {
                                   like row_block, only meaningful on the matrix the caller analyses (no presolve in between) */
     /* Matrix-free handle (the reference's Krylov family, src/KKT/Krylov/spd.jl): no analysis, no factor, O(nnz(A) + m + n) device memory.  See tlpk_create. */
     int32_t krylov;            /* TLPK_KRYLOV_NONE 0 (default: analyse + factorise) | TLPK_KRYLOV_CG 1: K1, conjugate gradients on
-                                  (A D A' + Rd) dy = xi_p + A D xi_d, matrix-free (src/KKT/Krylov/spd.jl) */
-    int32_t krylov_precond;    /* 0 = none (the reference) | 1 = Jacobi: M = diag(A D A' + Rd), rebuilt by every update */
-    int64_t krylov_itmax;      /* 0 = 2 m (Krylov.jl's default) */
+                                  (A D A' + Rd) dy = xi_p + A D xi_d, matrix-free (src/KKT/Krylov/spd.jl) | TLPK_KRYLOV_MINRES 16: K2 (system must be
+                                  TLPK_SYSTEM_K2), MINRES on [-E A'; A Rd] [dx; dy] = [xi_d; xi_p], E = theta^-1 + Rp (src/KKT/Krylov/sid.jl) */
+    int32_t krylov_precond;    /* 0 = none (the reference) | 1 = Jacobi, rebuilt by every update: CG: M = diag(A D A' + Rd); MINRES: the positive
+                                  definite block diagonal M = diag(E_j, sum_{E_j > 0} A_ij^2 / E_j + Rd_i) */
+    int64_t krylov_itmax;      /* 0 = twice the order of the system (Krylov.jl's default): 2 m for CG, 2 (m + n) for MINRES */
     double  krylov_atol, krylov_rtol;   /* 0 = sqrt(eps) (spd.jl:66-67); < 0 or non-finite: TLPK_BADARG */
 } tlpk_options;
 
@@ -136,10 +139,10 @@ typedef struct tlpk_stats {
                                   (2 per product); 0 on sparse handles */
     /* matrix-free handles (tlpk_options.krylov); 0 on every other handle.  (Placed in front of the tlpk_set_values pair, which stays the tail of the struct;
        tlpk_stats carries no size field, so any new field means a rebuild of the callers wherever it goes.) */
-    int64_t krylov_iters;        /* CG iterations of the last solve */
+    int64_t krylov_iters;        /* CG / MINRES iterations of the last solve */
     int64_t krylov_iters_total;  /* since the last update */
     int64_t krylov_converged;    /* 1 = the last solve met the stopping rule; 0 = it stopped at itmax or broke down */
-    double  krylov_resid0, krylov_resid;   /* sqrt(r' M^-1 r) at x = 0 and at exit of the last solve */
+    double  krylov_resid0, krylov_resid;   /* sqrt(r' M^-1 r) at x = 0 and at exit of the last solve (MINRES: beta1 and phibar, the recurrence's value of it) */
                                  /* tlpk_symbolic_get(h, "krylov_unsolved"): one entry, the number of solves since create that did NOT meet the stopping
                                     rule (what a loop of many solves checks once at its end instead of reading krylov_converged after every solve) */
     double  ms_last_set_values; /* device time of the last tlpk_set_values* (HIP events on the handle's stream; multi-device handles: the slowest shard);
@@ -178,7 +181,7 @@ int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr,
 /* Matrix-free handle: opt->krylov = TLPK_KRYLOV_CG (K1; the reference's src/KKT/Krylov/spd.jl).  tlpk_create then skips ordering, the pattern of S,
  * supernodes, lists and schedules and keeps only the CSC and the row-wise copy of A in the caller's order: tlpk_stats nnzS = nnzL = nnzL_stored = n_pairs =
  * n_supernodes = 0, flops_* = 0, tlpk_get_perm = the identity, every symbolic array empty, tlpk_get_factor: TLPK_BADARG.  The memory gate counts the copies of A
- * and the vectors.  TLPK_BADARG (sentence in tlpk_last_create_error()): system = K2, nranks > 1, dense_cols, refine_steps > 0, user_perm, an unknown krylov /
+ * and the vectors.  TLPK_BADARG (sentence in tlpk_last_create_error()): system = K2 (TLPK_KRYLOV_CG), nranks > 1, dense_cols, refine_steps > 0, user_perm, an unknown krylov /
  * krylov_precond value, krylov_itmax < 0, a negative or non-finite tolerance; tlpk_create_multi and tlpk_create_dense refuse the option.  row_block,
  * detect_blocks, ordering, relax and streams are ignored.  device = -1: an analyse-only handle (numeric calls: TLPK_NO_DEVICE).  The split-phase calls
  * (tlpk_*_local / tlpk_*_finish, tlpk_root_*, tlpk_refine_*) do not apply: TLPK_BADARG.
@@ -193,6 +196,18 @@ int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr,
  *            is known (iterations are enqueued in chunks, the host reads the outcome word between chunks); dx / dy are complete after tlpk_sync as usual.
  *            tlpk_solve2_device is two solves.  Two solves of the same data are bit-identical (no atomics, ordered reductions).
  *   tlpk_set_values* refreshes the copies of A; the device-resident loops (tlpk_ipm_*, tlpk_mpc_*) run through the same solve path.
+ * opt->krylov = TLPK_KRYLOV_MINRES with opt->system = TLPK_SYSTEM_K2 (the reference's src/KKT/Krylov/sid.jl) is the same handle -- the same analysis, refusals,
+ * identity permutation (of the n + m nodes of K2: tlpk_get_perm writes n + m entries, as on a direct K2 handle), tlpk_set_values*, loops, blocking solve, chunked enqueue and stats fields -- with preconditioned MINRES (Paige & Saunders) on the
+ * augmented system of order n + m.  system = K1 with it, and TLPK_KRYLOV_CG with K2, are TLPK_BADARG.  tlpk_linear_system: "Augmented system (K2)".
+ *   update : E = theta^-1 + Rp and Rd are kept; 1 / E is never formed outside the preconditioner, so columns with E_j = 0 (free variables without
+ *            regularisation) and Rd = 0 are fine as long as K is nonsingular.  Jacobi: M = diag(E_j, s_i), s_i = sum_{j: E_j > 0} A_ij^2 / E_j + Rd_i, in one pass
+ *            over the rows; an entry of M that is 0 is replaced by 1.  Never TLPK_NOT_POSDEF.
+ *   solve  : K [dx; dy] = [xi_d; xi_p], K = [-E A'; A Rd] (KKT.jl:70-75), from x = 0.  Lanczos with z = M^-1 r, beta = sqrt(r'z), one Givens rotation per step;
+ *            phibar is the recurrence's sqrt(r' M^-1 r).  SOLVED when phibar <= atol + rtol beta1 (a zero right-hand side: in 0 iterations); NOT solved after
+ *            krylov_itmax iterations (0 = 2 (m + n)), when r'z < 0 or a scalar is not finite, or when beta = 0 (the Krylov space is exhausted) with phibar
+ *            still above the tolerance.  This is the only stopping rule: Krylov.jl's minres may have others (a test on ||A r||, a condition-number limit) that
+ *            could not be compared.  As above, a solve that is NOT solved writes its last iterate and returns TLPK_OK (sid.jl:100-104).
+ *            launches_solve = 2 + 3 per enqueued iteration.
  * What to expect: conjugate gradients without a preconditioner (the reference: spd.jl:26 "TODO: preconditioner") or with Jacobi solve the early, well-conditioned
  * systems of an interior-point run in tens of iterations and stall on the late ones (DESIGN.md section 1b has the measured limits). */
 /* Dense constraint matrix (the reference's dense backend, src/KKT/Dense/lapack.jl; K1 only).  A: m x n, column-major, leading dimension

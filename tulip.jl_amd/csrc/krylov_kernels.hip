@@ -18,43 +18,16 @@
 
 #include <algorithm>
 
+#include "krylov_reduce.hpp"
 #include "tlpk_device.hpp"
 
 namespace tlpk {
 
 namespace {
 
-constexpr int CG_THREADS = 256;
 constexpr int CG_ROW_THREADS = 1024;    // k_cg_rows: its workgroups are capped at CG_MAX_SLOTS (one partial sum each), so each is as large as it can be
 
-// sum over the workgroup (T threads), the same on every thread: shuffle tree inside a wave, then the waves in wave order
-template <int T = CG_THREADS>
-__device__ __forceinline__ double cg_block_sum(double v, double *sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) s += sh[w];
-    __syncthreads();
-    return s;
-}
-// the partial sums of the producing kernel, added in slot order; every thread forms the same sum.  The slots come into LDS with one coalesced load
-// per thread first: read one by one from global memory, the 256 dependent loads of a large problem cost more than the kernel's own work
-// (measured: 35 ns per slot, 15 of 43 us per iteration on eight C4 blocks).
 constexpr int CG_SLOTS_LDS = CG_MAX_SLOTS + CG_MAX_LONG;
-__device__ __forceinline__ double cg_sum_slots(const double *__restrict__ slots, int ns, double *shs) {
-    for (int k = threadIdx.x; k < ns; k += blockDim.x) shs[k] = slots[k];
-    __syncthreads();
-    double s = 0.0;
-    for (int k = 0; k < ns; ++k) s += shs[k];
-    return s;
-}
-
-// an empty row with Rd_i = 0 has M_i = 0: it keeps M^-1_i = 1 (no scaling), so that z = M^-1 r stays finite and the solve behaves as without Jacobi
-__device__ __forceinline__ double cg_minv(double M) { return M == 0.0 ? 1.0 : 1.0 / M; }
-
 // M_i = sum_j A_ij^2 D_j + Rd_i, stored inverted.  Blocks [0, gs): 8 lanes per row; blocks behind: one long row each.
 __global__ __launch_bounds__(CG_THREADS) void k_cg_jacobi(i64 m, const i64 *__restrict__ Tp, const i32 *__restrict__ Tj, const double *__restrict__ Tx,
                                                           const double *__restrict__ D, const double *__restrict__ regD, double *__restrict__ Minv,

@@ -527,7 +527,12 @@ int tlpk_host_copy_threads(void) { return host_copy_threads(); }
 
 // ---- matrix-free K1 (tlpk_options.krylov): set-up ----
 // device memory of such a handle: the CSC copy of A and two row-wise copies (36 nnz), the vectors of every handle and of the iteration
-static double krylov_bytes(const tlpk_handle *h) { return 36.0 * (double)h->S.nnzA + 80.0 * (double)h->S.n + 136.0 * (double)h->S.m + 65536.0; }
+static double krylov_bytes(const tlpk_handle *h) {
+    // MINRES on K2: the same copies of A and vectors of every handle (72 n + 104 m), and nine vectors of order n + m (r1, r2, their two preconditioned
+    // copies, u, w1, w2, x, the inverted block diagonal) where conjugate gradients keep four of order m and one of order n
+    if (h->krylov == TLPK_KRYLOV_MINRES) return 36.0 * (double)h->S.nnzA + 144.0 * (double)h->S.n + 176.0 * (double)h->S.m + 65536.0;
+    return 36.0 * (double)h->S.nnzA + 80.0 * (double)h->S.n + 136.0 * (double)h->S.m + 65536.0;
+}
 // the options of a matrix-free handle: nullptr, or the sentence that says what is wrong
 // the memory gate of a matrix-free handle, with or without a device
 static int krylov_gate(tlpk_handle *h, double budget) {
@@ -539,12 +544,15 @@ static int krylov_gate(tlpk_handle *h, double budget) {
 }
 
 static const char *krylov_check(const tlpk_options &def) {
-    if (def.krylov != TLPK_KRYLOV_CG) return "krylov: TLPK_KRYLOV_NONE (0) or TLPK_KRYLOV_CG (1)";
+    if (def.krylov != TLPK_KRYLOV_CG && def.krylov != TLPK_KRYLOV_MINRES) return "krylov: TLPK_KRYLOV_NONE (0), TLPK_KRYLOV_CG (1) or TLPK_KRYLOV_MINRES (16)";
     if (def.krylov_precond != TLPK_PRECOND_NONE && def.krylov_precond != TLPK_PRECOND_JACOBI) return "krylov_precond: 0 (none) or 1 (Jacobi)";
-    if (def.krylov_itmax < 0) return "krylov_itmax: >= 0 (0 = 2 m)";
+    if (def.krylov_itmax < 0) return "krylov_itmax: >= 0 (0 = 2 m; MINRES: 2 (m + n))";
     if (!(def.krylov_atol >= 0.0) || !std::isfinite(def.krylov_atol) || !(def.krylov_rtol >= 0.0) || !std::isfinite(def.krylov_rtol))
         return "krylov_atol, krylov_rtol: finite and >= 0 (0 = sqrt(eps))";
-    if (def.system != TLPK_SYSTEM_K1) return "krylov: K1 only (conjugate gradients need the positive definite normal equations; MINRES / TriCG on K2 are not implemented)";
+    if (def.krylov == TLPK_KRYLOV_CG && def.system != TLPK_SYSTEM_K1)
+        return "krylov: TLPK_KRYLOV_CG is K1 only (conjugate gradients need the positive definite normal equations; TLPK_KRYLOV_MINRES solves K2)";
+    if (def.krylov == TLPK_KRYLOV_MINRES && def.system != TLPK_SYSTEM_K2)
+        return "krylov: TLPK_KRYLOV_MINRES is K2 only (system = TLPK_SYSTEM_K2; TLPK_KRYLOV_CG solves K1)";
     if (def.nranks > 1 || def.rank != 0) return "krylov: one rank only (nranks = 1)";
     if (def.dense_cols) return "krylov: dense_cols does not apply (A*D*A' is never formed)";
     if (def.refine_steps != 0) return "krylov: refine_steps > 0 is not supported";
@@ -563,16 +571,38 @@ static int krylov_upload(tlpk_handle *h) {
     int rc;
     if ((rc = dev_upload(h, &c.long_rows, lr)) != TLPK_OK) return rc;
     if ((rc = dev_upload(h, &c.long_cols, lc)) != TLPK_OK) return rc;
-    c.g_rows = (int)std::max<i64>(1, std::min<i64>((m * 8 + 1023) / 1024, CG_MAX_SLOTS));      // (k_cg_rows: 1024 threads, 8 lanes per row)
-    c.g_long = (int)std::min<i64>(c.n_long_rows, CG_MAX_LONG);
-    c.g_vec = (int)std::max<i64>(1, std::min<i64>((m + 255) / 256, CG_MAX_SLOTS));
-    if ((rc = dev_alloc(h, &c.x, m)) != TLPK_OK || (rc = dev_alloc(h, &c.p, m)) != TLPK_OK || (rc = dev_alloc(h, &c.q, m)) != TLPK_OK ||
-        (rc = dev_alloc(h, &c.t, n)) != TLPK_OK || (rc = dev_alloc(h, &c.slots_r, c.g_rows + c.g_long)) != TLPK_OK ||
-        (rc = dev_alloc(h, &c.slots_v, c.g_vec)) != TLPK_OK || (rc = dev_alloc(h, &c.sc, 1)) != TLPK_OK) return rc;
-    if (h->krylov_precond == TLPK_PRECOND_JACOBI && (rc = dev_alloc(h, &c.Minv, m)) != TLPK_OK) return rc;
-    HIPCHK(h, hipMemset(c.sc, 0, sizeof(CgScalars)));
-    HIPCHK(h, hipHostMalloc((void **)&h->cg_pin, sizeof(CgScalars), hipHostMallocDefault));
-    std::memset(h->cg_pin, 0, sizeof(CgScalars));
+    if (h->krylov == TLPK_KRYLOV_MINRES) {
+        // k_mr_op: 1024 threads, 4 lanes per column and 8 per row; at most CG_MAX_SLOTS workgroups of either kind, CG_MAX_LONG share the long ones
+        MrArrays &r = h->mr;
+        const i64 N = n + m;
+        r.long_rows = c.long_rows; r.long_cols = c.long_cols; r.n_long_rows = c.n_long_rows; r.n_long_cols = c.n_long_cols;
+        r.g_cols = n > 0 ? (int)std::min<i64>((n * 4 + 1023) / 1024, CG_MAX_SLOTS) : 0;
+        r.g_rows = m > 0 ? (int)std::min<i64>((m * 8 + 1023) / 1024, CG_MAX_SLOTS) : 0;
+        r.g_lcols = (int)std::min<i64>(r.n_long_cols, CG_MAX_LONG);
+        r.g_lrows = (int)std::min<i64>(r.n_long_rows, CG_MAX_LONG);
+        r.g_vec = (int)std::max<i64>(1, std::min<i64>((N + 255) / 256, CG_MAX_SLOTS));
+        const bool jac = h->krylov_precond == TLPK_PRECOND_JACOBI;
+        if ((rc = dev_alloc(h, &r.r[0], N)) != TLPK_OK || (rc = dev_alloc(h, &r.r[1], N)) != TLPK_OK || (rc = dev_alloc(h, &r.u, N)) != TLPK_OK ||
+            (rc = dev_alloc(h, &r.x, N)) != TLPK_OK || (rc = dev_alloc(h, &r.w[0], N)) != TLPK_OK || (rc = dev_alloc(h, &r.w[1], N)) != TLPK_OK ||
+            (rc = dev_alloc(h, &r.slots_a, std::max(1, r.g_cols + r.g_rows + r.g_lcols + r.g_lrows))) != TLPK_OK ||
+            (rc = dev_alloc(h, &r.slots_g, r.g_vec)) != TLPK_OK || (rc = dev_alloc(h, &r.sc, 1)) != TLPK_OK) return rc;
+        if (jac && ((rc = dev_alloc(h, &r.z[0], N)) != TLPK_OK || (rc = dev_alloc(h, &r.z[1], N)) != TLPK_OK || (rc = dev_alloc(h, &r.Minv, N)) != TLPK_OK)) return rc;
+        if (!jac) { r.z[0] = r.r[0]; r.z[1] = r.r[1]; }
+        HIPCHK(h, hipMemset(r.sc, 0, sizeof(MrScalars)));
+        HIPCHK(h, hipHostMalloc((void **)&h->mr_pin, sizeof(MrScalars), hipHostMallocDefault));
+        std::memset(h->mr_pin, 0, sizeof(MrScalars));
+    } else {
+        c.g_rows = (int)std::max<i64>(1, std::min<i64>((m * 8 + 1023) / 1024, CG_MAX_SLOTS));      // (k_cg_rows: 1024 threads, 8 lanes per row)
+        c.g_long = (int)std::min<i64>(c.n_long_rows, CG_MAX_LONG);
+        c.g_vec = (int)std::max<i64>(1, std::min<i64>((m + 255) / 256, CG_MAX_SLOTS));
+        if ((rc = dev_alloc(h, &c.x, m)) != TLPK_OK || (rc = dev_alloc(h, &c.p, m)) != TLPK_OK || (rc = dev_alloc(h, &c.q, m)) != TLPK_OK ||
+            (rc = dev_alloc(h, &c.t, n)) != TLPK_OK || (rc = dev_alloc(h, &c.slots_r, c.g_rows + c.g_long)) != TLPK_OK ||
+            (rc = dev_alloc(h, &c.slots_v, c.g_vec)) != TLPK_OK || (rc = dev_alloc(h, &c.sc, 1)) != TLPK_OK) return rc;
+        if (h->krylov_precond == TLPK_PRECOND_JACOBI && (rc = dev_alloc(h, &c.Minv, m)) != TLPK_OK) return rc;
+        HIPCHK(h, hipMemset(c.sc, 0, sizeof(CgScalars)));
+        HIPCHK(h, hipHostMalloc((void **)&h->cg_pin, sizeof(CgScalars), hipHostMallocDefault));
+        std::memset(h->cg_pin, 0, sizeof(CgScalars));
+    }
     HIPCHK(h, hipEventCreateWithFlags(&h->cg_ev, hipEventDisableTiming));
     if (const char *e = std::getenv("TLPK_CG_CHUNK")) {
         long long a = 0, b = 0;
@@ -791,7 +821,8 @@ int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr, 
     int rc = TLPK_OK;
     if (def.krylov != TLPK_KRYLOV_NONE) {
         h->krylov = def.krylov; h->krylov_precond = def.krylov_precond;
-        h->krylov_itmax = def.krylov_itmax > 0 ? def.krylov_itmax : 2 * std::max<int64_t>(m, 0);
+        h->krylov_itmax = def.krylov_itmax > 0 ? def.krylov_itmax
+                        : 2 * (std::max<int64_t>(m, 0) + (def.krylov == TLPK_KRYLOV_MINRES ? std::max<int64_t>(n, 0) : 0));      // Krylov.jl: twice the order of the system
         const double se = std::sqrt(std::numeric_limits<double>::epsilon());
         h->krylov_atol = def.krylov_atol > 0.0 ? def.krylov_atol : se;
         h->krylov_rtol = def.krylov_rtol > 0.0 ? def.krylov_rtol : se;
@@ -905,6 +936,7 @@ void tlpk_destroy(tlpk_handle *h) {
         if (h->pin_in) hipHostFree(h->pin_in);
         if (h->pin_out) hipHostFree(h->pin_out);
         if (h->cg_pin) hipHostFree(h->cg_pin);
+        if (h->mr_pin) hipHostFree(h->mr_pin);
         if (h->cg_ev) hipEventDestroy(h->cg_ev);
         for (hipEvent_t e : h->io_events) hipEventDestroy(e);
         for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
@@ -1169,8 +1201,15 @@ static int update_async_wait(tlpk_handle *h) {
 // update: D = 1 / (theta^-1 + Rp) and, with Jacobi, the inverted diagonal of S; there is no factor that could fail
 static int krylov_update(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
     if (int rc = update_begin(h, d_theta, d_regP, d_regD)) return rc;
-    { ProfScope ps(h, TLPK_KC_ASSEMBLE); launch_compute_d(h->stream, h->S.n, h->d_theta, h->d_regP, h->d_D); }
-    if (h->cg.Minv) { ProfScope ps(h, TLPK_KC_SPMV); launch_cg_jacobi(h->stream, h->d, h->cg, h->d_D, h->d_regD); }
+    if (h->krylov == TLPK_KRYLOV_MINRES) {
+        // d_D holds E = theta^-1 + Rp, NOT its inverse: a column with E_j = 0 (a free variable without regularisation) is as good as any other
+        ProfScope ps(h, TLPK_KC_SPMV);
+        launch_mr_diag(h->stream, h->S.n, h->d_theta, h->d_regP, h->d_D);
+        launch_mr_jacobi(h->stream, h->d, h->mr, h->d_D, h->d_regD);
+    } else {
+        { ProfScope ps(h, TLPK_KC_ASSEMBLE); launch_compute_d(h->stream, h->S.n, h->d_theta, h->d_regP, h->d_D); }
+        if (h->cg.Minv) { ProfScope ps(h, TLPK_KC_SPMV); launch_cg_jacobi(h->stream, h->d, h->cg, h->d_D, h->d_regD); }
+    }
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
@@ -1491,7 +1530,46 @@ static int solve_composed(tlpk_handle *h, const SolveIo &io, bool whole) {
     return solve_whole(h, io);
 }
 
-// ---- matrix-free K1 (tlpk_options.krylov) ----
+// ---- matrix-free K1 / K2 (tlpk_options.krylov) ----
+// MINRES on K2: b = [xi_d; xi_p] (KKT.jl:70-75, what the reference's run_ls_tests checks; src/KKT/Krylov/sid.jl:96-97 packs [xi_p; xi_d] against an operator
+// ordered [n; m], which its all-ones fixture cannot tell apart -- the system of KKT.jl is the one solved here).  The same chunked enqueue as conjugate
+// gradients; launches: 2 (init) + 3 per enqueued iteration; dx = x[0:n], dy = x[n:n+m] are two device copies behind the last chunk.
+static int minres_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
+    const i64 m = h->S.m, n = h->S.n, N = m + n, itmax = h->krylov_itmax;
+    i64 launches = 2;
+    { ProfScope ps(h, TLPK_KC_SPMV); launch_mr_init(h->stream, h->d, h->mr, d_xip, d_xid, h->krylov_atol, h->krylov_rtol, itmax); }
+    i64 enq = 0, chunk = h->cg_chunk0;
+    for (;;) {
+        const i64 cnt = N > 0 ? std::min(chunk, itmax - enq) : 0;
+        {
+            ProfScope ps(h, TLPK_KC_SPMV);
+            for (i64 k = enq; k < enq + cnt; ++k) launches += launch_mr_iter(h->stream, h->d, h->mr, h->d_D, h->d_regD, k);
+        }
+        HIPCHK(h, hipGetLastError());
+        enq += cnt;
+        chunk = std::min(chunk * 2, h->cg_chunk_max);
+        HIPCHK(h, hipMemcpyAsync(h->mr_pin, h->mr.sc, sizeof(MrScalars), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipEventRecord(h->cg_ev, h->stream));
+        HIPCHK(h, hipEventSynchronize(h->cg_ev));
+        if (h->mr_pin->outcome != CG_RUNNING || enq >= itmax || N <= 0) break;
+    }
+    const MrScalars &sc = *h->mr_pin;
+    h->cg_iters = sc.iters; h->cg_iters_total += sc.iters; h->cg_converged = mr_outcome(sc) == CG_SOLVED ? 1 : 0;
+    if (!h->cg_converged) ++h->cg_unsolved;
+    h->cg_resid0 = sc.resid0; h->cg_resid = sc.resid; h->cg_launches = launches;
+    if (sc.outcome == CG_RUNNING) {
+        solve_end(h);
+        h->last_error = "MINRES: every iteration was enqueued and the outcome word is still unset";
+        return TLPK_INTERNAL;
+    }
+    {
+        ProfScope ps(h, TLPK_KC_SPMV);
+        if (n > 0) HIPCHK(h, hipMemcpyAsync(d_dx, h->mr.x, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
+        if (m > 0) HIPCHK(h, hipMemcpyAsync(d_dy, h->mr.x + n, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
+    }
+    return solve_end(h);
+}
+
 // solve: b into xw, conjugate gradients from x = 0 in chunks of iterations -- after each chunk the scalar block comes back through pinned memory and the
 // host decides whether another chunk is needed (the kernels of a chunk enqueued past the end of the solve return at once) --, then dy = x and dx.
 // BLOCKS until the outcome is known; dy / dx are enqueued behind it.
@@ -1499,6 +1577,7 @@ static int krylov_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double
     if (!d_dx || !d_dy) return TLPK_BADARG;
     if (int g = refuse(h, d_xip && d_xid, R_MULTI | R_DEVICE | R_FACTORED)) return g;
     if (int rc = solve_begin(h)) return rc;
+    if (h->krylov == TLPK_KRYLOV_MINRES) return minres_solve(h, d_dx, d_dy, d_xip, d_xid);
     const double *xp[2] = {d_xip, d_xip}, *xd[2] = {d_xid, d_xid};
     double *dy[2] = {d_dy, d_dy}, *dx[2] = {d_dx, d_dx};
     const i64 m = h->S.m, itmax = h->krylov_itmax;
@@ -2501,6 +2580,10 @@ int tlpk_set_profile(tlpk_handle *h, int on) {
 int tlpk_get_perm(const tlpk_handle *h, int64_t *perm) {
     if (!h || !perm) return TLPK_BADARG;
     if (!h->sub.empty()) return tlpk_get_perm(h->sub[0], perm);
+    if (h->krylov == TLPK_KRYLOV_MINRES) {        // the n + m nodes of the augmented matrix, as a direct K2 handle numbers them; nothing is reordered
+        for (i64 i = 0; i < h->S.n + h->S.m; ++i) perm[i] = i;
+        return TLPK_OK;
+    }
     // (dense columns: the constraint nodes in their order; the dense nodes m .. m + k - 1 are left out)
     const i64 mu = user_m(h);
     i64 o = 0;
@@ -2643,6 +2726,6 @@ const char *tlpk_strerror(int code) {
 const char *tlpk_last_error(const tlpk_handle *h) { return h ? h->last_error.c_str() : ""; }
 const char *tlpk_backend_name(void) { return "HIP (gfx950)"; }
 const char *tlpk_system_name(void) { return "Normal equations (K1)"; }
-const char *tlpk_linear_system(const tlpk_handle *h) { return (h && h->S.system == 1) ? "Augmented system (K2)" : "Normal equations (K1)"; }
+const char *tlpk_linear_system(const tlpk_handle *h) { return (h && (h->S.system == 1 || h->krylov == TLPK_KRYLOV_MINRES)) ? "Augmented system (K2)" : "Normal equations (K1)"; }
 
 }  // extern "C"

@@ -157,6 +157,39 @@ void launch_cg_init(hipStream_t st, const DevArrays &a, const CgArrays &c, doubl
 // iteration k (0-based) of the solve: four launches; returns their number
 int launch_cg_iter(hipStream_t st, const DevArrays &a, const CgArrays &c, const double *D, const double *regD, i64 k);
 
+// ---- matrix-free K2: MINRES on [-E A'; A Rd] [dx; dy] = [xi_d; xi_p] (krylov_k2_kernels.hip; DESIGN.md section 1b''''') ----
+// The recurrence's state, kept twice: iteration k reads st[k & 1] and ONE thread of its last kernel writes st[(k + 1) & 1]
+struct MrState { double beta, oldb, dbar, eps, cs, sn, phibar, pad; };
+struct MrScalars {
+    MrState st[2];
+    double tol;           // atol + rtol beta1
+    double resid0, resid; // beta1 = sqrt(b' M^-1 b) / phibar after the last completed iteration
+    double alpha;         // of the running iteration: written by k_mr_step, read by k_mr_rot
+    long long outcome;    // CG_RUNNING until a kernel decides, then (outcome code) | (deciding iteration, 1-based) << 8; tlpk_device.hpp: mr_outcome
+    long long iters;      // completed iterations
+    long long itmax;
+    long long pad[9];
+};
+static_assert(sizeof(MrScalars) == 256, "MrScalars layout");
+inline long long mr_outcome(const MrScalars &sc) { return sc.outcome & 0xff; }
+struct MrArrays {
+    MrScalars *sc = nullptr;
+    double *r[2] = {nullptr, nullptr};            // r1 / r2 of the Lanczos recurrence, rotating by parity; order N = n + m, stored [n-part; m-part] like every vector here
+    double *z[2] = {nullptr, nullptr};            // M^-1 r[.]; without a preconditioner z[.] IS r[.] (the same storage)
+    double *u = nullptr, *x = nullptr;
+    double *w[2] = {nullptr, nullptr};
+    double *Minv = nullptr;                       // Jacobi: 1 / diag(E_j, s_i); nullptr = no preconditioner
+    double *slots_a = nullptr, *slots_g = nullptr;   // partial sums of v'u (k_mr_op) and of r'z (k_mr_init, k_mr_step), one per workgroup
+    i32 *long_rows = nullptr, *long_cols = nullptr; i64 n_long_rows = 0, n_long_cols = 0;
+    int g_cols = 0, g_rows = 0, g_lcols = 0, g_lrows = 0, g_vec = 0;   // workgroups of k_mr_op (short columns, short rows, long columns, long rows) / of the vector kernels
+};
+void launch_mr_diag(hipStream_t st, i64 n, const double *theta, const double *regP, double *E);
+void launch_mr_jacobi(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *E, const double *regD);
+// b = [xi_d; xi_p]: x = w = 0, z = M^-1 b, beta1, tolerance, outcome (a zero right-hand side is solved at once); two launches
+void launch_mr_init(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *xi_p, const double *xi_d, double atol, double rtol, i64 itmax);
+// iteration k (0-based) of the solve: three launches; returns their number
+int launch_mr_iter(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *E, const double *regD, i64 k);
+
 // new values on an analysed pattern (refresh_kernels.hip): w[t] = value(a[t]) * value(b[t]); out[q] = value(src[q]); the strided copy of a dense A
 void launch_refresh_pairs(hipStream_t st, i64 np, const i32 *a, const i32 *b, const double *nz, double *w);
 void launch_refresh_gather(hipStream_t st, i64 n, const i32 *src, const double *nz, double *out);

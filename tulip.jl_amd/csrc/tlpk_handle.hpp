@@ -107,6 +107,10 @@ struct tlpk_handle {
     i64 cg_chunk0 = 4, cg_chunk_max = 32;   // iterations enqueued before the first look at the outcome / at most between two looks (TLPK_CG_CHUNK=first,max)
     i64 cg_iters = 0, cg_iters_total = 0, cg_converged = 0, cg_launches = 0, cg_unsolved = 0;
     double cg_resid0 = 0, cg_resid = 0;
+    // matrix-free K2 (tlpk_options.krylov = TLPK_KRYLOV_MINRES; krylov_k2_kernels.hip): the same handle with MINRES on the augmented system; the chunking, the
+    // event and the counters above serve both methods
+    MrArrays mr;
+    MrScalars *mr_pin = nullptr;
     std::string last_error;
 };
 

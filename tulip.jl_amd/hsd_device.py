@@ -51,7 +51,8 @@ class DeviceHSD:
         if int(backend_kw.get("nranks", 1)) > 1:
             raise ValueError("the device-resident interior-point loops need one handle for the whole LP: nranks must be 1 "
                              "(ngpus > 1 is fine; sharded handles serve the split-phase KKT.update! / KKT.solve!)")
-        # backend = KrylovBackend(...): the matrix-free handle (K1, one device) -- every KKT.solve! of the loop is a conjugate-gradient solve.
+        # backend = KrylovBackend(...): the matrix-free handle (one device) -- every KKT.solve! of the loop is a conjugate-gradient solve (K1) or,
+        # with KrylovBackend(method="minres") and system="K2", a MINRES solve of the augmented system.
         # device / profile / mem_budget_bytes beside it are the object's own fields and override them (Model(..., backend=..., device=1))
         krylov = backend_kw.pop("backend", None)
         if krylov is not None:
@@ -61,9 +62,10 @@ class DeviceHSD:
                 krylov = copy.copy(krylov)
                 for key, value in backend_kw.items():
                     setattr(krylov, key, type(getattr(krylov, key))(value))
-            if str(system).upper() == "K2":
-                raise TypeError("the Krylov backend solves the normal equations (K1) only")
-            self.kkt = setup(A, K1(), krylov)
+            k2 = str(system).upper() == "K2"
+            if k2 and krylov.method != "minres":
+                raise TypeError("the Krylov backend solves the normal equations (K1) only (method='minres' solves K2)")
+            self.kkt = setup(A, K2() if k2 else K1(), krylov)        # (K1 with method="minres": setup's TypeError)
         elif dense:
             if str(system).upper() == "K2":
                 raise TypeError("the dense backend solves the normal equations (K1) only")

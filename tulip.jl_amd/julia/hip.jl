@@ -80,7 +80,7 @@ end
 DenseBackend(; device::Int=0, profile::Bool=false, mem_budget_bytes::Int=0) = DenseBackend(device, profile, mem_budget_bytes)
 
 """
-    KrylovBackend(; device=0, precond=:none, itmax=0, atol=0.0, rtol=0.0, profile=false, mem_budget_bytes=0)
+    KrylovBackend(; device=0, precond=:none, itmax=0, atol=0.0, rtol=0.0, profile=false, mem_budget_bytes=0, method=:cg)
 
 The matrix-free counterpart of `TlpKrylov.Backend(Krylov.CgSolver, ...)` with `KKT_System = K1()`
 (the reference's `src/KKT/Krylov/spd.jl`): nothing is analysed or factorised, every `solve!` runs conjugate gradients on
@@ -89,6 +89,9 @@ As in the reference (`spd.jl:100-101`), a solve that stops at `itmax` returns it
 
     set_parameter(model, "KKT_Backend", Tulip.KKT.TlpHIP.KrylovBackend(precond=:jacobi))
     set_parameter(model, "KKT_System",  Tulip.KKT.K1())
+
+`method = :minres` with `KKT_System = K2()` is `TlpKrylov.Backend(Krylov.MinresSolver, ...)` (`src/KKT/Krylov/sid.jl`): MINRES on the
+augmented system `[-E Aᵀ; A Rd]`; `:jacobi` is then the block diagonal `diag(E_j, Σ_j A_ij²/E_j + Rd_i)` and `itmax = 0` means 2 (m + n).
 """
 struct KrylovBackend <: AbstractKKTBackend
     device::Int
@@ -98,10 +101,13 @@ struct KrylovBackend <: AbstractKKTBackend
     rtol::Float64
     profile::Bool
     mem_budget_bytes::Int
+    method::Symbol
 end
-function KrylovBackend(; device::Int=0, precond::Symbol=:none, itmax::Int=0, atol::Real=0.0, rtol::Real=0.0, profile::Bool=false, mem_budget_bytes::Int=0)
+function KrylovBackend(; device::Int=0, precond::Symbol=:none, itmax::Int=0, atol::Real=0.0, rtol::Real=0.0, profile::Bool=false, mem_budget_bytes::Int=0,
+                       method::Symbol=:cg)
     precond in (:none, :jacobi) || throw(ArgumentError("precond: :none or :jacobi"))
-    return KrylovBackend(device, precond, itmax, Float64(atol), Float64(rtol), profile, mem_budget_bytes)
+    method in (:cg, :minres) || throw(ArgumentError("method: :cg or :minres"))
+    return KrylovBackend(device, precond, itmax, Float64(atol), Float64(rtol), profile, mem_budget_bytes, method)
 end
 
 """
@@ -210,18 +216,19 @@ function setup(A::SparseMatrixCSC{Float64,Int}, system::Union{K1,K2}, b::Backend
     return HIPNormalEquations(m, n, A, h)
 end
 
-# Matrix-free conjugate gradients (Krylov/spd.jl:52-63): K1 only
-function setup(A::SparseMatrixCSC{Float64,Int}, ::K1, b::KrylovBackend)
+# Matrix-free: conjugate gradients (Krylov/spd.jl:52-63) on K1, MINRES (Krylov/sid.jl) on K2
+function setup(A::SparseMatrixCSC{Float64,Int}, system::Union{K1,K2}, b::KrylovBackend)
+    (b.method === :minres) == (system isa K2) ||
+        throw(ArgumentError("TlpHIP.KrylovBackend: method = :cg solves the normal equations (K1), method = :minres the augmented system (K2)"))
     m, n = size(A)
     rc, h = LibTLPK.create_krylov(m, n, A.colptr, A.rowval, A.nzval; device=b.device, precond=b.precond, itmax=b.itmax, atol=b.atol,
-                                  rtol=b.rtol, profile=b.profile, mem_budget_bytes=b.mem_budget_bytes)
+                                  rtol=b.rtol, profile=b.profile, mem_budget_bytes=b.mem_budget_bytes, method=b.method)
     rc == LibTLPK.TLPK_OK || (h == C_NULL || LibTLPK.destroy(h); _check(rc, C_NULL, "KKT.setup"))
     kkt = HIPNormalEquations(m, n, A, h)
-    kkt.method = b.precond === :jacobi ? " CG, Jacobi" : " CG"
+    kkt.method = (b.method === :minres ? " MINRES" : " CG") * (b.precond === :jacobi ? ", Jacobi" : "")
     return kkt
 end
-setup(A::AbstractMatrix, system::K1, b::KrylovBackend) = setup(convert(SparseMatrixCSC{Float64,Int}, A), system, b)
-setup(::AbstractMatrix, ::K2, ::KrylovBackend) = throw(ArgumentError("TlpHIP.KrylovBackend solves the normal equations (K1) only"))
+setup(A::AbstractMatrix, system::Union{K1,K2}, b::KrylovBackend) = setup(convert(SparseMatrixCSC{Float64,Int}, A), system, b)
 
 # Dense constraint matrix (lapack.jl:52-63): the handle of tlpk_create_dense behaves like any single-device K1 handle
 function setup(A::Matrix{Float64}, ::K1, b::DenseBackend)

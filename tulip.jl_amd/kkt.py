@@ -117,11 +117,18 @@ class KrylovBackend(_BackendOptions):
     """`TlpHIP.KrylovBackend`: the analogue of `TlpKrylov.Backend` with `Krylov.CgSolver` (the reference's src/KKT/Krylov/spd.jl) --
     no analysis and no factor: every solve runs conjugate gradients on `A*D*A' + Rd` on the device, matrix-free.  K1 only, one GPU.
     precond: None (the reference) or "jacobi" (the diagonal of `A*D*A' + Rd`, rebuilt by every update); itmax = 0: 2 m; atol = rtol = 0:
-    sqrt(eps).  A solve that stops at `itmax` still returns its last iterate, as the reference does: `stats()["krylov_converged"]` tells."""
+    sqrt(eps).  A solve that stops at `itmax` still returns its last iterate, as the reference does: `stats()["krylov_converged"]` tells.
 
-    def __init__(self, device=0, precond=None, itmax=0, atol=0.0, rtol=0.0, profile=False, mem_budget_bytes=0):
+    method="minres": `Krylov.MinresSolver` (src/KKT/Krylov/sid.jl) -- MINRES on the augmented system `[-E A'; A Rd]`, K2 only
+    (`setup(A, K2(), KrylovBackend(method="minres"))`).  precond "jacobi" is then the block diagonal `diag(E_j, sum_j A_ij^2 / E_j + Rd_i)`
+    and itmax = 0 means 2 (m + n)."""
+
+    def __init__(self, device=0, precond=None, itmax=0, atol=0.0, rtol=0.0, profile=False, mem_budget_bytes=0, method="cg"):
         if precond not in (None, "none", "jacobi"):
             raise ValueError("precond: None or 'jacobi'")
+        if method not in ("cg", "minres"):
+            raise ValueError("method: 'cg' (K1) or 'minres' (K2)")
+        self.method = method
         self.device = int(device)
         self.precond = _lib.PRECOND_JACOBI if precond == "jacobi" else _lib.PRECOND_NONE
         self.itmax = int(itmax)
@@ -198,9 +205,11 @@ class HIPNormalEquations:
             opt.user_perm = _lib.as_p64(backend_.user_perm)
             self._keep.append(backend_.user_perm)
         if isinstance(backend_, KrylovBackend):
-            if system != _lib.SYSTEM_K1:
-                raise TypeError("the Krylov backend solves the normal equations (K1) only")
-            opt.krylov = _lib.KRYLOV_CG
+            if backend_.method == "cg" and system != _lib.SYSTEM_K1:
+                raise TypeError("the Krylov backend solves the normal equations (K1) only (method='minres' solves K2)")
+            if backend_.method == "minres" and system != _lib.SYSTEM_K2:
+                raise TypeError("KrylovBackend(method='minres') solves the augmented system (K2) only")
+            opt.krylov = _lib.KRYLOV_MINRES if backend_.method == "minres" else _lib.KRYLOV_CG
             opt.krylov_precond = backend_.precond
             opt.krylov_itmax = backend_.itmax
             opt.krylov_atol, opt.krylov_rtol = backend_.atol, backend_.rtol
@@ -495,7 +504,7 @@ def backend(kkt):
     name = _lib.lib().tlpk_backend_name().decode()
     be = getattr(kkt, "backend_options", None)
     if isinstance(be, KrylovBackend):                  # the method, as Krylov's `backend` names its solver type (src/KKT/Krylov/spd.jl:48)
-        name += " CG" + (", Jacobi" if be.precond == _lib.PRECOND_JACOBI else "")
+        name += (" MINRES" if be.method == "minres" else " CG") + (", Jacobi" if be.precond == _lib.PRECOND_JACOBI else "")
     return name
 
 
