@@ -636,7 +636,7 @@ def panels_to_dense_L(kkt, lval):
     """Dense L (permuted numbering) from panel storage copied off the device."""
     em = Emulator.__new__(Emulator)
     g = kkt.symbolic
-    em.m = kkt.m
+    em.m = len(g("perm"))          # order of the factored matrix: m for K1, n + m for K2, m + k with k dense columns
     em.f = g("front_f"); em.ns = g("front_ns"); em.col0 = g("front_col0"); em.loff = g("front_loff"); em.lda = g("front_lda")
     em.rowoff = g("front_rowoff"); em.rowidx = g("rowidx"); em.local = g("front_local")
     em.Lval = lval
