@@ -48,6 +48,8 @@ typedef struct tlpk_handle tlpk_handle;
 #define TLPK_KRYLOV_NONE 0
 #define TLPK_KRYLOV_CG 1        /* K1: conjugate gradients on the normal equations */
 #define TLPK_KRYLOV_MINRES 16   /* K2: MINRES on the augmented system.  The K2 methods start at 16; 2 - 15 and every other value: TLPK_BADARG */
+#define TLPK_KRYLOV_TRICG 32    /* K2 in its symmetric quasi-definite form [Rd A; A' -E]: TriCG.  The quasi-definite K2 methods start at 32; 33 is reserved for
+                                   TriMR (the minimum-residual sibling, not implemented) and refused like any unknown value */
 #define TLPK_PRECOND_NONE 0
 #define TLPK_PRECOND_JACOBI 1
 
@@ -94,10 +96,12 @@ typedef struct tlpk_options {
     /* Matrix-free handle (the reference's Krylov family, src/KKT/Krylov/spd.jl): no analysis, no factor, O(nnz(A) + m + n) device memory.  See tlpk_create. */
     int32_t krylov;            /* TLPK_KRYLOV_NONE 0 (default: analyse + factorise) | TLPK_KRYLOV_CG 1: K1, conjugate gradients on
                                   (A D A' + Rd) dy = xi_p + A D xi_d, matrix-free (src/KKT/Krylov/spd.jl) | TLPK_KRYLOV_MINRES 16: K2 (system must be
-                                  TLPK_SYSTEM_K2), MINRES on [-E A'; A Rd] [dx; dy] = [xi_d; xi_p], E = theta^-1 + Rp (src/KKT/Krylov/sid.jl) */
+                                  TLPK_SYSTEM_K2), MINRES on [-E A'; A Rd] [dx; dy] = [xi_d; xi_p], E = theta^-1 + Rp (src/KKT/Krylov/sid.jl) |
+                                  TLPK_KRYLOV_TRICG 32: K2, TriCG on the quasi-definite form [Rd A; A' -E] [dy; dx] = [xi_p; xi_d] (src/KKT/Krylov/sqd.jl) */
     int32_t krylov_precond;    /* 0 = none (the reference) | 1 = Jacobi, rebuilt by every update: CG: M = diag(A D A' + Rd); MINRES: the positive
-                                  definite block diagonal M = diag(E_j, sum_{E_j > 0} A_ij^2 / E_j + Rd_i) */
-    int64_t krylov_itmax;      /* 0 = twice the order of the system (Krylov.jl's default): 2 m for CG, 2 (m + n) for MINRES */
+                                  definite block diagonal M = diag(E_j, sum_{E_j > 0} A_ij^2 / E_j + Rd_i); TriCG: must be 0 (E and Rd are its inner products) */
+    int64_t krylov_itmax;      /* 0 = twice the order of the system (Krylov.jl's default): 2 m for CG, 2 (m + n) for MINRES; TriCG: 2 (m + n) by this
+                                  library's convention -- Krylov.jl's own default for tricg could not be read when this was written */
     double  krylov_atol, krylov_rtol;   /* 0 = sqrt(eps) (spd.jl:66-67); < 0 or non-finite: TLPK_BADARG */
 } tlpk_options;
 
@@ -139,10 +143,11 @@ typedef struct tlpk_stats {
                                   (2 per product); 0 on sparse handles */
     /* matrix-free handles (tlpk_options.krylov); 0 on every other handle.  (Placed in front of the tlpk_set_values pair, which stays the tail of the struct;
        tlpk_stats carries no size field, so any new field means a rebuild of the callers wherever it goes.) */
-    int64_t krylov_iters;        /* CG / MINRES iterations of the last solve */
+    int64_t krylov_iters;        /* CG / MINRES / TriCG iterations of the last solve */
     int64_t krylov_iters_total;  /* since the last update */
     int64_t krylov_converged;    /* 1 = the last solve met the stopping rule; 0 = it stopped at itmax or broke down */
-    double  krylov_resid0, krylov_resid;   /* sqrt(r' M^-1 r) at x = 0 and at exit of the last solve (MINRES: beta1 and phibar, the recurrence's value of it) */
+    double  krylov_resid0, krylov_resid;   /* sqrt(r' M^-1 r) at x = 0 and at exit of the last solve (MINRES: beta1 and phibar, the recurrence's value of it; TriCG: rho_0 and rho_k, the
+                                  residual in the norm of diag(Rd, E)^-1) */
                                  /* tlpk_symbolic_get(h, "krylov_unsolved"): one entry, the number of solves since create that did NOT meet the stopping
                                     rule (what a loop of many solves checks once at its end instead of reading krylov_converged after every solve) */
     double  ms_last_set_values; /* device time of the last tlpk_set_values* (HIP events on the handle's stream; multi-device handles: the slowest shard);
@@ -207,6 +212,26 @@ int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr,
  *            krylov_itmax iterations (0 = 2 (m + n)), when r'z < 0 or a scalar is not finite, or when beta = 0 (the Krylov space is exhausted) with phibar
  *            still above the tolerance.  This is the only stopping rule: Krylov.jl's minres may have others (a test on ||A r||, a condition-number limit) that
  *            could not be compared.  As above, a solve that is NOT solved writes its last iterate and returns TLPK_OK (sid.jl:100-104).
+ *            launches_solve = 2 + 3 per enqueued iteration.
+ * opt->krylov = TLPK_KRYLOV_TRICG with opt->system = TLPK_SYSTEM_K2 (the reference's src/KKT/Krylov/sqd.jl, Krylov.jl's tricg) is again the same handle -- analysis,
+ * refusals, identity permutation of the n + m nodes, tlpk_set_values*, loops, blocking solve, chunked enqueue, stats fields, "Augmented system (K2)" -- with
+ * TriCG (Montoison & Orban) on the symmetric quasi-definite form [Rd A; A' -E] [dy; dx] = [xi_p; xi_d], called with M = Rd^-1, N = E^-1 (sqd.jl:74-77, 87-92).
+ * system = K1 with it is TLPK_BADARG, and so is krylov_precond != 0: the two diagonal blocks are the method's inner products, there is nothing left to
+ * precondition with.  33 (TriMR) is reserved and refused.  Device memory (the gate): 36 nnz + 136 n + 168 m + 65536 bytes -- the copies of A and the vectors of
+ * every handle (36 nnz + 72 n + 104 m) and eight vectors of order n + m ([E; Rd], its reciprocal, [u; v] twice, [p; q], [dx; dy], the two columns of G).
+ *   update : E = theta^-1 + Rp, Rd and their reciprocals are kept (one launch: launches_update = 1).  The method needs E_j > 0 and Rd_i > 0; the reference
+ *            forms inv(0) silently, this library does not: the kernel records the smallest node with a non-positive or non-finite entry, numbered as a K2
+ *            handle numbers its nodes (j for E_j, n + i for Rd_i), and the update returns TLPK_NOT_POSDEF with tlpk_stats.fail_col = that node and
+ *            tlpk_last_error "... not quasi-definite ...".  The handle stays usable and NOT factored (a solve: TLPK_NOT_FACTORED) until an update succeeds --
+ *            the code an interior-point loop answers by raising its regularisation (HSD/step.jl:35-51).
+ *   solve  : v_k in R^m, u_k in R^n with <v, v> = v'Rd v, <u, u> = u'E u tridiagonalise A by two short recurrences (Saunders, Simon & Yip); the Galerkin
+ *            iterate comes from the 2 x 2 block L D L' of the permuted projected matrix (diagonal blocks [1 alpha_k; alpha_k -1], sub-diagonal blocks
+ *            [0 beta_k; gamma_k 0]); Krylov.jl factorises the same matrix scalar by scalar, the iterates agree in exact arithmetic.
+ *            rho_k = hypot(beta_{k+1} pi_k[1], gamma_{k+1} pi_k[0]) = sqrt(r_p'Rd^-1 r_p + r_d'E^-1 r_d) of the residual; rho_0 = hypot(beta_1, gamma_1).
+ *            SOLVED when rho_k <= atol + rtol rho_0 (a zero right-hand side: in 0 iterations); NOT solved after krylov_itmax iterations (0 = 2 (m + n)),
+ *            when a scalar is not finite, or when a 2 x 2 pivot block loses its signature (det D_k >= 0: impossible in exact arithmetic).  A zero
+ *            beta_{k+1} or gamma_{k+1} gives a zero Lanczos vector and the run goes on.  krylov_resid0 = rho_0, krylov_resid = rho_k.  As above, a solve that
+ *            is NOT solved writes its last iterate and returns TLPK_OK (sqd.jl:94-96).
  *            launches_solve = 2 + 3 per enqueued iteration.
  * What to expect: conjugate gradients without a preconditioner (the reference: spd.jl:26 "TODO: preconditioner") or with Jacobi solve the early, well-conditioned
  * systems of an interior-point run in tens of iterations and stall on the late ones (DESIGN.md section 1b has the measured limits). */

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("TLPK_LIB") or os.path.join(HERE, "libtlpk.so")      #
 OK, NOT_POSDEF, BADARG, OOM, HIPERR, NO_DEVICE, TOO_LARGE, NOT_FACTORED, INTERNAL = range(9)
 ORDER_AMD, ORDER_NATURAL, ORDER_USER = 0, 1, 2
 SYSTEM_K1, SYSTEM_K2 = 0, 1
-KRYLOV_NONE, KRYLOV_CG, KRYLOV_MINRES = 0, 1, 16     # (the K2 methods start at 16)
+KRYLOV_NONE, KRYLOV_CG, KRYLOV_MINRES, KRYLOV_TRICG = 0, 1, 16, 32     # (the K2 methods start at 16, the quasi-definite ones at 32; 33 is reserved for TriMR)
 PRECOND_NONE, PRECOND_JACOBI = 0, 1
 KC_NAMES = ["assemble", "extend_add", "potrf", "trsm", "update", "solve_fwd", "solve_bwd", "spmv", "update_reduce", "chain"]
 

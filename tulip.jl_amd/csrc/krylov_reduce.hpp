@@ -1,4 +1,5 @@
-// krylov_reduce.hpp -- the two ordered reductions of the matrix-free kernels (krylov_kernels.hip: conjugate gradients on K1; krylov_k2_kernels.hip: MINRES on K2).
+// krylov_reduce.hpp -- the two ordered reductions of the matrix-free kernels (krylov_kernels.hip: conjugate gradients on K1; krylov_k2_kernels.hip: MINRES on K2;
+// krylov_sqd_kernels.hip: TriCG on K2).
 // A workgroup reduces its partial sum with a fixed shuffle tree and writes it to its slot; every workgroup of the consuming kernel adds the slots in slot
 // order.  No atomics: two solves of the same data are bit-identical.
 #pragma once

@@ -1,0 +1,276 @@
+// krylov_sqd_kernels.hip -- matrix-free K2 in its quasi-definite form: TriCG (Montoison & Orban) on [Rd A; A' -E] [dy; dx] = [xi_p; xi_d],
+// E = theta^-1 + Rp > 0, Rd > 0 (tlpk_options.krylov = TLPK_KRYLOV_TRICG; DESIGN.md section 1b'''''').  A is tridiagonalised by two short recurrences
+// (Saunders, Simon & Yip), v_k in R^m orthonormal in the Rd inner product and u_k in R^n in the E inner product; the Galerkin iterate comes from the 2 x 2
+// block L D L' of the permuted projected matrix.  Every vector of order N = n + m is stored [n-part; m-part]: w = [u; v], the metric W = [E; Rd] and its
+// reciprocal, the iterate x = [dx; dy], the two columns g0, g1 of G = [Gy; Gx].
+//
+// One iteration = three launches and no host involvement (k = 0, 1, ... is the 0-based iteration, par = k & 1):
+//   k_tc_op     t = [A' v - beta E.u_old; A u - gamma Rd.v_old] in ONE grid (both products read vectors of the previous step only): the column lanes walk
+//               the CSC copy of A, the row lanes its row-wise copy;  partial sums of alpha = v'(A u - gamma Rd.v_old)
+//   k_tc_step   alpha from the slots;  t -= alpha W.w;  partial sums of gamma'^2 = p' E^-1 p (n-part) and of beta'^2 = q' Rd^-1 q (m-part), two slot arrays
+//   k_tc_upd    beta', gamma' from the slots;  the 2 x 2 algebra (Lambda, D, pi);  G <- P - G Lambda', x += G pi in place, row by row;
+//               w[par ^ 1] = W^-1 t / [gamma'; beta'] (a zero norm gives a zero vector), written over w_old, which is dead since k_tc_op;
+//               the scalars of the next iteration, the stopping rule, the counter, the outcome word
+// Scalars live in TcScalars (tlpk_device.hpp): the recurrence's state twice, by parity of the iteration that reads it, so that the one thread that writes
+// the next state never races the workgroups that still read this one.  Partial sums go one per workgroup to a slot and are added in slot order by every
+// workgroup of the consumer (krylov_reduce.hpp): no floating-point atomics, two solves of the same data are bit-identical.  Every kernel reads the
+// outcome word first and returns when it is set.  k_tc_upd is the kernel that SETS it, and a workgroup of it that starts late must still update its part
+// of x: the word carries the number of the iteration that set it, and k_tc_upd returns only on a word of another iteration.  No kernel waits for another
+// one: nothing here can hang.
+//
+// Rows and columns of an LP hold a handful of entries: 8 lanes per row, 4 per column, handed out round by round.  A row or column with more than
+// CG_LONG entries is listed at create and gets a whole workgroup in the same launch, behind those of the short ones.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+
+#include "krylov_reduce.hpp"
+#include "tlpk_device.hpp"
+
+namespace tlpk {
+
+namespace {
+
+constexpr int TC_OP_THREADS = 1024;   // k_tc_op: its workgroups are capped (one partial sum each), so each is as large as it can be
+constexpr int TC_SLOTS_LDS = 2 * CG_MAX_SLOTS + 2 * CG_MAX_LONG;
+
+__device__ __forceinline__ bool tc_stopped(const TcScalars *sc) { return sc->outcome != CG_RUNNING; }
+
+// W = [E; Rd], E = theta^-1 + Rp, and 1 / W.  The method needs W > 0: the smallest node (j for E_j, n + i for Rd_i, as a K2 handle numbers them) whose
+// entry is not positive or not finite goes to *bad by an integer minimum (the host sets it to LLONG_MAX first).
+__global__ void k_tc_diag(i64 n, i64 N, const double *__restrict__ theta, const double *__restrict__ regP, const double *__restrict__ regD,
+                          double *__restrict__ W, double *__restrict__ Winv, long long *__restrict__ bad) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const double w = i < n ? theta[i] + regP[i] : regD[i - n];
+    W[i] = w; Winv[i] = 1.0 / w;
+    if (!(w > 0.0) || !isfinite(w)) atomicMin(bad, (long long)i);
+}
+
+// t = b = [xi_d; xi_p], the partial sums of gamma1^2 = xi_d' E^-1 xi_d (slots_g) and beta1^2 = xi_p' Rd^-1 xi_p (slots_b)
+__global__ __launch_bounds__(CG_THREADS) void k_tc_init(i64 n, i64 N, const double *__restrict__ xi_d, const double *__restrict__ xi_p,
+                                                        const double *__restrict__ Winv, double *__restrict__ t, double *__restrict__ slots_g,
+                                                        double *__restrict__ slots_b) {
+    __shared__ double sh[CG_THREADS / 64];
+    double accg = 0.0, accb = 0.0;
+    for (i64 i = (i64)blockIdx.x * CG_THREADS + threadIdx.x; i < N; i += (i64)gridDim.x * CG_THREADS) {
+        const double bi = i < n ? xi_d[i] : xi_p[i - n], s = bi * Winv[i] * bi;
+        t[i] = bi;
+        if (i < n) accg += s; else accb += s;
+    }
+    accg = cg_block_sum(accg, sh);
+    accb = cg_block_sum(accb, sh);
+    if (threadIdx.x == 0) { slots_g[blockIdx.x] = accg; slots_b[blockIdx.x] = accb; }
+}
+
+__device__ __forceinline__ double tc_scaled(double winv, double t, double norm) { return norm > 0.0 ? winv * t / norm : 0.0; }
+
+// Every workgroup forms beta1, gamma1 from the slots: w[0] = [u_1; v_1] = W^-1 b / [gamma1; beta1], w[1] = 0, x = 0, G = 0.  The first one's first thread
+// writes the tolerance of this solve, the state of iteration 0 and the outcome word.
+__global__ __launch_bounds__(CG_THREADS) void k_tc_start(TcScalars *__restrict__ sc, i64 n, i64 N, const double *__restrict__ Winv, const double *__restrict__ t,
+                                                         double *__restrict__ w0, double *__restrict__ w1, double *__restrict__ x, double *__restrict__ g0,
+                                                         double *__restrict__ g1, const double *__restrict__ slots_g, const double *__restrict__ slots_b, int ns,
+                                                         double atol, double rtol, long long itmax) {
+    __shared__ double shs[TC_SLOTS_LDS];
+    const double sg = cg_sum_slots(slots_g, ns, shs);
+    __syncthreads();
+    const double sb = cg_sum_slots(slots_b, ns, shs);
+    const bool ok = sg >= 0.0 && sb >= 0.0 && isfinite(sg) && isfinite(sb);
+    const double gamma1 = sqrt(sg), beta1 = sqrt(sb);
+    for (i64 i = (i64)blockIdx.x * CG_THREADS + threadIdx.x; i < N; i += (i64)gridDim.x * CG_THREADS) {
+        w0[i] = ok ? tc_scaled(Winv[i], t[i], i < n ? gamma1 : beta1) : 0.0;
+        w1[i] = 0.0; x[i] = 0.0; g0[i] = 0.0; g1[i] = 0.0;
+    }
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const double rho0 = hypot(beta1, gamma1), tol = atol + rtol * rho0;
+    TcState s;
+    s.beta = beta1; s.gamma = gamma1; s.i00 = 0.0; s.i01 = 0.0; s.i11 = 0.0; s.pi0 = 0.0; s.pi1 = 0.0; s.pad = 0.0;
+    sc->st[0] = s; sc->st[1] = s;
+    sc->tol = tol; sc->resid0 = rho0; sc->resid = rho0; sc->alpha = 0.0;
+    sc->iters = 0; sc->itmax = itmax;
+    sc->outcome = !ok ? CG_BREAKDOWN : (rho0 <= tol ? CG_SOLVED : (itmax <= 0 ? CG_ITMAX : CG_RUNNING));      // (iteration stamp 0)
+}
+
+// t = [A' v - beta E.u_old; A u - gamma Rd.v_old] and the partial sums of alpha = v'(A u - gamma Rd.v_old); [u; v] = w, [u_old; v_old] = wo (zero in the
+// first iteration).  Blocks [0, gc): 4 lanes per column; [gc, gc + gr): 8 lanes per row; then glc workgroups that share the long columns and glr that
+// share the long rows.  Slot = block index; the column workgroups write a zero.
+__global__ __launch_bounds__(TC_OP_THREADS) void k_tc_op(const TcScalars *__restrict__ sc, int par, i64 n, i64 m, const i64 *__restrict__ Ap,
+                                                         const i32 *__restrict__ Ai, const double *__restrict__ Ax, const i64 *__restrict__ Tp,
+                                                         const i32 *__restrict__ Tj, const double *__restrict__ Tx, const double *__restrict__ W,
+                                                         const double *__restrict__ w, const double *__restrict__ wo, double *__restrict__ t,
+                                                         double *__restrict__ slots_a, unsigned gc, unsigned gr, unsigned glc, unsigned glr,
+                                                         const i32 *__restrict__ long_cols, i64 n_long_cols, const i32 *__restrict__ long_rows, i64 n_long_rows) {
+    __shared__ double sh[TC_OP_THREADS / 64];
+    if (tc_stopped(sc)) return;
+    const double beta = sc->st[par].beta, gamma = sc->st[par].gamma;
+    const double *__restrict__ u = w, *__restrict__ v = w + n;
+    double acc = 0.0;
+    unsigned b = blockIdx.x;
+    if (b < gc) {
+        const int lane = threadIdx.x & 3;
+        const i64 per_round = (i64)gc * (TC_OP_THREADS / 4);
+        for (i64 base = 0; base < n; base += per_round) {
+            const i64 j = base + (((i64)b * TC_OP_THREADS + threadIdx.x) >> 2);
+            const bool live = j < n;
+            const i64 q0 = live ? Ap[j] : 0, q1 = live ? Ap[j + 1] : 0;
+            const bool mine = live && q1 - q0 <= CG_LONG;
+            double s = 0.0;
+            if (mine) for (i64 q = q0 + lane; q < q1; q += 4) s += Ax[q] * v[Ai[q]];
+            s += __shfl_down(s, 2, 4);
+            s += __shfl_down(s, 1, 4);
+            if (mine && lane == 0) t[j] = s - beta * (W[j] * wo[j]);
+        }
+        if (threadIdx.x == 0) slots_a[blockIdx.x] = 0.0;
+        return;
+    }
+    b -= gc;
+    if (b < gr) {
+        const int lane = threadIdx.x & 7;
+        const i64 per_round = (i64)gr * (TC_OP_THREADS / 8);
+        for (i64 base = 0; base < m; base += per_round) {
+            const i64 i = base + (((i64)b * TC_OP_THREADS + threadIdx.x) >> 3);
+            const bool live = i < m;
+            const i64 q0 = live ? Tp[i] : 0, q1 = live ? Tp[i + 1] : 0;
+            const bool mine = live && q1 - q0 <= CG_LONG;
+            double s = 0.0;
+            if (mine) for (i64 q = q0 + lane; q < q1; q += 8) s += Tx[q] * u[Tj[q]];
+#pragma unroll
+            for (int off = 4; off > 0; off >>= 1) s += __shfl_down(s, off, 8);
+            if (mine && lane == 0) {
+                const double qi = s - gamma * (W[n + i] * wo[n + i]);
+                t[n + i] = qi; acc += v[i] * qi;
+            }
+        }
+        acc = cg_block_sum<TC_OP_THREADS>(acc, sh);
+        if (threadIdx.x == 0) slots_a[blockIdx.x] = acc;
+        return;
+    }
+    b -= gr;
+    if (b < glc) {
+        for (i64 k = b; k < n_long_cols; k += glc) {
+            const i64 j = long_cols[k];
+            double s = 0.0;
+            for (i64 q = Ap[j] + threadIdx.x; q < Ap[j + 1]; q += TC_OP_THREADS) s += Ax[q] * v[Ai[q]];
+            s = cg_block_sum<TC_OP_THREADS>(s, sh);
+            if (threadIdx.x == 0) t[j] = s - beta * (W[j] * wo[j]);
+        }
+        if (threadIdx.x == 0) slots_a[blockIdx.x] = 0.0;
+        return;
+    }
+    b -= glc;
+    for (i64 k = b; k < n_long_rows; k += glr) {
+        const i64 i = long_rows[k];
+        double s = 0.0;
+        for (i64 q = Tp[i] + threadIdx.x; q < Tp[i + 1]; q += TC_OP_THREADS) s += Tx[q] * u[Tj[q]];
+        s = cg_block_sum<TC_OP_THREADS>(s, sh);
+        if (threadIdx.x == 0) {
+            const double qi = s - gamma * (W[n + i] * wo[n + i]);
+            t[n + i] = qi; acc += v[i] * qi;
+        }
+    }
+    if (threadIdx.x == 0) slots_a[blockIdx.x] = acc;
+}
+
+// alpha from the slots; t -= alpha W.w; the partial sums of p' E^-1 p (slots_g) and q' Rd^-1 q (slots_b)
+__global__ __launch_bounds__(CG_THREADS) void k_tc_step(TcScalars *__restrict__ sc, i64 n, i64 N, const double *__restrict__ W, const double *__restrict__ Winv,
+                                                        const double *__restrict__ w, double *__restrict__ t, const double *__restrict__ slots_a, int ns_a,
+                                                        double *__restrict__ slots_g, double *__restrict__ slots_b) {
+    __shared__ double sh[CG_THREADS / 64];
+    __shared__ double shs[TC_SLOTS_LDS];
+    if (tc_stopped(sc)) return;
+    const double alpha = cg_sum_slots(slots_a, ns_a, shs);
+    double accg = 0.0, accb = 0.0;
+    for (i64 i = (i64)blockIdx.x * CG_THREADS + threadIdx.x; i < N; i += (i64)gridDim.x * CG_THREADS) {
+        const double ti = t[i] - alpha * (W[i] * w[i]), s = ti * Winv[i] * ti;
+        t[i] = ti;
+        if (i < n) accg += s; else accb += s;
+    }
+    accg = cg_block_sum(accg, sh);
+    accb = cg_block_sum(accb, sh);
+    if (threadIdx.x == 0) { slots_g[blockIdx.x] = accg; slots_b[blockIdx.x] = accb; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) sc->alpha = alpha;      // (no workgroup of this kernel reads it)
+}
+
+// The 2 x 2 algebra and the update.  Every workgroup forms the same scalars from the same slots and the same state st[par]; the first one's first thread
+// writes st[par ^ 1], the stopping rule, the counter and the outcome word (stamped with k + 1).  With Omega = [1 alpha; alpha -1], Psi = [0 beta; gamma 0]:
+// Lambda = Psi D_prev^-1, D = Omega - Lambda Psi', pi = D^-1 (-Psi pi_prev)  (first iteration: Lambda = 0, D = Omega, pi = D^-1 (beta1, gamma1)').  D has
+// one pivot of each sign: det D >= 0 or not finite is NOT solved, x stays.  rho = hypot(beta' pi[1], gamma' pi[0]) is the residual in the W^-1 norm.
+__global__ __launch_bounds__(CG_THREADS) void k_tc_upd(TcScalars *__restrict__ sc, int par, int first, long long k, i64 n, i64 N, const double *__restrict__ Winv,
+                                                       const double *__restrict__ t, const double *__restrict__ w, double *__restrict__ wn, double *__restrict__ g0,
+                                                       double *__restrict__ g1, double *__restrict__ x, const double *__restrict__ slots_g,
+                                                       const double *__restrict__ slots_b, int ns) {
+    __shared__ double shs[TC_SLOTS_LDS];
+    const long long word = sc->outcome;
+    if (word != CG_RUNNING && (word >> 8) != k + 1) return;
+    const double sg = cg_sum_slots(slots_g, ns, shs);
+    __syncthreads();
+    const double sb = cg_sum_slots(slots_b, ns, shs);
+    const TcState s = sc->st[par];
+    const double alpha = sc->alpha, tol = sc->tol;
+    const long long itmax = sc->itmax;
+    double l00 = 0.0, l01 = 0.0, l10 = 0.0, l11 = 0.0, d00 = 1.0, d01 = alpha, d11 = -1.0, r0 = s.beta, r1 = s.gamma;
+    if (!first) {
+        l00 = s.beta * s.i01; l01 = s.beta * s.i11; l10 = s.gamma * s.i00; l11 = s.gamma * s.i01;      // Lambda = Psi D_prev^-1
+        d00 = 1.0 - l01 * s.beta; d01 = alpha - l00 * s.gamma; d11 = -1.0 - l10 * s.gamma;             // D = Omega - Lambda Psi' (symmetric)
+        r0 = -s.beta * s.pi1; r1 = -s.gamma * s.pi0;                                                  // - Psi pi_prev
+    }
+    const double det = d00 * d11 - d01 * d01;
+    const bool broken = !(det < 0.0) || !isfinite(det) || !(sg >= 0.0) || !(sb >= 0.0) || !isfinite(sg) || !isfinite(sb);
+    if (broken) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { sc->iters = k + 1; sc->outcome = CG_BREAKDOWN | ((k + 1) << 8); }
+        return;
+    }
+    const double i00 = d11 / det, i01 = -d01 / det, i11 = d00 / det;
+    const double pi0 = i00 * r0 + i01 * r1, pi1 = i01 * r0 + i11 * r1;
+    const double gamma_n = sqrt(sg), beta_n = sqrt(sb);
+    for (i64 i = (i64)blockIdx.x * CG_THREADS + threadIdx.x; i < N; i += (i64)gridDim.x * CG_THREADS) {
+        const double wi = w[i], a = g0[i], b = g1[i];
+        const double c0 = (i < n ? 0.0 : wi) - (a * l00 + b * l01), c1 = (i < n ? wi : 0.0) - (a * l10 + b * l11);      // P = [v_k 0] on the m-part, [0 u_k] on the n-part
+        g0[i] = c0; g1[i] = c1;
+        x[i] += c0 * pi0 + c1 * pi1;
+        wn[i] = tc_scaled(Winv[i], t[i], i < n ? gamma_n : beta_n);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const double rho = hypot(beta_n * pi1, gamma_n * pi0);
+        TcState nx;
+        nx.beta = beta_n; nx.gamma = gamma_n; nx.i00 = i00; nx.i01 = i01; nx.i11 = i11; nx.pi0 = pi0; nx.pi1 = pi1; nx.pad = 0.0;
+        sc->st[par ^ 1] = nx;
+        sc->resid = rho;
+        sc->iters = k + 1;
+        const long long out = rho <= tol ? CG_SOLVED : (!isfinite(rho) ? CG_BREAKDOWN : (k + 1 >= itmax ? CG_ITMAX : CG_RUNNING));
+        if (out != CG_RUNNING) sc->outcome = out | ((k + 1) << 8);
+    }
+}
+
+inline unsigned nblk(i64 n, int b) { return (unsigned)((n + b - 1) / b); }
+
+}  // namespace
+
+void launch_tc_diag(hipStream_t st, const DevArrays &a, const TcArrays &c, const double *theta, const double *regP, const double *regD) {
+    const i64 N = a.n + a.m;
+    if (N > 0) hipLaunchKernelGGL(k_tc_diag, dim3(nblk(N, 256)), dim3(256), 0, st, a.n, N, theta, regP, regD, c.W, c.Winv, c.bad);
+}
+
+void launch_tc_init(hipStream_t st, const DevArrays &a, const TcArrays &c, const double *xi_p, const double *xi_d, double atol, double rtol, i64 itmax) {
+    const i64 N = a.n + a.m;
+    if (N > 0) hipLaunchKernelGGL(k_tc_init, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, a.n, N, xi_d, xi_p, c.Winv, c.t, c.slots_g, c.slots_b);
+    hipLaunchKernelGGL(k_tc_start, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, c.sc, a.n, N, c.Winv, c.t, c.w[0], c.w[1], c.x, c.g[0], c.g[1], c.slots_g,
+                       c.slots_b, N > 0 ? c.g_vec : 0, atol, rtol, (long long)itmax);
+}
+
+int launch_tc_iter(hipStream_t st, const DevArrays &a, const TcArrays &c, i64 k) {
+    const i64 N = a.n + a.m;
+    if (N <= 0) return 0;
+    const int par = (int)(k & 1);
+    const int ns_a = c.g_cols + c.g_rows + c.g_lcols + c.g_lrows;
+    hipLaunchKernelGGL(k_tc_op, dim3((unsigned)ns_a), dim3(TC_OP_THREADS), 0, st, c.sc, par, a.n, a.m, a.Ap, a.Ai, a.Ax, a.Tp, a.Tj, a.Tx, c.W, c.w[par], c.w[par ^ 1],
+                       c.t, c.slots_a, (unsigned)c.g_cols, (unsigned)c.g_rows, (unsigned)c.g_lcols, (unsigned)c.g_lrows, c.long_cols, c.n_long_cols, c.long_rows,
+                       c.n_long_rows);
+    hipLaunchKernelGGL(k_tc_step, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, c.sc, a.n, N, c.W, c.Winv, c.w[par], c.t, c.slots_a, ns_a, c.slots_g, c.slots_b);
+    hipLaunchKernelGGL(k_tc_upd, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, k == 0 ? 1 : 0, (long long)k, a.n, N, c.Winv, c.t, c.w[par],
+                       c.w[par ^ 1], c.g[0], c.g[1], c.x, c.slots_g, c.slots_b, c.g_vec);
+    return 3;
+}
+
+}  // namespace tlpk

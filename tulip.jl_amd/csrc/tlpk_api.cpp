@@ -527,7 +527,10 @@ int tlpk_host_copy_threads(void) { return host_copy_threads(); }
 
 // ---- matrix-free K1 (tlpk_options.krylov): set-up ----
 // device memory of such a handle: the CSC copy of A and two row-wise copies (36 nnz), the vectors of every handle and of the iteration
+static inline bool krylov_k2(const tlpk_handle *h) { return h->krylov == TLPK_KRYLOV_MINRES || h->krylov == TLPK_KRYLOV_TRICG; }
 static double krylov_bytes(const tlpk_handle *h) {
+    // TriCG on K2: eight vectors of order n + m (the metric [E; Rd] and its reciprocal, [u; v] twice, [p; q], x, the two columns of G)
+    if (h->krylov == TLPK_KRYLOV_TRICG) return 36.0 * (double)h->S.nnzA + 136.0 * (double)h->S.n + 168.0 * (double)h->S.m + 65536.0;
     // MINRES on K2: the same copies of A and vectors of every handle (72 n + 104 m), and nine vectors of order n + m (r1, r2, their two preconditioned
     // copies, u, w1, w2, x, the inverted block diagonal) where conjugate gradients keep four of order m and one of order n
     if (h->krylov == TLPK_KRYLOV_MINRES) return 36.0 * (double)h->S.nnzA + 144.0 * (double)h->S.n + 176.0 * (double)h->S.m + 65536.0;
@@ -544,15 +547,20 @@ static int krylov_gate(tlpk_handle *h, double budget) {
 }
 
 static const char *krylov_check(const tlpk_options &def) {
-    if (def.krylov != TLPK_KRYLOV_CG && def.krylov != TLPK_KRYLOV_MINRES) return "krylov: TLPK_KRYLOV_NONE (0), TLPK_KRYLOV_CG (1) or TLPK_KRYLOV_MINRES (16)";
+    if (def.krylov != TLPK_KRYLOV_CG && def.krylov != TLPK_KRYLOV_MINRES && def.krylov != TLPK_KRYLOV_TRICG)
+        return "krylov: TLPK_KRYLOV_NONE (0), TLPK_KRYLOV_CG (1), TLPK_KRYLOV_MINRES (16) or TLPK_KRYLOV_TRICG (32)";
     if (def.krylov_precond != TLPK_PRECOND_NONE && def.krylov_precond != TLPK_PRECOND_JACOBI) return "krylov_precond: 0 (none) or 1 (Jacobi)";
-    if (def.krylov_itmax < 0) return "krylov_itmax: >= 0 (0 = 2 m; MINRES: 2 (m + n))";
+    if (def.krylov_itmax < 0) return "krylov_itmax: >= 0 (0 = 2 m; MINRES, TriCG: 2 (m + n))";
     if (!(def.krylov_atol >= 0.0) || !std::isfinite(def.krylov_atol) || !(def.krylov_rtol >= 0.0) || !std::isfinite(def.krylov_rtol))
         return "krylov_atol, krylov_rtol: finite and >= 0 (0 = sqrt(eps))";
     if (def.krylov == TLPK_KRYLOV_CG && def.system != TLPK_SYSTEM_K1)
         return "krylov: TLPK_KRYLOV_CG is K1 only (conjugate gradients need the positive definite normal equations; TLPK_KRYLOV_MINRES solves K2)";
     if (def.krylov == TLPK_KRYLOV_MINRES && def.system != TLPK_SYSTEM_K2)
         return "krylov: TLPK_KRYLOV_MINRES is K2 only (system = TLPK_SYSTEM_K2; TLPK_KRYLOV_CG solves K1)";
+    if (def.krylov == TLPK_KRYLOV_TRICG && def.system != TLPK_SYSTEM_K2)
+        return "krylov: TLPK_KRYLOV_TRICG is K2 only (system = TLPK_SYSTEM_K2; TLPK_KRYLOV_CG solves K1)";
+    if (def.krylov == TLPK_KRYLOV_TRICG && def.krylov_precond != TLPK_PRECOND_NONE)
+        return "krylov_precond: TLPK_KRYLOV_TRICG takes no preconditioner (the diagonal blocks E and Rd are the method's inner products)";
     if (def.nranks > 1 || def.rank != 0) return "krylov: one rank only (nranks = 1)";
     if (def.dense_cols) return "krylov: dense_cols does not apply (A*D*A' is never formed)";
     if (def.refine_steps != 0) return "krylov: refine_steps > 0 is not supported";
@@ -571,7 +579,26 @@ static int krylov_upload(tlpk_handle *h) {
     int rc;
     if ((rc = dev_upload(h, &c.long_rows, lr)) != TLPK_OK) return rc;
     if ((rc = dev_upload(h, &c.long_cols, lc)) != TLPK_OK) return rc;
-    if (h->krylov == TLPK_KRYLOV_MINRES) {
+    if (h->krylov == TLPK_KRYLOV_TRICG) {
+        // k_tc_op has the geometry of k_mr_op; the vector kernels write two partial sums per workgroup (the n-part and the m-part)
+        TcArrays &r = h->tc;
+        const i64 N = n + m;
+        r.long_rows = c.long_rows; r.long_cols = c.long_cols; r.n_long_rows = c.n_long_rows; r.n_long_cols = c.n_long_cols;
+        r.g_cols = n > 0 ? (int)std::min<i64>((n * 4 + 1023) / 1024, CG_MAX_SLOTS) : 0;
+        r.g_rows = m > 0 ? (int)std::min<i64>((m * 8 + 1023) / 1024, CG_MAX_SLOTS) : 0;
+        r.g_lcols = (int)std::min<i64>(r.n_long_cols, CG_MAX_LONG);
+        r.g_lrows = (int)std::min<i64>(r.n_long_rows, CG_MAX_LONG);
+        r.g_vec = (int)std::max<i64>(1, std::min<i64>((N + 255) / 256, CG_MAX_SLOTS));
+        if ((rc = dev_alloc(h, &r.W, N)) != TLPK_OK || (rc = dev_alloc(h, &r.Winv, N)) != TLPK_OK || (rc = dev_alloc(h, &r.w[0], N)) != TLPK_OK ||
+            (rc = dev_alloc(h, &r.w[1], N)) != TLPK_OK || (rc = dev_alloc(h, &r.t, N)) != TLPK_OK || (rc = dev_alloc(h, &r.x, N)) != TLPK_OK ||
+            (rc = dev_alloc(h, &r.g[0], N)) != TLPK_OK || (rc = dev_alloc(h, &r.g[1], N)) != TLPK_OK ||
+            (rc = dev_alloc(h, &r.slots_a, std::max(1, r.g_cols + r.g_rows + r.g_lcols + r.g_lrows))) != TLPK_OK ||
+            (rc = dev_alloc(h, &r.slots_g, r.g_vec)) != TLPK_OK || (rc = dev_alloc(h, &r.slots_b, r.g_vec)) != TLPK_OK ||
+            (rc = dev_alloc(h, &r.sc, 1)) != TLPK_OK || (rc = dev_alloc(h, &r.bad, 1)) != TLPK_OK) return rc;
+        HIPCHK(h, hipMemset(r.sc, 0, sizeof(TcScalars)));
+        HIPCHK(h, hipHostMalloc((void **)&h->tc_pin, sizeof(TcScalars) + sizeof(long long), hipHostMallocDefault));
+        std::memset(h->tc_pin, 0, sizeof(TcScalars) + sizeof(long long));
+    } else if (h->krylov == TLPK_KRYLOV_MINRES) {
         // k_mr_op: 1024 threads, 4 lanes per column and 8 per row; at most CG_MAX_SLOTS workgroups of either kind, CG_MAX_LONG share the long ones
         MrArrays &r = h->mr;
         const i64 N = n + m;
@@ -822,7 +849,7 @@ int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr, 
     if (def.krylov != TLPK_KRYLOV_NONE) {
         h->krylov = def.krylov; h->krylov_precond = def.krylov_precond;
         h->krylov_itmax = def.krylov_itmax > 0 ? def.krylov_itmax
-                        : 2 * (std::max<int64_t>(m, 0) + (def.krylov == TLPK_KRYLOV_MINRES ? std::max<int64_t>(n, 0) : 0));      // Krylov.jl: twice the order of the system
+                        : 2 * (std::max<int64_t>(m, 0) + (def.krylov != TLPK_KRYLOV_CG ? std::max<int64_t>(n, 0) : 0));      // Krylov.jl: twice the order of the system
         const double se = std::sqrt(std::numeric_limits<double>::epsilon());
         h->krylov_atol = def.krylov_atol > 0.0 ? def.krylov_atol : se;
         h->krylov_rtol = def.krylov_rtol > 0.0 ? def.krylov_rtol : se;
@@ -937,6 +964,7 @@ void tlpk_destroy(tlpk_handle *h) {
         if (h->pin_out) hipHostFree(h->pin_out);
         if (h->cg_pin) hipHostFree(h->cg_pin);
         if (h->mr_pin) hipHostFree(h->mr_pin);
+        if (h->tc_pin) hipHostFree(h->tc_pin);
         if (h->cg_ev) hipEventDestroy(h->cg_ev);
         for (hipEvent_t e : h->io_events) hipEventDestroy(e);
         for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
@@ -1201,7 +1229,16 @@ static int update_async_wait(tlpk_handle *h) {
 // update: D = 1 / (theta^-1 + Rp) and, with Jacobi, the inverted diagonal of S; there is no factor that could fail
 static int krylov_update(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
     if (int rc = update_begin(h, d_theta, d_regP, d_regD)) return rc;
-    if (h->krylov == TLPK_KRYLOV_MINRES) {
+    long long *tc_bad = nullptr;
+    if (h->krylov == TLPK_KRYLOV_TRICG) {
+        // W = [E; Rd] and 1 / W in one launch; the status word (the smallest node whose entry is not positive) comes back behind it
+        ProfScope ps(h, TLPK_KC_SPMV);
+        tc_bad = reinterpret_cast<long long *>(h->tc_pin + 1);
+        *tc_bad = LLONG_MAX;
+        HIPCHK(h, hipMemcpyAsync(h->tc.bad, tc_bad, sizeof(long long), hipMemcpyHostToDevice, h->stream));
+        launch_tc_diag(h->stream, h->d, h->tc, h->d_theta, h->d_regP, h->d_regD);
+        HIPCHK(h, hipMemcpyAsync(tc_bad, h->tc.bad, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    } else if (h->krylov == TLPK_KRYLOV_MINRES) {
         // d_D holds E = theta^-1 + Rp, NOT its inverse: a column with E_j = 0 (a free variable without regularisation) is as good as any other
         ProfScope ps(h, TLPK_KC_SPMV);
         launch_mr_diag(h->stream, h->S.n, h->d_theta, h->d_regP, h->d_D);
@@ -1215,8 +1252,14 @@ static int krylov_update(tlpk_handle *h, const double *d_theta, const double *d_
     HIPCHK(h, hipGetLastError());
     float ms = 0.f; hipEventElapsedTime(&ms, h->ev0, h->ev1); h->ms_update = ms;
     prof_collect(h);
-    h->factored = true;
     h->cg_iters_total = 0;
+    if (tc_bad && *tc_bad != LLONG_MAX) {          // (factored stays false: the handle takes the next update)
+        h->fail_col = *tc_bad;
+        h->last_error = "TriCG: K2 is not quasi-definite: theta^-1 + Rp (nodes 0 .. n - 1) and Rd (nodes n .. n + m - 1) must be positive, node " +
+                        std::to_string(*tc_bad) + " is not";
+        return TLPK_NOT_POSDEF;
+    }
+    h->factored = true;
     return TLPK_OK;
 }
 int tlpk_update_device_async(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
@@ -1570,6 +1613,43 @@ static int minres_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double
     return solve_end(h);
 }
 
+// TriCG on the quasi-definite form of K2: the same chunked enqueue; launches: 2 (init) + 3 per enqueued iteration; x = [dx; dy]
+static int tricg_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
+    const i64 m = h->S.m, n = h->S.n, N = m + n, itmax = h->krylov_itmax;
+    i64 launches = 2;
+    { ProfScope ps(h, TLPK_KC_SPMV); launch_tc_init(h->stream, h->d, h->tc, d_xip, d_xid, h->krylov_atol, h->krylov_rtol, itmax); }
+    i64 enq = 0, chunk = h->cg_chunk0;
+    for (;;) {
+        const i64 cnt = N > 0 ? std::min(chunk, itmax - enq) : 0;
+        {
+            ProfScope ps(h, TLPK_KC_SPMV);
+            for (i64 k = enq; k < enq + cnt; ++k) launches += launch_tc_iter(h->stream, h->d, h->tc, k);
+        }
+        HIPCHK(h, hipGetLastError());
+        enq += cnt;
+        chunk = std::min(chunk * 2, h->cg_chunk_max);
+        HIPCHK(h, hipMemcpyAsync(h->tc_pin, h->tc.sc, sizeof(TcScalars), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipEventRecord(h->cg_ev, h->stream));
+        HIPCHK(h, hipEventSynchronize(h->cg_ev));
+        if (h->tc_pin->outcome != CG_RUNNING || enq >= itmax || N <= 0) break;
+    }
+    const TcScalars &sc = *h->tc_pin;
+    h->cg_iters = sc.iters; h->cg_iters_total += sc.iters; h->cg_converged = tc_outcome(sc) == CG_SOLVED ? 1 : 0;
+    if (!h->cg_converged) ++h->cg_unsolved;
+    h->cg_resid0 = sc.resid0; h->cg_resid = sc.resid; h->cg_launches = launches;
+    if (sc.outcome == CG_RUNNING) {
+        solve_end(h);
+        h->last_error = "TriCG: every iteration was enqueued and the outcome word is still unset";
+        return TLPK_INTERNAL;
+    }
+    {
+        ProfScope ps(h, TLPK_KC_SPMV);
+        if (n > 0) HIPCHK(h, hipMemcpyAsync(d_dx, h->tc.x, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
+        if (m > 0) HIPCHK(h, hipMemcpyAsync(d_dy, h->tc.x + n, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
+    }
+    return solve_end(h);
+}
+
 // solve: b into xw, conjugate gradients from x = 0 in chunks of iterations -- after each chunk the scalar block comes back through pinned memory and the
 // host decides whether another chunk is needed (the kernels of a chunk enqueued past the end of the solve return at once) --, then dy = x and dx.
 // BLOCKS until the outcome is known; dy / dx are enqueued behind it.
@@ -1578,6 +1658,7 @@ static int krylov_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double
     if (int g = refuse(h, d_xip && d_xid, R_MULTI | R_DEVICE | R_FACTORED)) return g;
     if (int rc = solve_begin(h)) return rc;
     if (h->krylov == TLPK_KRYLOV_MINRES) return minres_solve(h, d_dx, d_dy, d_xip, d_xid);
+    if (h->krylov == TLPK_KRYLOV_TRICG) return tricg_solve(h, d_dx, d_dy, d_xip, d_xid);
     const double *xp[2] = {d_xip, d_xip}, *xd[2] = {d_xid, d_xid};
     double *dy[2] = {d_dy, d_dy}, *dx[2] = {d_dx, d_dx};
     const i64 m = h->S.m, itmax = h->krylov_itmax;
@@ -2555,7 +2636,7 @@ int tlpk_info(const tlpk_handle *h, tlpk_stats *out) {
     if (h->sv_pending && h->has_device && hipSetDevice(h->device) == hipSuccess) sv_time_take(const_cast<tlpk_handle *>(h));      // an enqueued refresh: its time once the events have completed
     out->ms_last_set_values = h->ms_set_values; out->set_values_bytes = h->set_values_bytes;
     if (h->krylov) {
-        out->launches_update = 1 + (h->krylov_precond == TLPK_PRECOND_JACOBI ? 1 : 0);
+        out->launches_update = 1 + (h->krylov_precond == TLPK_PRECOND_JACOBI ? 1 : 0);      // (TriCG: the one kernel of W, 1 / W and the check)
         out->launches_solve = h->cg_launches;                   // of the last solve: the number depends on the data
         out->krylov_iters = h->cg_iters; out->krylov_iters_total = h->cg_iters_total; out->krylov_converged = h->cg_converged;
         out->krylov_resid0 = h->cg_resid0; out->krylov_resid = h->cg_resid;
@@ -2580,7 +2661,7 @@ int tlpk_set_profile(tlpk_handle *h, int on) {
 int tlpk_get_perm(const tlpk_handle *h, int64_t *perm) {
     if (!h || !perm) return TLPK_BADARG;
     if (!h->sub.empty()) return tlpk_get_perm(h->sub[0], perm);
-    if (h->krylov == TLPK_KRYLOV_MINRES) {        // the n + m nodes of the augmented matrix, as a direct K2 handle numbers them; nothing is reordered
+    if (krylov_k2(h)) {        // the n + m nodes of the augmented matrix, as a direct K2 handle numbers them; nothing is reordered
         for (i64 i = 0; i < h->S.n + h->S.m; ++i) perm[i] = i;
         return TLPK_OK;
     }
@@ -2726,6 +2807,6 @@ const char *tlpk_strerror(int code) {
 const char *tlpk_last_error(const tlpk_handle *h) { return h ? h->last_error.c_str() : ""; }
 const char *tlpk_backend_name(void) { return "HIP (gfx950)"; }
 const char *tlpk_system_name(void) { return "Normal equations (K1)"; }
-const char *tlpk_linear_system(const tlpk_handle *h) { return (h && (h->S.system == 1 || h->krylov == TLPK_KRYLOV_MINRES)) ? "Augmented system (K2)" : "Normal equations (K1)"; }
+const char *tlpk_linear_system(const tlpk_handle *h) { return (h && (h->S.system == 1 || krylov_k2(h))) ? "Augmented system (K2)" : "Normal equations (K1)"; }
 
 }  // extern "C"

@@ -190,6 +190,40 @@ void launch_mr_init(hipStream_t st, const DevArrays &a, const MrArrays &c, const
 // iteration k (0-based) of the solve: three launches; returns their number
 int launch_mr_iter(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *E, const double *regD, i64 k);
 
+// ---- matrix-free K2, quasi-definite form: TriCG on [Rd A; A' -E] [dy; dx] = [xi_p; xi_d] (krylov_sqd_kernels.hip; DESIGN.md section 1b'''''') ----
+// The recurrence's state, kept twice like MrState: beta_k, gamma_k (the norms that scaled v_k, u_k), the inverse of the previous 2 x 2 pivot block
+// D (symmetric) and the previous pi
+struct TcState { double beta, gamma, i00, i01, i11, pi0, pi1, pad; };
+struct TcScalars {
+    TcState st[2];
+    double tol;           // atol + rtol rho_0
+    double resid0, resid; // rho_0 = hypot(beta1, gamma1) / rho_k after the last completed iteration
+    double alpha;         // of the running iteration: written by k_tc_step, read by k_tc_upd
+    long long outcome;    // as MrScalars: CG_RUNNING, then (outcome code) | (deciding iteration, 1-based) << 8
+    long long iters;      // completed iterations
+    long long itmax;
+    long long pad[9];
+};
+static_assert(sizeof(TcScalars) == 256, "TcScalars layout");
+inline long long tc_outcome(const TcScalars &sc) { return sc.outcome & 0xff; }
+struct TcArrays {
+    TcScalars *sc = nullptr;
+    long long *bad = nullptr;                     // update: the smallest node with a non-positive or non-finite diagonal entry, LLONG_MAX = none
+    double *W = nullptr, *Winv = nullptr;         // the metric [E; Rd] and its reciprocal; order N = n + m, stored [n-part; m-part] like every vector here
+    double *w[2] = {nullptr, nullptr};            // [u_k; v_k] and [u_{k-1}; v_{k-1}], rotating by parity
+    double *t = nullptr, *x = nullptr;            // [p; q] of the iteration; the iterate [dx; dy]
+    double *g[2] = {nullptr, nullptr};            // the two columns of G = [Gy; Gx], updated in place row by row
+    double *slots_a = nullptr, *slots_g = nullptr, *slots_b = nullptr;   // partial sums of alpha (k_tc_op), of p'E^-1 p and of q'Rd^-1 q (k_tc_init, k_tc_step)
+    i32 *long_rows = nullptr, *long_cols = nullptr; i64 n_long_rows = 0, n_long_cols = 0;
+    int g_cols = 0, g_rows = 0, g_lcols = 0, g_lrows = 0, g_vec = 0;   // workgroups of k_tc_op (short columns, short rows, long columns, long rows) / of the vector kernels
+};
+// W, 1 / W and the quasi-definiteness check (one launch; *c.bad must hold LLONG_MAX before it)
+void launch_tc_diag(hipStream_t st, const DevArrays &a, const TcArrays &c, const double *theta, const double *regP, const double *regD);
+// b = [xi_d; xi_p]: beta1, gamma1, v_1, u_1, x = G = 0, tolerance, outcome (a zero right-hand side is solved at once); two launches
+void launch_tc_init(hipStream_t st, const DevArrays &a, const TcArrays &c, const double *xi_p, const double *xi_d, double atol, double rtol, i64 itmax);
+// iteration k (0-based) of the solve: three launches; returns their number
+int launch_tc_iter(hipStream_t st, const DevArrays &a, const TcArrays &c, i64 k);
+
 // new values on an analysed pattern (refresh_kernels.hip): w[t] = value(a[t]) * value(b[t]); out[q] = value(src[q]); the strided copy of a dense A
 void launch_refresh_pairs(hipStream_t st, i64 np, const i32 *a, const i32 *b, const double *nz, double *w);
 void launch_refresh_gather(hipStream_t st, i64 n, const i32 *src, const double *nz, double *out);

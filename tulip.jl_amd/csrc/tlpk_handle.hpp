@@ -111,6 +111,9 @@ struct tlpk_handle {
     // event and the counters above serve both methods
     MrArrays mr;
     MrScalars *mr_pin = nullptr;
+    // the quasi-definite form of K2 (TLPK_KRYLOV_TRICG; krylov_sqd_kernels.hip); tc_pin: the scalar block, behind it the update's status word
+    TcArrays tc;
+    TcScalars *tc_pin = nullptr;
     std::string last_error;
 };
 

@@ -52,7 +52,7 @@ class DeviceHSD:
             raise ValueError("the device-resident interior-point loops need one handle for the whole LP: nranks must be 1 "
                              "(ngpus > 1 is fine; sharded handles serve the split-phase KKT.update! / KKT.solve!)")
         # backend = KrylovBackend(...): the matrix-free handle (one device) -- every KKT.solve! of the loop is a conjugate-gradient solve (K1) or,
-        # with KrylovBackend(method="minres") and system="K2", a MINRES solve of the augmented system.
+        # with KrylovBackend(method="minres" | "tricg") and system="K2", a MINRES / TriCG solve of the augmented system.
         # device / profile / mem_budget_bytes beside it are the object's own fields and override them (Model(..., backend=..., device=1))
         krylov = backend_kw.pop("backend", None)
         if krylov is not None:
@@ -63,9 +63,9 @@ class DeviceHSD:
                 for key, value in backend_kw.items():
                     setattr(krylov, key, type(getattr(krylov, key))(value))
             k2 = str(system).upper() == "K2"
-            if k2 and krylov.method != "minres":
-                raise TypeError("the Krylov backend solves the normal equations (K1) only (method='minres' solves K2)")
-            self.kkt = setup(A, K2() if k2 else K1(), krylov)        # (K1 with method="minres": setup's TypeError)
+            if k2 and krylov.method == "cg":
+                raise TypeError("the Krylov backend solves the normal equations (K1) only (method='minres' and method='tricg' solve K2)")
+            self.kkt = setup(A, K2() if k2 else K1(), krylov)        # (K1 with a K2 method: setup's TypeError)
         elif dense:
             if str(system).upper() == "K2":
                 raise TypeError("the dense backend solves the normal equations (K1) only")

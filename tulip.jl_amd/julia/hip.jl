@@ -92,6 +92,10 @@ As in the reference (`spd.jl:100-101`), a solve that stops at `itmax` returns it
 
 `method = :minres` with `KKT_System = K2()` is `TlpKrylov.Backend(Krylov.MinresSolver, ...)` (`src/KKT/Krylov/sid.jl`): MINRES on the
 augmented system `[-E Aᵀ; A Rd]`; `:jacobi` is then the block diagonal `diag(E_j, Σ_j A_ij²/E_j + Rd_i)` and `itmax = 0` means 2 (m + n).
+
+`method = :tricg` with `KKT_System = K2()` is `TlpKrylov.Backend(Krylov.TricgSolver, ...)` (`src/KKT/Krylov/sqd.jl`): TriCG on the
+quasi-definite form `[Rd A; Aᵀ -E]`; `precond` must be `:none` (`E` and `Rd` are the method's inner products).  An `update!` with an
+`E_j ≤ 0` or an `Rd_i ≤ 0` throws `PosDefException`, which the interior-point loops answer by raising the regularisation.
 """
 struct KrylovBackend <: AbstractKKTBackend
     device::Int
@@ -106,7 +110,8 @@ end
 function KrylovBackend(; device::Int=0, precond::Symbol=:none, itmax::Int=0, atol::Real=0.0, rtol::Real=0.0, profile::Bool=false, mem_budget_bytes::Int=0,
                        method::Symbol=:cg)
     precond in (:none, :jacobi) || throw(ArgumentError("precond: :none or :jacobi"))
-    method in (:cg, :minres) || throw(ArgumentError("method: :cg or :minres"))
+    method in (:cg, :minres, :tricg) || throw(ArgumentError("method: :cg, :minres or :tricg"))
+    (method === :tricg && precond !== :none) && throw(ArgumentError("method = :tricg takes no preconditioner: precond must be :none"))
     return KrylovBackend(device, precond, itmax, Float64(atol), Float64(rtol), profile, mem_budget_bytes, method)
 end
 
@@ -216,16 +221,16 @@ function setup(A::SparseMatrixCSC{Float64,Int}, system::Union{K1,K2}, b::Backend
     return HIPNormalEquations(m, n, A, h)
 end
 
-# Matrix-free: conjugate gradients (Krylov/spd.jl:52-63) on K1, MINRES (Krylov/sid.jl) on K2
+# Matrix-free: conjugate gradients (Krylov/spd.jl:52-63) on K1, MINRES (Krylov/sid.jl) or TriCG (Krylov/sqd.jl) on K2
 function setup(A::SparseMatrixCSC{Float64,Int}, system::Union{K1,K2}, b::KrylovBackend)
-    (b.method === :minres) == (system isa K2) ||
-        throw(ArgumentError("TlpHIP.KrylovBackend: method = :cg solves the normal equations (K1), method = :minres the augmented system (K2)"))
+    (b.method !== :cg) == (system isa K2) ||
+        throw(ArgumentError("TlpHIP.KrylovBackend: method = :cg solves the normal equations (K1), method = :minres / :tricg the augmented system (K2)"))
     m, n = size(A)
     rc, h = LibTLPK.create_krylov(m, n, A.colptr, A.rowval, A.nzval; device=b.device, precond=b.precond, itmax=b.itmax, atol=b.atol,
                                   rtol=b.rtol, profile=b.profile, mem_budget_bytes=b.mem_budget_bytes, method=b.method)
     rc == LibTLPK.TLPK_OK || (h == C_NULL || LibTLPK.destroy(h); _check(rc, C_NULL, "KKT.setup"))
     kkt = HIPNormalEquations(m, n, A, h)
-    kkt.method = (b.method === :minres ? " MINRES" : " CG") * (b.precond === :jacobi ? ", Jacobi" : "")
+    kkt.method = (b.method === :tricg ? " TriCG" : b.method === :minres ? " MINRES" : " CG") * (b.precond === :jacobi ? ", Jacobi" : "")
     return kkt
 end
 setup(A::AbstractMatrix, system::Union{K1,K2}, b::KrylovBackend) = setup(convert(SparseMatrixCSC{Float64,Int}, A), system, b)

@@ -27,6 +27,7 @@ const TLPK_SYSTEM_K2 = Int32(1)
 const TLPK_KRYLOV_NONE = Int32(0)
 const TLPK_KRYLOV_CG = Int32(1)
 const TLPK_KRYLOV_MINRES = Int32(16)    # the K2 methods start at 16
+const TLPK_KRYLOV_TRICG = Int32(32)     # the quasi-definite K2 methods start at 32 (33 is reserved for TriMR)
 
 # return codes (include/tlpk.h)
 const TLPK_OK = Cint(0)
@@ -60,9 +61,9 @@ Base.@kwdef mutable struct Options
     max_dense_cols::Int32 = 0    # cap on their number; 0 = 1024
     dense_col_min::Int64 = 0     # 0 = 1000
     col_dense::Ptr{Int64} = C_NULL
-    krylov::Int32 = 0            # TLPK_KRYLOV_NONE | TLPK_KRYLOV_CG: matrix-free conjugate gradients on the normal equations (K1) | TLPK_KRYLOV_MINRES: MINRES on K2
+    krylov::Int32 = 0            # TLPK_KRYLOV_NONE | TLPK_KRYLOV_CG: matrix-free conjugate gradients on the normal equations (K1) | TLPK_KRYLOV_MINRES: MINRES on K2 | TLPK_KRYLOV_TRICG: TriCG on K2
     krylov_precond::Int32 = 0    # 0 = none | 1 = Jacobi
-    krylov_itmax::Int64 = 0      # 0 = 2 m (MINRES: 2 (m + n))
+    krylov_itmax::Int64 = 0      # 0 = 2 m (MINRES, TriCG: 2 (m + n))
     krylov_atol::Float64 = 0.0   # 0 = sqrt(eps)
     krylov_rtol::Float64 = 0.0
 end
@@ -145,19 +146,20 @@ end
 
 `tlpk_create` with `krylov = TLPK_KRYLOV_CG`: no analysis, no factor; every solve runs conjugate gradients on the device.
 `precond`: `:none` or `:jacobi`.  `method = :minres`: `krylov = TLPK_KRYLOV_MINRES` and `system = TLPK_SYSTEM_K2`, MINRES on the
-augmented system.
+augmented system.  `method = :tricg`: `krylov = TLPK_KRYLOV_TRICG` and `system = TLPK_SYSTEM_K2`, TriCG on its quasi-definite form;
+`precond` must be `:none`.
 """
 function create_krylov(m::Int, n::Int, colptr::Vector{Int}, rowval::Vector{Int}, nzval::Vector{Float64};
                        device::Integer=0, precond::Symbol=:none, itmax::Integer=0, atol::Real=0.0, rtol::Real=0.0,
                        profile::Bool=false, mem_budget_bytes::Integer=0, method::Symbol=:cg)
-    method in (:cg, :minres) || throw(ArgumentError("method: :cg or :minres"))
+    method in (:cg, :minres, :tricg) || throw(ArgumentError("method: :cg, :minres or :tricg"))
     opt = Options()
     opt.struct_size = Int32(sizeof(Options))
     opt.device = Int32(device)
     opt.profile = Int32(profile)
     opt.mem_budget_bytes = Int64(mem_budget_bytes)
-    opt.krylov = method === :minres ? TLPK_KRYLOV_MINRES : TLPK_KRYLOV_CG
-    opt.system = method === :minres ? TLPK_SYSTEM_K2 : TLPK_SYSTEM_K1
+    opt.krylov = method === :tricg ? TLPK_KRYLOV_TRICG : method === :minres ? TLPK_KRYLOV_MINRES : TLPK_KRYLOV_CG
+    opt.system = method === :cg ? TLPK_SYSTEM_K1 : TLPK_SYSTEM_K2
     opt.krylov_precond = Int32(precond === :jacobi)
     opt.krylov_itmax = Int64(itmax)
     opt.krylov_atol = Float64(atol)

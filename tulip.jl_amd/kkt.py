@@ -121,13 +121,19 @@ class KrylovBackend(_BackendOptions):
 
     method="minres": `Krylov.MinresSolver` (src/KKT/Krylov/sid.jl) -- MINRES on the augmented system `[-E A'; A Rd]`, K2 only
     (`setup(A, K2(), KrylovBackend(method="minres"))`).  precond "jacobi" is then the block diagonal `diag(E_j, sum_j A_ij^2 / E_j + Rd_i)`
-    and itmax = 0 means 2 (m + n)."""
+    and itmax = 0 means 2 (m + n).
+
+    method="tricg": `Krylov.TricgSolver` (src/KKT/Krylov/sqd.jl) -- TriCG on the symmetric quasi-definite form `[Rd A; A' -E]`, K2 only.
+    precond must be None (`E` and `Rd` are the method's inner products); itmax = 0 means 2 (m + n).  An update with an `E_j <= 0` or an
+    `Rd_i <= 0` raises PosDefException (`stats()["fail_col"]`: `j`, or `n + i`) and leaves the handle usable."""
 
     def __init__(self, device=0, precond=None, itmax=0, atol=0.0, rtol=0.0, profile=False, mem_budget_bytes=0, method="cg"):
         if precond not in (None, "none", "jacobi"):
             raise ValueError("precond: None or 'jacobi'")
-        if method not in ("cg", "minres"):
-            raise ValueError("method: 'cg' (K1) or 'minres' (K2)")
+        if method not in ("cg", "minres", "tricg"):
+            raise ValueError("method: 'cg' (K1), 'minres' or 'tricg' (K2)")
+        if method == "tricg" and precond not in (None, "none"):
+            raise ValueError("method='tricg' takes no preconditioner: precond must be None")
         self.method = method
         self.device = int(device)
         self.precond = _lib.PRECOND_JACOBI if precond == "jacobi" else _lib.PRECOND_NONE
@@ -206,10 +212,10 @@ class HIPNormalEquations:
             self._keep.append(backend_.user_perm)
         if isinstance(backend_, KrylovBackend):
             if backend_.method == "cg" and system != _lib.SYSTEM_K1:
-                raise TypeError("the Krylov backend solves the normal equations (K1) only (method='minres' solves K2)")
-            if backend_.method == "minres" and system != _lib.SYSTEM_K2:
-                raise TypeError("KrylovBackend(method='minres') solves the augmented system (K2) only")
-            opt.krylov = _lib.KRYLOV_MINRES if backend_.method == "minres" else _lib.KRYLOV_CG
+                raise TypeError("the Krylov backend solves the normal equations (K1) only (method='minres' and method='tricg' solve K2)")
+            if backend_.method != "cg" and system != _lib.SYSTEM_K2:
+                raise TypeError(f"KrylovBackend(method='{backend_.method}') solves the augmented system (K2) only")
+            opt.krylov = {"cg": _lib.KRYLOV_CG, "minres": _lib.KRYLOV_MINRES, "tricg": _lib.KRYLOV_TRICG}[backend_.method]
             opt.krylov_precond = backend_.precond
             opt.krylov_itmax = backend_.itmax
             opt.krylov_atol, opt.krylov_rtol = backend_.atol, backend_.rtol
@@ -504,7 +510,7 @@ def backend(kkt):
     name = _lib.lib().tlpk_backend_name().decode()
     be = getattr(kkt, "backend_options", None)
     if isinstance(be, KrylovBackend):                  # the method, as Krylov's `backend` names its solver type (src/KKT/Krylov/spd.jl:48)
-        name += (" MINRES" if be.method == "minres" else " CG") + (", Jacobi" if be.precond == _lib.PRECOND_JACOBI else "")
+        name += {"cg": " CG", "minres": " MINRES", "tricg": " TriCG"}[be.method] + (", Jacobi" if be.precond == _lib.PRECOND_JACOBI else "")
     return name
 
 
