@@ -415,6 +415,39 @@ int tlpk_ipm_advance(tlpk_handle *h, double alpha, double *out);   /* step.jl:13
 /* what = 0 x, 1 xl, 2 xu, 3 zl, 4 zu (n), 5 y (m) */
 int tlpk_ipm_get(tlpk_handle *h, int what, double *host, int64_t len);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batched device-resident HSD: MANY SMALL LPs in one set of launches.  B LPs stacked into one block-diagonal A are an ordinary handle
+ * (row_block = LP index and no linking rows: the analysis is a forest, the level-batched kernels serve every block in the launches one
+ * block needs).  tlpk_ipm_load_batch takes the place of tlpk_ipm_load on such a handle and the tlpk_ipm_batch_* calls run the routines
+ * above with PER-LP scalars: LP k owns the contiguous rows [row_off[k], row_off[k+1]) and columns [col_off[k], col_off[k+1]) of the
+ * stacked vectors, every array argument below has one entry (or one group of entries) per LP, and an LP with active[k] = 0 is not
+ * touched: no kernel writes its iterate, direction or right-hand sides, its outputs are 0.  The reductions of an LP do not depend on
+ * what else is in the batch; with nlp = 1 every call returns what its unbatched counterpart returns, bit for bit.
+ *   tlpk_ipm_load_batch checks, in this order (TLPK_BADARG with a sentence in tlpk_last_error): pointers not NULL and nlp >= 1; offsets
+ *   start at 0, do not decrease, leave no LP without rows or columns and end at m and n; every stored entry of A lies in its LP's diagonal
+ *   block; the handle is a single-device direct one (K1 or K2; row_block and refine_steps are fine; multi-device, sharded, dense-matrix,
+ *   Krylov and dense_cols handles are refused); nothing is loaded yet (either load after the other: TLPK_BADARG).  Then TLPK_NO_DEVICE on
+ *   an analyse-only handle.
+ *   tlpk_ipm_reset, tlpk_ipm_reload and tlpk_ipm_get serve a batch-loaded handle unchanged (stacked vectors); every other tlpk_ipm_* /
+ *   tlpk_mpc_* call on it returns TLPK_BADARG, as does every tlpk_ipm_batch_* call on a handle loaded with tlpk_ipm_load (or not loaded).
+ *   tlpk_ipm_batch_factor: regP[k] / regD[k] are uniform within LP k.  An LP with active[k] = 0 is PARKED: theta_inv = 1, Rp = Rd = 1 on
+ *   its block (the matrix the handle is analysed with), so a finished or failed LP cannot fail the update of the others.  On
+ *   TLPK_NOT_POSDEF *fail_lp is the LP that owns tlpk_stats.fail_col (through the permutation; K2: node j < n is a column, n + i a row),
+ *   or -1 if that cannot be told; one failure is reported per update.  Otherwise *fail_lp = -1.
+ * --------------------------------------------------------------------------------------------- */
+int tlpk_ipm_load_batch(tlpk_handle *h, int64_t nlp, const int64_t *row_off /*nlp+1*/, const int64_t *col_off /*nlp+1*/,
+                        const double *b, const double *c, const double *l, const double *u);   /* stacked, lengths m, n, n, n */
+int tlpk_ipm_batch_residuals(tlpk_handle *h, const double *tau /*nlp*/, double *out /*13 nlp, the layout of tlpk_ipm_residuals per LP*/);
+int tlpk_ipm_batch_factor(tlpk_handle *h, const uint8_t *active, const double *regP /*nlp*/, const double *regD /*nlp*/, int64_t *fail_lp);
+/* sc[8 k ..], out[4 k ..]: as tlpk_ipm_hsolve_newton for LP k */
+int tlpk_ipm_batch_hsolve_newton(tlpk_handle *h, const uint8_t *active, const double *sc /*8 nlp*/, double *out /*4 nlp*/);
+/* one mode for the call; sc[8 k ..], out[3 k ..]: as tlpk_ipm_newton for LP k */
+int tlpk_ipm_batch_newton(tlpk_handle *h, int mode, const uint8_t *active, const double *sc /*8 nlp*/, double *out /*3 nlp*/);
+int tlpk_ipm_batch_targets(tlpk_handle *h, const uint8_t *active, const double *par /*3 nlp: a_, mu_l, mu_u*/, double *out /*2 nlp*/);
+/* the candidates of the LPs with active[k] != 0 become their accepted directions (a copy: the LPs accept independently) */
+int tlpk_ipm_batch_accept(tlpk_handle *h, const uint8_t *active);
+int tlpk_ipm_batch_advance(tlpk_handle *h, const uint8_t *active, const double *alpha /*nlp*/, double *out /*nlp*/);
+
 /* ---- Mehrotra predictor-corrector with the iterate in HBM (/root/reference/src/IPM/MPC/MPC.jl:218-410,
  * MPC/step.jl:10-358).  Same vectors as above: tlpk_ipm_load once, tlpk_ipm_residuals with tau = 1 (MPC.jl:101-141),
  * tlpk_ipm_factor (step.jl:24-51), tlpk_ipm_accept and tlpk_ipm_get are shared. */

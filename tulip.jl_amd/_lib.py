@@ -78,6 +78,8 @@ EXPORTS = [
     "tlpk_refine_local", "tlpk_refine_finish", "tlpk_solve2_local", "tlpk_root_rhs2", "tlpk_solve2_finish", "tlpk_last_create_error",
     "tlpk_host_copy_threads", "tlpk_create_dense",
     "tlpk_set_values", "tlpk_set_values_device", "tlpk_set_values_dense", "tlpk_set_values_dense_device", "tlpk_ipm_reload",
+    "tlpk_ipm_load_batch", "tlpk_ipm_batch_residuals", "tlpk_ipm_batch_factor", "tlpk_ipm_batch_hsolve_newton", "tlpk_ipm_batch_newton",
+    "tlpk_ipm_batch_targets", "tlpk_ipm_batch_accept", "tlpk_ipm_batch_advance",
 ]
 
 
@@ -184,6 +186,17 @@ def lib():
                  "tlpk_ipm_targets", "tlpk_ipm_newton", "tlpk_ipm_accept", "tlpk_ipm_advance", "tlpk_ipm_get",
                  "tlpk_mpc_start", "tlpk_mpc_newton", "tlpk_mpc_gap", "tlpk_mpc_targets", "tlpk_mpc_advance"):
         getattr(L, name).restype = C.c_int
+    pu8 = C.POINTER(C.c_uint8)
+    L.tlpk_ipm_load_batch.argtypes = [vp, C.c_int64, p64, p64, pd, pd, pd, pd]
+    L.tlpk_ipm_batch_residuals.argtypes = [vp, pd, pd]
+    L.tlpk_ipm_batch_factor.argtypes = [vp, pu8, pd, pd, p64]
+    L.tlpk_ipm_batch_hsolve_newton.argtypes = [vp, pu8, pd, pd]
+    L.tlpk_ipm_batch_newton.argtypes = [vp, C.c_int, pu8, pd, pd]
+    L.tlpk_ipm_batch_targets.argtypes = [vp, pu8, pd, pd]
+    L.tlpk_ipm_batch_accept.argtypes = [vp, pu8]
+    L.tlpk_ipm_batch_advance.argtypes = [vp, pu8, pd, pd]
+    for name in EXPORTS[-8:]:
+        getattr(L, name).restype = C.c_int
     for name in ("tlpk_create", "tlpk_update", "tlpk_solve", "tlpk_update_device", "tlpk_solve_device",
                  "tlpk_sync", "tlpk_update_local", "tlpk_root_panel", "tlpk_update_finish",
                  "tlpk_solve_local", "tlpk_root_rhs", "tlpk_solve_finish", "tlpk_info",
@@ -199,6 +212,10 @@ def as_p64(a):
 
 def as_pd(a):
     return a.ctypes.data_as(pd)
+
+
+def as_pu8(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
 def strerror(code):

@@ -17,42 +17,10 @@
 // finalize kernel (deterministic, no floating-point atomics).
 #include <hip/hip_runtime.h>
 
+#include "ipm_shared.hpp"
 #include "tlpk_ipm.hpp"
 
 namespace tlpk {
-
-constexpr int IPM_T = 256;
-
-__device__ __forceinline__ double blk_sum(double v, double *sh) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = IPM_T / 2; s > 0; s >>= 1) { if (tid < s) sh[tid] += sh[tid + s]; __syncthreads(); }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double blk_max(double v, double *sh) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = IPM_T / 2; s > 0; s >>= 1) { if (tid < s) sh[tid] = fmax(sh[tid], sh[tid + s]); __syncthreads(); }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double blk_min(double v, double *sh) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = IPM_T / 2; s > 0; s >>= 1) { if (tid < s) sh[tid] = fmin(sh[tid], sh[tid + s]); __syncthreads(); }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
 
 // partials[block][slot]; slots [0, nsum) are sums, [nsum, nsum + nmax) maxima, the rest minima.  One wave per slot: lane l combines the blocks l, l + 64, ... in
 // that order, then a fixed butterfly over the 64 lanes -- the same order in every run (bitwise deterministic), whatever the number of blocks.  (Until round 5 one
@@ -85,18 +53,7 @@ __global__ __launch_bounds__(IPM_T) void k_ipm_res_cols(IpmVecs v, double tau, d
     __shared__ double sh[IPM_T];
     double s0 = 0, s1 = 0, s2 = 0, s3 = 0, m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0, m5 = 0;
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) {
-        double aty = 0.0;
-        if (v.aty) aty = v.aty[j];
-        else for (i64 p = v.Ap[j]; p < v.Ap[j + 1]; ++p) aty += v.Ax[p] * v.y[v.Ai[p]];
-        const double x = v.x[j], xl = v.xl[j], xu = v.xu[j], zl = v.zl[j], zu = v.zu[j], lf = v.lflag[j], uf = v.uflag[j];
-        const double rl = (-x + xl + tau * v.lz[j]) * lf, ru = (-x - xu + tau * v.uz[j]) * uf;
-        const double rd = tau * v.c[j] - aty + zu * uf - zl * lf;
-        v.rl[j] = rl; v.ru[j] = ru; v.rd[j] = rd;
-        s0 += v.c[j] * x; s1 += v.lz[j] * zl; s2 += v.uz[j] * zu; s3 += xl * zl + xu * zu;
-        m0 = fmax(m0, fabs(rl)); m1 = fmax(m1, fabs(ru)); m2 = fmax(m2, fabs(rd));
-        m3 = fmax(m3, fabs((x - xl) * lf)); m4 = fmax(m4, fabs((x + xu) * uf)); m5 = fmax(m5, fabs(aty + zl * lf - zu * uf));
-    }
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) ipm_res_col(v, j, tau, s0, s1, s2, s3, m0, m1, m2, m3, m4, m5);
     double *P = partials + (size_t)blockIdx.x * IPM_SLOTS;
     double r;
     r = blk_sum(s0, sh); if (threadIdx.x == 0) P[0] = r;
@@ -118,21 +75,7 @@ __global__ __launch_bounds__(IPM_T) void k_ipm_res_rows(IpmVecs v, double tau, d
     const int lane = threadIdx.x & 7;
     const i64 stride = ((i64)gridDim.x * blockDim.x) >> 3;
     const i64 mround = (v.m + stride - 1) / stride * stride;                 // every group runs the same number of trips: the shuffles stay convergent
-    for (i64 i = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 3; i < mround; i += stride) {
-        const bool live = i < v.m;
-        double ax = 0.0;
-        if (live && v.ax) ax = (lane == 0) ? v.ax[i] : 0.0;
-        else if (live)
-            for (i64 q = v.Tp[i] + lane; q < v.Tp[i + 1]; q += 8) ax += v.Tx[q] * v.x[v.Tj[q]];
-#pragma unroll
-        for (int off = 4; off > 0; off >>= 1) ax += __shfl_down(ax, off, 8);
-        if (!live || lane != 0) continue;
-        const double rp = tau * v.b[i] - ax;
-        v.rp[i] = rp;
-        s0 += v.b[i] * v.y[i];
-        if (v.row_skip && v.row_skip[i]) continue;                          // a shard's PARTIAL linking row: the host sums the shards' rows
-        m0 = fmax(m0, fabs(rp)); m1 = fmax(m1, fabs(ax));
-    }
+    for (i64 i = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 3; i < mround; i += stride) ipm_res_row(v, i, i < v.m, lane, tau, s0, m0, m1);
     double *P = partials + (size_t)blockIdx.x * IPM_SLOTS;
     double r;
     r = blk_sum(s0, sh); if (threadIdx.x == 0) P[0] = r;
@@ -143,25 +86,19 @@ __global__ __launch_bounds__(IPM_T) void k_ipm_res_rows(IpmVecs v, double tau, d
 // theta_inv = zl/xl + zu/xu (exactly 0 for free variables), uniform regularisation vectors   step.jl:24-31
 __global__ void k_ipm_theta(IpmVecs v, double *__restrict__ theta, double *__restrict__ regP, double *__restrict__ regD, double rP, double rD) {
     const i64 stride = (i64)gridDim.x * blockDim.x, t0 = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    for (i64 j = t0; j < v.n; j += stride) {
-        const double tl = (v.lflag[j] != 0.0) ? v.zl[j] / v.xl[j] : 0.0, tu = (v.uflag[j] != 0.0) ? v.zu[j] / v.xu[j] : 0.0;
-        v.thl[j] = tl; v.thu[j] = tu; theta[j] = tl + tu; regP[j] = rP;
-    }
+    for (i64 j = t0; j < v.n; j += stride) { ipm_theta_col(v, j, theta); regP[j] = rP; }
     for (i64 i = t0; i < v.m; i += stride) regD[i] = rD;
 }
 __global__ void k_ipm_hrhs(IpmVecs v) {                                     // step.jl:61: xi_ = c - th_l lz - th_u uz
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) v.hxid[j] = v.c[j] - v.thl[j] * v.lz[j] - v.thu[j] * v.uz[j];
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) ipm_hrhs_col(v, j);
 }
 // h0 pieces (step.jl:69-76): sum_j lz^2 th_l + uz^2 th_u - (c + th_l lz + th_u uz) hx ; sum_i b hy
 __global__ __launch_bounds__(IPM_T) void k_ipm_hdots(IpmVecs v, double *__restrict__ partials) {
     __shared__ double sh[IPM_T];
     double s0 = 0, s1 = 0;
     const i64 stride = (i64)gridDim.x * blockDim.x, t0 = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    for (i64 j = t0; j < v.n; j += stride) {
-        const double lz = v.lz[j], uz = v.uz[j], tl = v.thl[j], tu = v.thu[j];
-        s0 += lz * (lz * tl) + uz * (uz * tu) - (v.c[j] + tl * lz + tu * uz) * v.hx[j];
-    }
+    for (i64 j = t0; j < v.n; j += stride) ipm_hdots_col(v, j, s0);
     for (i64 i = t0; i < v.m; i += stride) s1 += v.b[i] * v.hy[i];
     double *P = partials + (size_t)blockIdx.x * IPM_SLOTS;
     double r;
@@ -176,14 +113,7 @@ __global__ __launch_bounds__(IPM_T) void k_ipm_targets(IpmVecs v, IpmDir D, doub
     __shared__ double sh[IPM_T];
     double s0 = 0, s1 = 0;
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) {
-        double vl = ((v.xl[j] + a_p * D.xl[j]) * (v.zl[j] + a_d * D.zl[j])) * v.lflag[j];
-        double vu = ((v.xu[j] + a_p * D.xu[j]) * (v.zu[j] + a_d * D.zu[j])) * v.uflag[j];
-        if (v.lflag[j] != 0.0) vl = (vl < mu_l) ? mu_l - vl : ((vl > mu_u) ? mu_u - vl : 0.0);
-        if (v.uflag[j] != 0.0) vu = (vu < mu_l) ? mu_l - vu : ((vu > mu_u) ? mu_u - vu : 0.0);
-        v.xzl[j] = vl; v.xzu[j] = vu;
-        s0 += vl; s1 += vu;
-    }
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) ipm_targets_col(v, D, j, a_p, a_d, mu_l, mu_u, s0, s1);
     double *P = partials + (size_t)blockIdx.x * IPM_SLOTS;
     double r;
     r = blk_sum(s0, sh); if (threadIdx.x == 0) P[0] = r;
@@ -197,21 +127,8 @@ __global__ __launch_bounds__(IPM_T) void k_ipm_newton_pre(IpmVecs v, IpmDir D, i
     __shared__ double sh[IPM_T];
     double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
     const i64 stride = (i64)gridDim.x * blockDim.x, t0 = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    for (i64 j = t0; j < v.n; j += stride) {
-        const double lf = v.lflag[j], uf = v.uflag[j], xl = v.xl[j], xu = v.xu[j], zl = v.zl[j], zu = v.zu[j];
-        double xil, xiu, xd, xzl, xzu;
-        if (mode == 0) { xil = v.rl[j]; xiu = v.ru[j]; xd = v.rd[j]; xzl = -(xl * zl) * lf; xzu = -(xu * zu) * uf; }
-        else if (mode == 1) {
-            xil = eta * v.rl[j]; xiu = eta * v.ru[j]; xd = eta * v.rd[j];
-            xzl = (-xl * zl + gmu - D.xl[j] * D.zl[j]) * lf; xzu = (-xu * zu + gmu - D.xu[j] * D.zu[j]) * uf;
-        } else { xil = 0.0; xiu = 0.0; xd = 0.0; xzl = v.xzl[j] - delta; xzu = v.xzu[j] - delta; }
-        v.xil[j] = xil; v.xiu[j] = xiu; v.xzl[j] = xzl; v.xzu[j] = xzu;
-        const double tl = (lf != 0.0) ? (xzl + zl * xil) / xl : 0.0, tu = (uf != 0.0) ? (xzu - zu * xiu) / xu : 0.0;
-        v.xid[j] = xd - tl + tu;                                            // step.jl:214
-        const double ixl = (lf != 0.0) ? xzl / xl : 0.0, ixu = (uf != 0.0) ? xzu / xu : 0.0;
-        s0 += ixl * v.lz[j]; s1 += ixu * v.uz[j]; s2 += (v.thl[j] * xil) * v.lz[j]; s3 += (v.thu[j] * xiu) * v.uz[j];
-    }
-    for (i64 i = t0; i < v.m; i += stride) v.xip[i] = (mode == 0) ? v.rp[i] : (mode == 1 ? eta * v.rp[i] : 0.0);
+    for (i64 j = t0; j < v.n; j += stride) ipm_newton_pre_col(v, D, j, mode, eta, gmu, delta, s0, s1, s2, s3);
+    for (i64 i = t0; i < v.m; i += stride) ipm_newton_pre_row(v, i, mode, eta);
     double *P = partials + (size_t)blockIdx.x * IPM_SLOTS;
     double r;
     r = blk_sum(s0, sh); if (threadIdx.x == 0) P[0] = r;
@@ -224,7 +141,7 @@ __global__ __launch_bounds__(IPM_T) void k_ipm_newton_dots(IpmVecs v, IpmDir D, 
     __shared__ double sh[IPM_T];
     double s0 = 0, s1 = 0;
     const i64 stride = (i64)gridDim.x * blockDim.x, t0 = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    for (i64 j = t0; j < v.n; j += stride) s0 += (v.c[j] + v.thl[j] * v.lz[j] + v.thu[j] * v.uz[j]) * D.x[j];
+    for (i64 j = t0; j < v.n; j += stride) ipm_newton_dots_col(v, D, j, s0);
     for (i64 i = t0; i < v.m; i += stride) s1 += v.b[i] * D.y[i];
     double *P = partials + (size_t)blockIdx.x * IPM_SLOTS;
     double r;
@@ -237,19 +154,8 @@ __global__ __launch_bounds__(IPM_T) void k_ipm_newton_post(IpmVecs v, IpmDir D, 
     __shared__ double sh[IPM_T];
     double amin_p = __builtin_inf(), amin_d = __builtin_inf();               // primal (xl, xu) and dual (zl, zu) sides
     const i64 stride = (i64)gridDim.x * blockDim.x, t0 = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    for (i64 j = t0; j < v.n; j += stride) {
-        const double lf = v.lflag[j], uf = v.uflag[j];
-        double dx = D.x[j] + dtau * v.hx[j];
-        double dxl = (-v.xil[j] + dx - dtau * v.lz[j]) * lf, dxu = (v.xiu[j] - dx + dtau * v.uz[j]) * uf;
-        double dzl = (lf != 0.0) ? (v.xzl[j] - v.zl[j] * dxl) / v.xl[j] : 0.0, dzu = (uf != 0.0) ? (v.xzu[j] - v.zu[j] * dxu) / v.xu[j] : 0.0;
-        if (add) { dx += Add.x[j]; dxl += Add.xl[j]; dxu += Add.xu[j]; dzl += Add.zl[j]; dzu += Add.zu[j]; }
-        D.x[j] = dx; D.xl[j] = dxl; D.xu[j] = dxu; D.zl[j] = dzl; D.zu[j] = dzu;
-        if (dxl < 0.0) amin_p = fmin(amin_p, -v.xl[j] / dxl);
-        if (dxu < 0.0) amin_p = fmin(amin_p, -v.xu[j] / dxu);
-        if (dzl < 0.0) amin_d = fmin(amin_d, -v.zl[j] / dzl);
-        if (dzu < 0.0) amin_d = fmin(amin_d, -v.zu[j] / dzu);
-    }
-    for (i64 i = t0; i < v.m; i += stride) { double dy = D.y[i] + dtau * v.hy[i]; if (add) dy += Add.y[i]; D.y[i] = dy; }
+    for (i64 j = t0; j < v.n; j += stride) ipm_newton_post_col(v, D, Add, j, add, dtau, amin_p, amin_d);
+    for (i64 i = t0; i < v.m; i += stride) ipm_newton_post_row(v, D, Add, i, add, dtau);
     double r = blk_min(amin_p, sh);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 0] = r;
     r = blk_min(amin_d, sh);
@@ -261,12 +167,7 @@ __global__ __launch_bounds__(IPM_T) void k_ipm_advance(IpmVecs v, IpmDir D, doub
     __shared__ double sh[IPM_T];
     double s0 = 0;
     const i64 stride = (i64)gridDim.x * blockDim.x, t0 = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    for (i64 j = t0; j < v.n; j += stride) {
-        v.x[j] += alpha * D.x[j];
-        const double xl = v.xl[j] + alpha * D.xl[j], xu = v.xu[j] + alpha * D.xu[j], zl = v.zl[j] + alpha_d * D.zl[j], zu = v.zu[j] + alpha_d * D.zu[j];
-        v.xl[j] = xl; v.xu[j] = xu; v.zl[j] = zl; v.zu[j] = zu;
-        s0 += xl * zl + xu * zu;
-    }
+    for (i64 j = t0; j < v.n; j += stride) ipm_advance_col(v, D, j, alpha, alpha_d, s0);
     for (i64 i = t0; i < v.m; i += stride) v.y[i] += alpha_d * D.y[i];
     const double r = blk_sum(s0, sh);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 0] = r;

@@ -9,10 +9,12 @@
 // regularisation scalars and the control flow (tulip.jl_amd/hsd_device.py mirrors HSD.jl:203-350).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "tlpk_handle.hpp"
@@ -28,6 +30,17 @@ struct IpmState {
     int pre_blocks = 0;
     // multi-device parent only: the linking rows (user indices, ascending), b on them, staging for the shards' partial rp
     std::vector<i64> link_rows; std::vector<double> b_link; double *h_link = nullptr; i64 link_lo = 0, link_hi = 0;
+    struct IpmBatchState *bat = nullptr;      // tlpk_ipm_load_batch: the handle holds a stack of LPs (the tlpk_ipm_batch_* calls serve it)
+};
+
+// a stack of LPs on one single-device handle: segment offsets, the block tables of ipm_batch_kernels.hip and buffers sized by the number of LPs
+struct IpmBatchState {
+    i64 nlp = 0;
+    std::vector<i64> row_off, col_off;
+    IpmBatch B{};
+    double *partials[2] = {nullptr, nullptr};     // rows = blocks of the longest table
+    double *d_out = nullptr, *h_out = nullptr;    // 2 x nlp x IPM_SLOTS finalised scalars (device / pinned)
+    double *d_sc = nullptr, *h_sc = nullptr;      // nlp x IPM_BSC scalars of the current call (device / pinned)
 };
 
 // ---- one device or several ---------------------------------------------------------------------------------------------------
@@ -47,7 +60,7 @@ namespace {
 
 struct Shards { tlpk_handle *c[MAX_DEVICES]; int n = 0; bool multi = false; };
 
-int ipm_shards(tlpk_handle *h, Shards &sh, bool need_loaded = true, bool allow_stale = false) {
+int ipm_shards(tlpk_handle *h, Shards &sh, bool need_loaded = true, bool allow_stale = false, bool allow_batch = false) {
     if (!h) return TLPK_BADARG;
     if (!h->has_device) return TLPK_NO_DEVICE;
     if (h->opt.nranks > 1) { h->last_error = "the device-resident IPM vectors need a single-rank or a tlpk_create_multi handle (a sharded handle's reductions belong to its caller)"; return TLPK_BADARG; }
@@ -56,6 +69,10 @@ int ipm_shards(tlpk_handle *h, Shards &sh, bool need_loaded = true, bool allow_s
         for (int r = 0; r < sh.n; ++r) sh.c[r] = h->sub[(size_t)r];
     } else { sh.multi = false; sh.n = 1; sh.c[0] = h; }
     if (need_loaded && !h->ipm) { h->last_error = "tlpk_ipm_load has not been called"; return TLPK_BADARG; }
+    if (need_loaded && h->ipm->bat && !allow_batch) {
+        h->last_error = "the handle holds a stack of LPs (tlpk_ipm_load_batch): use the tlpk_ipm_batch_* calls (tlpk_ipm_reset, tlpk_ipm_reload and tlpk_ipm_get are shared)";
+        return TLPK_BADARG;
+    }
     if (need_loaded && h->ipm_stale && !allow_stale) {
         h->last_error = "the matrix values changed (tlpk_set_values) after the LP was loaded: call tlpk_ipm_reload before the device-resident loops";
         return TLPK_BADARG;
@@ -146,6 +163,11 @@ void ipm_free(tlpk_handle *h) {
     if (!h || !h->ipm) return;
     if (h->ipm->h_out) hipHostFree(h->ipm->h_out);
     if (h->ipm->h_link) hipHostFree(h->ipm->h_link);
+    if (IpmBatchState *bs = h->ipm->bat) {
+        if (bs->h_out) hipHostFree(bs->h_out);
+        if (bs->h_sc) hipHostFree(bs->h_sc);
+        delete bs;
+    }
     delete h->ipm;                  // device vectors are in h->allocs
     h->ipm = nullptr;
 }
@@ -385,7 +407,7 @@ int tlpk_ipm_reload(tlpk_handle *h, const double *b, const double *c, const doub
 
 int tlpk_ipm_reset(tlpk_handle *h) {
     Shards sh;
-    if (int rc = ipm_shards(h, sh)) return rc;
+    if (int rc = ipm_shards(h, sh, true, false, true)) return rc;
     for (int r = 0; r < sh.n; ++r) {
         tlpk_handle *c = sh.c[r];
         HIPCHK(h, hipSetDevice(c->device));
@@ -638,7 +660,7 @@ int tlpk_ipm_advance(tlpk_handle *h, double alpha, double *out) { return advance
 /* download one vector of the iterate: what = 0 x, 1 xl, 2 xu, 3 zl, 4 zu (length n), 5 y (length m) */
 int tlpk_ipm_get(tlpk_handle *h, int what, double *host, int64_t len) {
     Shards sh;
-    if (int rc = ipm_shards(h, sh, true, true)) return rc;
+    if (int rc = ipm_shards(h, sh, true, true, true)) return rc;
     if (!host || what < 0 || what > 5) return TLPK_BADARG;
     const IpmVecs &v0 = sh.c[0]->ipm->v;
     const int64_t need = (what == 5) ? v0.m : v0.n;
@@ -772,5 +794,327 @@ int tlpk_mpc_targets(tlpk_handle *h, double ap_, double ad_, double tmin, double
 
 /* MPC/step.jl:112-123: primal side += ap * D, dual side += ad * D; out[0] = xl'zl + xu'zu of the new point */
 int tlpk_mpc_advance(tlpk_handle *h, double ap, double ad, double *out) { return advance_all(h, ap, ad, out); }
+
+/* ---- a stack of LPs on one handle (include/tlpk.h, "Batched device-resident HSD"; DESIGN.md section 4b') -------------------------------
+ * B LPs stacked into one block-diagonal A are an ordinary handle: the level-batched factorisation and solve kernels serve every block in
+ * the launches one block needs.  What these calls add is the interior-point loop with PER-LP scalars: the kernels of
+ * ipm_batch_kernels.hip, the scalar algebra between them once per LP, and `active` masks (an LP whose flag is 0 is not touched). */
+}  // extern "C"
+
+namespace {
+
+// the stacked-LP state of a handle, or the reason why there is none
+int batch_state(tlpk_handle *h, IpmBatchState *&bs) {
+    if (!h) return TLPK_BADARG;
+    if (!h->ipm) { h->last_error = "tlpk_ipm_load_batch has not been called (load first)"; return TLPK_BADARG; }
+    if (!h->ipm->bat) { h->last_error = "the handle holds one LP (tlpk_ipm_load): the tlpk_ipm_batch_* calls need tlpk_ipm_load_batch"; return TLPK_BADARG; }
+    if (!h->has_device) return TLPK_NO_DEVICE;
+    if (h->ipm_stale) {
+        h->last_error = "the matrix values changed (tlpk_set_values) after the LPs were loaded: call tlpk_ipm_reload before the device-resident loops";
+        return TLPK_BADARG;
+    }
+    bs = h->ipm->bat;
+    return TLPK_OK;
+}
+// the scalars of this call: sc(k, q) for q < IPM_BSC - 1, the flags (nullptr: every LP).  The previous call (or half of a call) has been waited for.
+template <class F>
+int batch_scalars(tlpk_handle *h, IpmBatchState &bs, const uint8_t *active, F &&sc) {
+    for (i64 k = 0; k < bs.nlp; ++k) {
+        double *row = bs.h_sc + (size_t)k * IPM_BSC;
+        for (int q = 0; q < IPM_BSC - 1; ++q) row[q] = sc(k, q);
+        row[IPM_BSC - 1] = (!active || active[k]) ? 1.0 : 0.0;
+    }
+    HIPCHK(h, hipMemcpyAsync(bs.d_sc, bs.h_sc, (size_t)bs.nlp * IPM_BSC * 8, hipMemcpyHostToDevice, h->stream));
+    return TLPK_OK;
+}
+// the finalised scalars of `groups` reductions (group g at d_out + g nlp IPM_SLOTS): copy, wait
+int batch_gather(tlpk_handle *h, IpmBatchState &bs, int groups) {
+    HIPCHK(h, hipMemcpyAsync(bs.h_out, bs.d_out, (size_t)groups * (size_t)bs.nlp * IPM_SLOTS * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    return TLPK_OK;
+}
+// which LP owns node `col` of the factored matrix (tlpk_stats.fail_col: a permuted index), or -1
+i64 batch_owner(const tlpk_handle *h, const IpmBatchState &bs, i64 col) {
+    const Symbolic &S = h->S;
+    if (col < 0 || col >= (i64)S.perm.size()) return -1;
+    i64 old = S.perm[(size_t)col];
+    const std::vector<i64> *off = &bs.row_off;
+    if (S.system == 1) { if (old < S.k2_n) off = &bs.col_off; else old -= S.k2_n; }      // K2: node j < n is a column, n + i a row
+    if (old < 0 || old >= off->back()) return -1;
+    return (i64)(std::upper_bound(off->begin(), off->end(), old) - off->begin()) - 1;
+}
+// step.jl:232-246 for one LP, from the six sums of the pre / dots kernels
+inline void newton_scalars(const double *q, double tau, double kappa, double h0, double xi_g, double xi_tk, double &dtau, double &dkappa) {
+    const double xi_g_ = xi_g + xi_tk / tau - q[0] + q[1] - q[2] - q[3];
+    dtau = (xi_g_ + q[4] - q[5]) / h0;
+    dkappa = (xi_tk - kappa * dtau) / tau;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tlpk_ipm_load_batch(tlpk_handle *h, int64_t nlp, const int64_t *row_off, const int64_t *col_off,
+                        const double *b, const double *c, const double *l, const double *u) {
+    if (!h) return TLPK_BADARG;
+    // 1. the arguments themselves
+    if (!row_off || !col_off || !b || !c || !l || !u) { h->last_error = "tlpk_ipm_load_batch: a NULL pointer"; return TLPK_BADARG; }
+    if (nlp < 1) { h->last_error = "tlpk_ipm_load_batch: nlp must be at least 1"; return TLPK_BADARG; }
+    // 2. the offsets
+    const Symbolic &S = h->S;
+    const bool k2 = S.system == 1;
+    const i64 m = k2 ? S.k2_m : S.m - S.n_dense, n = k2 ? S.k2_n : S.n;
+    if (row_off[0] != 0 || col_off[0] != 0) { h->last_error = "tlpk_ipm_load_batch: the offsets must start at 0"; return TLPK_BADARG; }
+    for (i64 k = 0; k < nlp; ++k) {
+        if (row_off[k + 1] < row_off[k] || col_off[k + 1] < col_off[k]) { h->last_error = "tlpk_ipm_load_batch: the offsets must not decrease (LP " + std::to_string(k) + ")"; return TLPK_BADARG; }
+        if (row_off[k + 1] == row_off[k] || col_off[k + 1] == col_off[k]) { h->last_error = "tlpk_ipm_load_batch: LP " + std::to_string(k) + " is an empty segment (no rows or no columns)"; return TLPK_BADARG; }
+    }
+    if (row_off[nlp] != m || col_off[nlp] != n) {
+        h->last_error = "tlpk_ipm_load_batch: the offsets must end at m = " + std::to_string(m) + " and n = " + std::to_string(n);
+        return TLPK_BADARG;
+    }
+    // 3. every stored entry of A inside its LP's diagonal block: one walk of the handle's column-major copy (K2: the incidence matrix of
+    //    the augmented system -- column p holds entry p of A as the pair variable node j, constraint node n + i)
+    const bool has_csc = !S.dense_matrix && S.Ap.size() == (size_t)S.n + 1;
+    if (has_csc && !k2) {
+        i64 k = 0;
+        for (i64 j = 0; j < n; ++j) {
+            while (j >= col_off[k + 1]) ++k;
+            for (i64 q = S.Ap[(size_t)j]; q < S.Ap[(size_t)j + 1]; ++q) {
+                const i64 i = S.Ai[(size_t)q];
+                if (i >= m) continue;                                     // (not a constraint row of the caller's matrix)
+                if (i < row_off[k] || i >= row_off[k + 1]) {
+                    h->last_error = "tlpk_ipm_load_batch: entry (" + std::to_string(i) + ", " + std::to_string(j) + ") of A lies outside the diagonal block of LP " + std::to_string(k);
+                    return TLPK_BADARG;
+                }
+            }
+        }
+    } else if (has_csc) {
+        for (i64 p = 0; p < S.n; ++p) {
+            if (S.Ap[(size_t)p + 1] - S.Ap[(size_t)p] != 2) { h->last_error = "K2 incidence matrix: unexpected column"; return TLPK_INTERNAL; }
+            const i64 q = S.Ap[(size_t)p];
+            const i64 a = S.Ai[(size_t)q], b2 = S.Ai[(size_t)q + 1];
+            const i64 j = std::min(a, b2), i = std::max(a, b2) - n;
+            if (j < 0 || j >= n || i < 0 || i >= m) { h->last_error = "K2 incidence matrix: unexpected column"; return TLPK_INTERNAL; }
+            const i64 k = (i64)(std::upper_bound(col_off, col_off + nlp + 1, j) - col_off) - 1;
+            if (i < row_off[k] || i >= row_off[k + 1]) {
+                h->last_error = "tlpk_ipm_load_batch: entry (" + std::to_string(i) + ", " + std::to_string(j) + ") of A lies outside the diagonal block of LP " + std::to_string(k);
+                return TLPK_BADARG;
+            }
+        }
+    }
+    // the kind of handle
+    const char *why = nullptr;
+    if (!h->sub.empty()) why = "a multi-device handle";
+    else if (h->opt.nranks > 1) why = "a sharded handle";
+    else if (S.dense_matrix) why = "a dense-matrix handle";
+    else if (h->krylov) why = "a matrix-free (Krylov) handle";
+    else if (S.n_dense > 0) why = "a handle with dense columns (dense_cols)";
+    if (why) { h->last_error = std::string("tlpk_ipm_load_batch: ") + why + " cannot hold a stack of LPs (single-device direct handles, K1 or K2, only)"; return TLPK_BADARG; }
+    if (h->ipm) { h->last_error = "tlpk_ipm_load_batch: an LP is already loaded on this handle (tlpk_ipm_load or tlpk_ipm_load_batch)"; return TLPK_BADARG; }
+    if (!h->has_device) return TLPK_NO_DEVICE;
+
+    int rc = ipm_load_impl(h, b, c, l, u, false);
+    IpmBatchState *bs = nullptr;
+    if (rc == TLPK_OK) { bs = new (std::nothrow) IpmBatchState(); if (!bs) rc = TLPK_OOM; }
+    if (rc == TLPK_OK) {
+        h->ipm->bat = bs;
+        rc = [&]() -> int {
+            bs->nlp = nlp;
+            bs->row_off.assign(row_off, row_off + nlp + 1); bs->col_off.assign(col_off, col_off + nlp + 1);
+            IpmBatch &B = bs->B;
+            B.nlp = nlp;
+            i64 *dp;
+            if (int r = dev_upload(h, &dp, bs->row_off)) return r; B.row_off = dp;
+            if (int r = dev_upload(h, &dp, bs->col_off)) return r; B.col_off = dp;
+            // block tables: LP k gets the blocks the unbatched kernels launch for its lengths
+            auto table = [&](IpmBlockTab &t, auto len) -> int {
+                std::vector<int> seg, loc, first((size_t)nlp + 1, 0);
+                for (i64 k = 0; k < nlp; ++k) {
+                    const int nb = ipm_seg_blocks(len(k));
+                    if ((i64)seg.size() + nb > (i64)1 << 30) { h->last_error = "tlpk_ipm_load_batch: too many workgroups"; return TLPK_TOO_LARGE; }
+                    for (int q = 0; q < nb; ++q) { seg.push_back((int)k); loc.push_back(q); }
+                    first[(size_t)k + 1] = (int)seg.size();
+                }
+                int *di;
+                t.nblocks = (int)seg.size();
+                if (int r = dev_upload(h, &di, seg)) return r; t.seg = di;
+                if (int r = dev_upload(h, &di, loc)) return r; t.loc = di;
+                if (int r = dev_upload(h, &di, first)) return r; t.first = di;
+                return TLPK_OK;
+            };
+            if (int r = table(B.tc, [&](i64 k) { return col_off[k + 1] - col_off[k]; })) return r;
+            if (int r = table(B.tr, [&](i64 k) { return row_off[k + 1] - row_off[k]; })) return r;
+            if (int r = table(B.tb, [&](i64 k) { return std::max(col_off[k + 1] - col_off[k], row_off[k + 1] - row_off[k]); })) return r;
+            const i64 rows = std::max(B.tb.nblocks, std::max(B.tc.nblocks, B.tr.nblocks));
+            double *p;
+            for (int g = 0; g < 2; ++g) {
+                if (int r = dev_alloc(h, &p, rows * IPM_SLOTS)) return r;
+                HIPCHK(h, hipMemset(p, 0, (size_t)rows * IPM_SLOTS * 8));
+                bs->partials[g] = p;
+            }
+            if (int r = dev_alloc(h, &p, 2 * nlp * IPM_SLOTS)) return r;
+            HIPCHK(h, hipMemset(p, 0, (size_t)(2 * nlp * IPM_SLOTS) * 8)); bs->d_out = p;
+            if (int r = dev_alloc(h, &p, nlp * IPM_BSC)) return r;
+            HIPCHK(h, hipMemset(p, 0, (size_t)(nlp * IPM_BSC) * 8)); bs->d_sc = p; B.sc = p;
+            HIPCHK(h, hipHostMalloc((void **)&bs->h_out, (size_t)(2 * nlp * IPM_SLOTS) * 8, hipHostMallocDefault));
+            HIPCHK(h, hipHostMalloc((void **)&bs->h_sc, (size_t)(nlp * IPM_BSC) * 8, hipHostMallocDefault));
+            return TLPK_OK;
+        }();
+    }
+    if (rc != TLPK_OK) ipm_free(h);
+    return rc;
+}
+
+/* tlpk_ipm_residuals per LP: out[13 k ..] in its layout, from tau[k] */
+int tlpk_ipm_batch_residuals(tlpk_handle *h, const double *tau, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!tau || !out) return TLPK_BADARG;
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm; const i64 nlp = bs.nlp;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, nullptr, [&](i64 k, int q) { return q == 0 ? tau[k] : 0.0; })) return rc;
+    ipmb_launch_res_cols(h->stream, s.v, bs.B, bs.partials[0]);
+    ipmb_launch_res_rows(h->stream, s.v, bs.B, bs.partials[1]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tc, 4, 6, 0, bs.partials[0], bs.d_out);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tr, 1, 2, 0, bs.partials[1], bs.d_out + nlp * IPM_SLOTS);
+    if (int rc = batch_gather(h, bs, 2)) return rc;
+    for (i64 k = 0; k < nlp; ++k) {
+        const double *a = bs.h_out + (size_t)k * IPM_SLOTS, *r = bs.h_out + (size_t)(nlp + k) * IPM_SLOTS;
+        double *o = out + 13 * k;
+        o[0] = r[1]; o[1] = a[4]; o[2] = a[5]; o[3] = a[6]; o[4] = a[0]; o[5] = r[0]; o[6] = a[1]; o[7] = a[2];
+        o[8] = a[3]; o[9] = r[2]; o[10] = a[7]; o[11] = a[8]; o[12] = a[9];
+    }
+    return TLPK_OK;
+}
+
+/* tlpk_ipm_factor with regP[k] / regD[k] uniform within LP k; an LP with active[k] = 0 is parked (theta_inv = Rp = Rd = 1 on its block).
+ * TLPK_NOT_POSDEF: *fail_lp = the LP that owns tlpk_stats.fail_col (-1 if it cannot be told); otherwise *fail_lp = -1. */
+int tlpk_ipm_batch_factor(tlpk_handle *h, const uint8_t *active, const double *regP, const double *regD, int64_t *fail_lp) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!active || !regP || !regD || !fail_lp) return TLPK_BADARG;
+    IpmBatchState &bs = *bp;
+    *fail_lp = -1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q == 0 ? regP[k] : (q == 1 ? regD[k] : 0.0); })) return rc;
+    ipmb_launch_theta(h->stream, h->ipm->v, bs.B, h->d_theta, h->d_regP, h->d_regD);
+    const int rc = tlpk_update_device(h, h->d_theta, h->d_regP, h->d_regD);
+    if (rc == TLPK_NOT_POSDEF) *fail_lp = batch_owner(h, bs, h->fail_col);
+    return rc;
+}
+
+/* tlpk_ipm_hsolve_newton per LP: sc[8 k ..] and out[4 k ..] in its layouts; inactive LPs: out = 0 */
+int tlpk_ipm_batch_hsolve_newton(tlpk_handle *h, const uint8_t *active, const double *sc, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!active || !sc || !out) return TLPK_BADARG;
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm; const i64 nlp = bs.nlp;
+    const IpmDir &dst = s.D[s.cur];
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q < 3 ? sc[8 * k + 5 + q] : 0.0; })) return rc;      // eta, gamma mu, delta
+    ipmb_launch_hrhs(h->stream, s.v, bs.B);
+    ipmb_launch_newton_pre(h->stream, s.v, dst, bs.B, 0, bs.partials[0]);
+    int rc = tlpk_solve2_device(h, s.v.hx, s.v.hy, s.v.b, s.v.hxid, dst.x, dst.y, s.v.xip, s.v.xid);
+    if (rc != TLPK_OK) return rc;
+    ipmb_launch_hdots(h->stream, s.v, bs.B, bs.partials[1]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 2, 0, 0, bs.partials[1], bs.d_out + nlp * IPM_SLOTS);
+    ipmb_launch_newton_dots(h->stream, s.v, dst, bs.B, bs.partials[0]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 6, 0, 0, bs.partials[0], bs.d_out);
+    if ((rc = batch_gather(h, bs, 2)) != TLPK_OK) return rc;
+    if ((rc = tlpk_sync(h)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) {
+        double *o = out + 4 * k;
+        o[0] = o[1] = o[2] = o[3] = 0.0;
+        if (!active[k]) continue;
+        const double *q = bs.h_out + (size_t)k * IPM_SLOTS, *qh = bs.h_out + (size_t)(nlp + k) * IPM_SLOTS, *c = sc + 8 * k;
+        const double tau = c[0], kappa = c[1], regG = c[2];
+        o[3] = ((qh[0] + qh[1]) + kappa / tau) + regG;                   // h0: the association of tlpk_ipm_hsolve_newton
+        newton_scalars(q, tau, kappa, o[3], c[3], c[4], o[0], o[1]);
+    }
+    if ((rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q == 0 ? out[4 * k] : 0.0; })) != TLPK_OK) return rc;      // dtau
+    ipmb_launch_newton_post(h->stream, s.v, dst, dst, bs.B, 0, bs.partials[1]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 0, 0, 2, bs.partials[1], bs.d_out);
+    if ((rc = batch_gather(h, bs, 1)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) if (active[k]) { const double *q = bs.h_out + (size_t)k * IPM_SLOTS; out[4 * k + 2] = std::fmin(q[0], q[1]); }
+    return TLPK_OK;
+}
+
+/* tlpk_ipm_newton per LP (one mode for the call): sc[8 k ..], out[3 k ..]; inactive LPs: out = 0 */
+int tlpk_ipm_batch_newton(tlpk_handle *h, int mode, const uint8_t *active, const double *sc, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!active || !sc || !out || mode < 0 || mode > 2) return TLPK_BADARG;
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm; const i64 nlp = bs.nlp;
+    const IpmDir &acc = s.D[s.cur];
+    const IpmDir &dst = (mode == 2) ? s.D[1 - s.cur] : s.D[s.cur];
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q < 3 ? sc[8 * k + 5 + q] : 0.0; })) return rc;
+    ipmb_launch_newton_pre(h->stream, s.v, acc, bs.B, mode, bs.partials[0]);
+    int rc = tlpk_solve_device(h, dst.x, dst.y, s.v.xip, s.v.xid);
+    if (rc != TLPK_OK) return rc;
+    ipmb_launch_newton_dots(h->stream, s.v, dst, bs.B, bs.partials[0]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 6, 0, 0, bs.partials[0], bs.d_out);
+    if ((rc = batch_gather(h, bs, 1)) != TLPK_OK) return rc;
+    if ((rc = tlpk_sync(h)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) {
+        double *o = out + 3 * k;
+        o[0] = o[1] = o[2] = 0.0;
+        if (!active[k]) continue;
+        const double *c = sc + 8 * k;
+        newton_scalars(bs.h_out + (size_t)k * IPM_SLOTS, c[0], c[1], c[2], c[3], c[4], o[0], o[1]);
+    }
+    if ((rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q == 0 ? out[3 * k] : 0.0; })) != TLPK_OK) return rc;
+    ipmb_launch_newton_post(h->stream, s.v, dst, acc, bs.B, mode == 2 ? 1 : 0, bs.partials[1]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 0, 0, 2, bs.partials[1], bs.d_out);
+    if ((rc = batch_gather(h, bs, 1)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) if (active[k]) { const double *q = bs.h_out + (size_t)k * IPM_SLOTS; out[3 * k + 2] = std::fmin(q[0], q[1]); }
+    return TLPK_OK;
+}
+
+/* tlpk_ipm_targets per LP: par[3 k ..] = { a_, mu_l, mu_u }, out[2 k ..] = { sum(vl), sum(vu) } */
+int tlpk_ipm_batch_targets(tlpk_handle *h, const uint8_t *active, const double *par, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!active || !par || !out) return TLPK_BADARG;
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q < 3 ? par[3 * k + q] : 0.0; })) return rc;
+    ipmb_launch_targets(h->stream, s.v, s.D[s.cur], bs.B, bs.partials[0]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tc, 2, 0, 0, bs.partials[0], bs.d_out);
+    if (int rc = batch_gather(h, bs, 1)) return rc;
+    for (i64 k = 0; k < bs.nlp; ++k) { const double *q = bs.h_out + (size_t)k * IPM_SLOTS; out[2 * k] = q[0]; out[2 * k + 1] = q[1]; }
+    return TLPK_OK;
+}
+
+/* tlpk_ipm_accept for the LPs with active[k] != 0: their candidate of the last mode-2 call becomes their accepted direction */
+int tlpk_ipm_batch_accept(tlpk_handle *h, const uint8_t *active) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!active) return TLPK_BADARG;
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, active, [](i64, int) { return 0.0; })) return rc;
+    ipmb_launch_accept(h->stream, s.D[s.cur], s.D[1 - s.cur], bs.B);
+    HIPCHK(h, hipStreamSynchronize(h->stream));                      // the next call rewrites the pinned scalars
+    HIPCHK(h, hipGetLastError());
+    return TLPK_OK;
+}
+
+/* tlpk_ipm_advance per LP: pt_k += alpha[k] D_k; out[k] = xl'zl + xu'zu of the new point (0 for an inactive LP, which is not moved) */
+int tlpk_ipm_batch_advance(tlpk_handle *h, const uint8_t *active, const double *alpha, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!active || !alpha || !out) return TLPK_BADARG;
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q == 0 ? alpha[k] : 0.0; })) return rc;
+    ipmb_launch_advance(h->stream, s.v, s.D[s.cur], bs.B, bs.partials[0]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 1, 0, 0, bs.partials[0], bs.d_out);
+    if (int rc = batch_gather(h, bs, 1)) return rc;
+    for (i64 k = 0; k < bs.nlp; ++k) out[k] = bs.h_out[(size_t)k * IPM_SLOTS];
+    return TLPK_OK;
+}
 
 }  // extern "C"

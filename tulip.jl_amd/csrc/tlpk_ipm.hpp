@@ -49,4 +49,32 @@ void mpc_launch_fill(hipStream_t st, const IpmVecs &v, double *theta, double *re
 int mpc_launch_start(hipStream_t st, const IpmVecs &v, int stage, double a, double b, double *partials);
 int mpc_launch_gap(hipStream_t st, const IpmVecs &v, const IpmDir &D, double ap, double ad, double *partials);
 
+// ---- a stack of LPs on one handle (tlpk_ipm_load_batch, ipm_batch_kernels.hip) ----
+// LP k owns the rows [row_off[k], row_off[k + 1]) and the columns [col_off[k], col_off[k + 1]) of the stacked vectors.  Every workgroup works inside one LP:
+// a block table maps blockIdx.x to (LP, block within the LP); LP k has the blocks [first[k], first[k + 1]) -- as many as the unbatched kernel launches for a
+// vector of the LP's length -- and its partials are the rows [first[k], first[k + 1]) of partials[block][slot].
+constexpr int IPM_BSC = 8;         // scalars per LP and call; the last one is the LP's `active` flag (0.0 / 1.0)
+struct IpmBlockTab { int nblocks; const int *seg, *loc, *first /* nlp + 1 */; };
+struct IpmBatch {
+    i64 nlp;
+    const i64 *row_off, *col_off;          // nlp + 1 each
+    IpmBlockTab tc, tr, tb;                // blocks sized by the LP's columns / rows / the longer of the two
+    const double *sc;                      // nlp x IPM_BSC, uploaded per call
+};
+// blocks of one LP's segment of `len` entries: what ipm_kernels.hip launches for a vector of that length
+inline int ipm_seg_blocks(i64 len) { return (int)std::max<i64>(1, std::min<i64>(IPM_BLOCKS, (len + 255) / 256)); }
+
+void ipmb_launch_finalize(hipStream_t st, const IpmBatch &B, const IpmBlockTab &t, int nsum, int nmax, int nmin, const double *partials, double *out);
+void ipmb_launch_res_cols(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *partials);
+void ipmb_launch_res_rows(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *partials);
+void ipmb_launch_theta(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD);
+void ipmb_launch_hrhs(hipStream_t st, const IpmVecs &v, const IpmBatch &B);
+void ipmb_launch_hdots(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *partials);
+void ipmb_launch_targets(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
+void ipmb_launch_newton_pre(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, int mode, double *partials);
+void ipmb_launch_newton_dots(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
+void ipmb_launch_newton_post(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmDir &Add, const IpmBatch &B, int add, double *partials);
+void ipmb_launch_advance(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
+void ipmb_launch_accept(hipStream_t st, const IpmDir &dst, const IpmDir &src, const IpmBatch &B);
+
 }  // namespace tlpk

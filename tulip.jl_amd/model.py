@@ -117,6 +117,39 @@ class Model:
         self.status = res.status
         return self
 
+    @classmethod
+    def optimize_batch(cls, models, **kw):
+        """`optimize()` of many models in one set of launches (hsd_batch.BatchedDeviceHSD): each model is presolved and brought to standard
+        form on its own, ONE batched homogeneous self-dual run solves the LPs presolve did not already finish, each is postsolved, and every
+        model ends as after its own `optimize()`.  kw: the backend's keywords (system=, device=, ...; default: those of the first model)."""
+        from .hsd_batch import BatchedDeviceHSD
+        models = list(models)
+        if any(mdl.algorithm != "hsd" for mdl in models):
+            raise ValueError("optimize_batch runs the homogeneous self-dual loop: every model must have algorithm='hsd'")
+        pending = []
+        for mdl in models:
+            lp_inner = mdl.lp
+            if mdl.presolve_options.Level > 0:
+                ps = mdl.presolve = Presolve(mdl.lp, mdl.presolve_options)
+                st = mdl.status = ps.run()
+                if st in (TRM_OPTIMAL, TRM_PRIMAL_INFEASIBLE, TRM_DUAL_INFEASIBLE):    # presolve solved the problem
+                    mdl.solution = ps.postsolve(ps.solution)
+                    mdl.inner = None
+                    continue
+                lp_inner = ps.reduced_problem()
+            pending.append((mdl, lp_inner))
+        if pending:
+            opt = BatchedDeviceHSD([standard_form(lp) for _, lp in pending], **(kw or models[0].backend_kw)).optimize()
+            for k, (mdl, lp_inner) in enumerate(pending):
+                res = mdl.inner = InnerResult(str(opt.status[k]), str(opt.primal_status[k]), str(opt.dual_status[k]), opt._get(k, 0), opt._get(k, 5),
+                                              opt._get(k, 3), opt._get(k, 4), float(opt.tau[k]), float(opt.primal_objective[k]),
+                                              float(opt.dual_objective[k]), int(opt.niter[k]))
+                sol_inner = extract_solution(lp_inner, res)
+                mdl.solution = mdl.presolve.postsolve(sol_inner) if mdl.presolve_options.Level > 0 else sol_inner
+                mdl.status = res.status
+            opt.kkt.close()
+        return models
+
     # tulip_julia_api.jl:243-300
     def objective_value(self):
         sol = self.solution
