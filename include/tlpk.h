@@ -412,7 +412,16 @@ int tlpk_ipm_hsolve_newton(tlpk_handle *h, const double *sc, double *out);
 int tlpk_ipm_factor_hsolve_newton(tlpk_handle *h, double regP, double regD, const double *sc, double *out);
 int tlpk_ipm_accept(tlpk_handle *h);                         /* step.jl:112-118: candidate -> accepted direction */
 int tlpk_ipm_advance(tlpk_handle *h, double alpha, double *out);   /* step.jl:139-148; out[0] = xl'zl + xu'zu */
-/* what = 0 x, 1 xl, 2 xu, 3 zl, 4 zu (n), 5 y (m) */
+/* Read one device vector (nothing is written on the device; there is no setter).  `len` must be the vector's length.
+ *   what  0-5    the iterate x, xl, xu, zl, zu (n), y (m)
+ *         6-11   the accepted direction, same order;  12-17  the candidate direction of the last mode-2 call, same order
+ *         18-21  the residuals rp (m), rl, ru, rd (n)
+ *         22-26  thl, thu, hx (n), hy (m), hxid (n): the two halves of theta_inv, the solution and the dual right-hand side of the h-system
+ *         27-32  xil, xiu, xzl, xzu, xid (n), xip (m): the right-hand sides of the last Newton system (xzl / xzu: the targets after tlpk_ipm_targets)
+ *         33-35  theta_inv (n), regP (n), regD (m) as the last factor call wrote them on the handle
+ * Codes 0-5 serve every handle with a loaded LP; 6-35 single-device handles only (batch-loaded ones included: the stacked vectors) --
+ * on a multi-device handle they return TLPK_BADARG with a sentence in tlpk_last_error.  Any other code: TLPK_BADARG.
+ * The codes above 5 exist for tests (tests/test_ipm_kernels.py reads every kernel's output through them). */
 int tlpk_ipm_get(tlpk_handle *h, int what, double *host, int64_t len);
 
 /* ---------------------------------------------------------------------------------------------
@@ -421,7 +430,8 @@ int tlpk_ipm_get(tlpk_handle *h, int what, double *host, int64_t len);
  * block needs).  tlpk_ipm_load_batch takes the place of tlpk_ipm_load on such a handle and the tlpk_ipm_batch_* calls run the routines
  * above with PER-LP scalars: LP k owns the contiguous rows [row_off[k], row_off[k+1]) and columns [col_off[k], col_off[k+1]) of the
  * stacked vectors, every array argument below has one entry (or one group of entries) per LP, and an LP with active[k] = 0 is not
- * touched: no kernel writes its iterate, direction or right-hand sides, its outputs are 0.  The reductions of an LP do not depend on
+ * touched: nothing writes its iterate, direction, h-system or right-hand sides (the KKT solves of these calls write scratch vectors and only
+ * the active LPs take their segments), its outputs are 0.  The reductions of an LP do not depend on
  * what else is in the batch; with nlp = 1 every call returns what its unbatched counterpart returns, bit for bit.
  *   tlpk_ipm_load_batch checks, in this order (TLPK_BADARG with a sentence in tlpk_last_error): pointers not NULL and nlp >= 1; offsets
  *   start at 0, do not decrease, leave no LP without rows or columns and end at m and n; every stored entry of A lies in its LP's diagonal

@@ -19,6 +19,15 @@ KRYLOV_NONE, KRYLOV_CG, KRYLOV_MINRES, KRYLOV_TRICG = 0, 1, 16, 32     # (the K2
 PRECOND_NONE, PRECOND_JACOBI = 0, 1
 KC_NAMES = ["assemble", "extend_add", "potrf", "trsm", "update", "solve_fwd", "solve_bwd", "spmv", "update_reduce", "chain"]
 
+# `what` of tlpk_ipm_get (include/tlpk.h): the iterate, the accepted / candidate direction, the residuals, the h-system, the Newton right-hand sides,
+# the handle's theta_inv / regularisations.  Codes above 5: single-device handles.
+IPM_GET_NAMES = ["x", "xl", "xu", "zl", "zu", "y", "dx", "dxl", "dxu", "dzl", "dzu", "dy", "cx", "cxl", "cxu", "czl", "czu", "cy",
+                 "rp", "rl", "ru", "rd", "thl", "thu", "hx", "hy", "hxid", "xil", "xiu", "xzl", "xzu", "xid", "xip", "theta", "regP", "regD"]
+(IPM_X, IPM_XL, IPM_XU, IPM_ZL, IPM_ZU, IPM_Y, IPM_DX, IPM_DXL, IPM_DXU, IPM_DZL, IPM_DZU, IPM_DY,
+ IPM_CX, IPM_CXL, IPM_CXU, IPM_CZL, IPM_CZU, IPM_CY, IPM_RP, IPM_RL, IPM_RU, IPM_RD, IPM_THL, IPM_THU, IPM_HX, IPM_HY, IPM_HXID,
+ IPM_XIL, IPM_XIU, IPM_XZL, IPM_XZU, IPM_XID, IPM_XIP, IPM_THETA, IPM_REGP, IPM_REGD) = range(36)
+IPM_GET_ROWS = frozenset((IPM_Y, IPM_DY, IPM_CY, IPM_RP, IPM_HY, IPM_XIP, IPM_REGD))      # length m; every other code: length n
+
 p64 = C.POINTER(C.c_int64)
 pd = C.POINTER(C.c_double)
 

@@ -12,7 +12,8 @@
 //     What an LP's reductions return does not depend on what else is in the batch; with one LP they are the unbatched ones
 //     bit for bit (tests/test_hsd_batch.py).
 //   * Inactive LPs (flag 0: finished, failed, or masked out of a corrector round) are SKIPPED, not multiplied by zero: no
-//     kernel writes their iterate, direction or right-hand sides, and their outputs are written as 0.
+//     kernel writes their iterate, direction or right-hand sides, and their outputs are written as 0.  The KKT solves of the
+//     batched calls write scratch vectors; k_ipmb_take copies the active LPs' segments to where they belong.
 //   * Nothing waits inside a kernel: bounded grid-stride passes and __syncthreads only.
 //
 // The per-entry bodies are those of ipm_kernels.hip (ipm_shared.hpp): the formulas exist once.
@@ -220,6 +221,16 @@ __global__ void k_ipmb_accept(IpmDir dst, IpmDir src, IpmBatch B) {
     for (i64 jj = t0; jj < g.nk; jj += stride) { const i64 j = g.c0 + jj; dst.x[j] = src.x[j]; dst.xl[j] = src.xl[j]; dst.xu[j] = src.xu[j]; dst.zl[j] = src.zl[j]; dst.zu[j] = src.zu[j]; }
     for (i64 ii = t0; ii < g.mk; ii += stride) { const i64 i = g.r0 + ii; dst.y[i] = src.y[i]; }
 }
+// A KKT solve writes whole stacked vectors, the segments of the inactive LPs with them (their right-hand sides are whatever their last call
+// left).  So the batched calls solve into scratch vectors and the ACTIVE LPs take their segments from there: an inactive LP's direction and
+// h-system stay as they are, like everything else of it.
+__global__ void k_ipmb_take(double *__restrict__ dx, double *__restrict__ dy, const double *__restrict__ sx, const double *__restrict__ sy, IpmBatch B) {
+    const Seg g = seg_of(B, B.tb);
+    if (!g.active) return;
+    const i64 stride = (i64)g.nbk * blockDim.x, t0 = (i64)g.lb * blockDim.x + threadIdx.x;
+    for (i64 jj = t0; jj < g.nk; jj += stride) { const i64 j = g.c0 + jj; dx[j] = sx[j]; }
+    for (i64 ii = t0; ii < g.mk; ii += stride) { const i64 i = g.r0 + ii; dy[i] = sy[i]; }
+}
 
 // ---------------------------------------------------------------------------------------------
 void ipmb_launch_finalize(hipStream_t st, const IpmBatch &B, const IpmBlockTab &t, int nsum, int nmax, int nmin, const double *partials, double *out) {
@@ -246,6 +257,9 @@ void ipmb_launch_newton_post(hipStream_t st, const IpmVecs &v, const IpmDir &D, 
 }
 void ipmb_launch_advance(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials) {
     hipLaunchKernelGGL(k_ipmb_advance, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, D, B, partials);
+}
+void ipmb_launch_take(hipStream_t st, double *dx, double *dy, const double *sx, const double *sy, const IpmBatch &B) {
+    hipLaunchKernelGGL(k_ipmb_take, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, dx, dy, sx, sy, B);
 }
 void ipmb_launch_accept(hipStream_t st, const IpmDir &dst, const IpmDir &src, const IpmBatch &B) { hipLaunchKernelGGL(k_ipmb_accept, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, dst, src, B); }
 

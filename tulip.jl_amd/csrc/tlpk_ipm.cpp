@@ -41,6 +41,7 @@ struct IpmBatchState {
     double *partials[2] = {nullptr, nullptr};     // rows = blocks of the longest table
     double *d_out = nullptr, *h_out = nullptr;    // 2 x nlp x IPM_SLOTS finalised scalars (device / pinned)
     double *d_sc = nullptr, *h_sc = nullptr;      // nlp x IPM_BSC scalars of the current call (device / pinned)
+    double *sx[2] = {nullptr, nullptr}, *sy[2] = {nullptr, nullptr};      // what the solves write (n, m; two right-hand sides): the active LPs take their segments from here
 };
 
 // ---- one device or several ---------------------------------------------------------------------------------------------------
@@ -657,22 +658,34 @@ static int advance_all(tlpk_handle *h, double ap, double ad, double *out) {
 }
 int tlpk_ipm_advance(tlpk_handle *h, double alpha, double *out) { return advance_all(h, alpha, alpha, out); }
 
-/* download one vector of the iterate: what = 0 x, 1 xl, 2 xu, 3 zl, 4 zu (length n), 5 y (length m) */
+/* download one device vector, read-only (nothing here writes device state):
+ *   0-5    the iterate x, xl, xu, zl, zu (n), y (m)
+ *   6-11   the accepted direction, same order (D[cur]);  12-17  the candidate direction (D[1 - cur])
+ *   18-21  rp (m), rl, ru, rd          22-26  thl, thu, hx, hy (m), hxid          27-32  xil, xiu, xzl, xzu, xid, xip (m)
+ *   33-35  the handle's theta_inv (n), regP (n), regD (m) as the last factor call wrote them
+ * Codes above 5 serve single-device handles (batch-loaded ones included: stacked vectors); tests read the kernels' work through them. */
 int tlpk_ipm_get(tlpk_handle *h, int what, double *host, int64_t len) {
     Shards sh;
     if (int rc = ipm_shards(h, sh, true, true, true)) return rc;
-    if (!host || what < 0 || what > 5) return TLPK_BADARG;
+    if (!host || what < 0 || what > 35) return TLPK_BADARG;
+    if (sh.multi && what > 5) { h->last_error = "tlpk_ipm_get: the codes 6 .. 35 (directions, residuals, right-hand sides, theta) need a single-device handle"; return TLPK_BADARG; }
     const IpmVecs &v0 = sh.c[0]->ipm->v;
-    const int64_t need = (what == 5) ? v0.m : v0.n;
+    const bool rows = what == 5 || what == 11 || what == 17 || what == 18 || what == 25 || what == 32 || what == 35;
+    const int64_t need = rows ? v0.m : v0.n;
     if (len != need) { h->last_error = "tlpk_ipm_get: wrong length"; return TLPK_BADARG; }
     std::vector<double> tmp;
     if (sh.multi) tmp.resize((size_t)std::max<int64_t>(need, 1));
     for (int r = 0; r < sh.n; ++r) {
-        tlpk_handle *c = sh.c[r]; const IpmVecs &v = c->ipm->v;
-        const double *src[6] = {v.x, v.xl, v.xu, v.zl, v.zu, v.y};
+        tlpk_handle *c = sh.c[r]; const IpmState &s = *c->ipm; const IpmVecs &v = s.v;
+        const IpmDir &acc = s.D[s.cur], &cand = s.D[1 - s.cur];
+        const double *src[36] = {v.x, v.xl, v.xu, v.zl, v.zu, v.y,
+                                 acc.x, acc.xl, acc.xu, acc.zl, acc.zu, acc.y, cand.x, cand.xl, cand.xu, cand.zl, cand.zu, cand.y,
+                                 v.rp, v.rl, v.ru, v.rd, v.thl, v.thu, v.hx, v.hy, v.hxid, v.xil, v.xiu, v.xzl, v.xzu, v.xid, v.xip,
+                                 c->d_theta, c->d_regP, c->d_regD};
         HIPCHK(h, hipSetDevice(c->device));
         HIPCHK(h, hipStreamSynchronize(c->stream));
         if (need <= 0) continue;
+        if (!src[what]) { h->last_error = "tlpk_ipm_get: the handle does not hold that vector"; return TLPK_BADARG; }
         if (!sh.multi) { HIPCHK(h, hipMemcpy(host, src[what], (size_t)need * 8, hipMemcpyDeviceToHost)); continue; }
         // every entry from the shard that owns it (linking rows: the lead)
         HIPCHK(h, hipMemcpy(tmp.data(), src[what], (size_t)need * 8, hipMemcpyDeviceToHost));
@@ -958,6 +971,12 @@ int tlpk_ipm_load_batch(tlpk_handle *h, int64_t nlp, const int64_t *row_off, con
             HIPCHK(h, hipMemset(p, 0, (size_t)(2 * nlp * IPM_SLOTS) * 8)); bs->d_out = p;
             if (int r = dev_alloc(h, &p, nlp * IPM_BSC)) return r;
             HIPCHK(h, hipMemset(p, 0, (size_t)(nlp * IPM_BSC) * 8)); bs->d_sc = p; B.sc = p;
+            for (int g = 0; g < 2; ++g) {
+                if (int r = dev_alloc(h, &p, n)) return r;
+                HIPCHK(h, hipMemset(p, 0, (size_t)std::max<i64>(n, 1) * 8)); bs->sx[g] = p;
+                if (int r = dev_alloc(h, &p, m)) return r;
+                HIPCHK(h, hipMemset(p, 0, (size_t)std::max<i64>(m, 1) * 8)); bs->sy[g] = p;
+            }
             HIPCHK(h, hipHostMalloc((void **)&bs->h_out, (size_t)(2 * nlp * IPM_SLOTS) * 8, hipHostMallocDefault));
             HIPCHK(h, hipHostMalloc((void **)&bs->h_sc, (size_t)(nlp * IPM_BSC) * 8, hipHostMallocDefault));
             return TLPK_OK;
@@ -1016,8 +1035,10 @@ int tlpk_ipm_batch_hsolve_newton(tlpk_handle *h, const uint8_t *active, const do
     if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q < 3 ? sc[8 * k + 5 + q] : 0.0; })) return rc;      // eta, gamma mu, delta
     ipmb_launch_hrhs(h->stream, s.v, bs.B);
     ipmb_launch_newton_pre(h->stream, s.v, dst, bs.B, 0, bs.partials[0]);
-    int rc = tlpk_solve2_device(h, s.v.hx, s.v.hy, s.v.b, s.v.hxid, dst.x, dst.y, s.v.xip, s.v.xid);
+    int rc = tlpk_solve2_device(h, bs.sx[0], bs.sy[0], s.v.b, s.v.hxid, bs.sx[1], bs.sy[1], s.v.xip, s.v.xid);
     if (rc != TLPK_OK) return rc;
+    ipmb_launch_take(h->stream, s.v.hx, s.v.hy, bs.sx[0], bs.sy[0], bs.B);      // an inactive LP keeps its h-system and direction
+    ipmb_launch_take(h->stream, dst.x, dst.y, bs.sx[1], bs.sy[1], bs.B);
     ipmb_launch_hdots(h->stream, s.v, bs.B, bs.partials[1]);
     ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 2, 0, 0, bs.partials[1], bs.d_out + nlp * IPM_SLOTS);
     ipmb_launch_newton_dots(h->stream, s.v, dst, bs.B, bs.partials[0]);
@@ -1052,8 +1073,9 @@ int tlpk_ipm_batch_newton(tlpk_handle *h, int mode, const uint8_t *active, const
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q < 3 ? sc[8 * k + 5 + q] : 0.0; })) return rc;
     ipmb_launch_newton_pre(h->stream, s.v, acc, bs.B, mode, bs.partials[0]);
-    int rc = tlpk_solve_device(h, dst.x, dst.y, s.v.xip, s.v.xid);
+    int rc = tlpk_solve_device(h, bs.sx[0], bs.sy[0], s.v.xip, s.v.xid);
     if (rc != TLPK_OK) return rc;
+    ipmb_launch_take(h->stream, dst.x, dst.y, bs.sx[0], bs.sy[0], bs.B);        // an inactive LP keeps its direction
     ipmb_launch_newton_dots(h->stream, s.v, dst, bs.B, bs.partials[0]);
     ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 6, 0, 0, bs.partials[0], bs.d_out);
     if ((rc = batch_gather(h, bs, 1)) != TLPK_OK) return rc;

@@ -76,5 +76,6 @@ void ipmb_launch_newton_dots(hipStream_t st, const IpmVecs &v, const IpmDir &D, 
 void ipmb_launch_newton_post(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmDir &Add, const IpmBatch &B, int add, double *partials);
 void ipmb_launch_advance(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
 void ipmb_launch_accept(hipStream_t st, const IpmDir &dst, const IpmDir &src, const IpmBatch &B);
+void ipmb_launch_take(hipStream_t st, double *dx, double *dy, const double *sx, const double *sy, const IpmBatch &B);
 
 }  // namespace tlpk

@@ -335,14 +335,14 @@ class BatchedDeviceHSD:
 
     def _vec(self, what):
         if what not in self._cache:
-            v = np.empty(self.m if what == 5 else self.n)
+            v = np.empty(self.m if what in _lib.IPM_GET_ROWS else self.n)
             self._call(self.L.tlpk_ipm_get(self.kkt._h, what, _lib.as_pd(v), v.shape[0]))
             self._cache[what] = v
         return self._cache[what]
 
     def _get(self, k, what):
-        """Vector `what` (0 x, 1 xl, 2 xu, 3 zl, 4 zu, 5 y) of LP k, as the device holds it."""
-        off = self.row_off if what == 5 else self.col_off
+        """Vector `what` (a code of tlpk_ipm_get: 0 x, 1 xl, 2 xu, 3 zl, 4 zu, 5 y, ... _lib.IPM_REGD) of LP k, as the device holds it."""
+        off = self.row_off if what in _lib.IPM_GET_ROWS else self.col_off
         return self._vec(what)[off[k]:off[k + 1]].copy()
 
     def solution(self, k, nvar=None):

@@ -82,6 +82,10 @@ class DeviceHSD:
         self.L = _lib.lib()
         self._l, self._u = l, u
         self._call(self.L.tlpk_ipm_load(self.kkt._h, _lib.as_pd(self._b), _lib.as_pd(self._c), _lib.as_pd(l), _lib.as_pd(u)))
+        self._init_loop()
+
+    def _init_loop(self):
+        """The host state of a freshly loaded LP (needs L, kkt, m, n, opt and the LP's vectors; tests/test_ipm_kernels.py runs it on a stand-in library)."""
         self._host_norms()
         self.regP = self.regD = self.regG = 1.0                              # HSD.jl:50-52 (uniform vectors)
         self.tau = self.kappa = 1.0
@@ -281,6 +285,7 @@ class DeviceHSD:
         return self
 
     def _get(self, what, length):
+        # what: a code of tlpk_ipm_get (_lib.IPM_X .. _lib.IPM_REGD), passed through
         v = np.empty(length)
         self._call(self.L.tlpk_ipm_get(self.kkt._h, what, _lib.as_pd(v), length))
         return v

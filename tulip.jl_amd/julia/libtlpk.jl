@@ -211,6 +211,13 @@ function ipm_reload!(h::Ptr{Cvoid}; b::Union{Nothing,Vector{Float64}}=nothing, c
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, p(b), p(c), p(l), p(u))
 end
 
+# tlpk_ipm_get(h, what, host, len) reads one device vector of a loaded handle (read-only; `len` = its length):
+#   what 0-5 x, xl, xu, zl, zu (n), y (m) | 6-11 accepted direction | 12-17 candidate direction (same order) | 18-21 rp (m), rl, ru, rd
+#   | 22-26 thl, thu, hx, hy (m), hxid | 27-32 xil, xiu, xzl, xzu, xid, xip (m) | 33-35 theta_inv, regP (n), regD (m) of the last factor call.
+#   Codes above 5: single-device handles only (TLPK_BADARG on a multi-device one).
+ipm_get!(h::Ptr{Cvoid}, what::Integer, host::Vector{Float64}) =
+    GC.@preserve host ccall((:tlpk_ipm_get, libtlpk[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64), h, what, host, length(host))
+
 update(h::Ptr{Cvoid}, θinv::Vector{Float64}, regP::Vector{Float64}, regD::Vector{Float64}) =
     GC.@preserve θinv regP regD ccall((:tlpk_update, libtlpk[]), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, θinv, regP, regD)

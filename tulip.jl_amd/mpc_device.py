@@ -20,8 +20,8 @@ from .kkt import OutOfMemoryError, PosDefException
 class DeviceMPC(DeviceHSD):
     """Shares the vectors on the device, the residual / status quantities and the accessors with DeviceHSD."""
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
+    def _init_loop(self):
+        super()._init_loop()
         self.tau, self.kappa = 1.0, 0.0
         self.alpha_p = self.alpha_d = 0.0
 
