@@ -15,6 +15,8 @@ def load_golden(name=None):
     out = []
     for f in files:
         d = json.load(open(f))
+        if "A" not in d:          # not a KKT instance of make_golden.py (krylov_family_digests.json: recorded digests)
+            continue
         if name is None or d["name"] == name:
             for k in ("A", "theta_inv", "regP", "regD", "xi_p", "xi_d", "dx", "dy"):
                 d[k] = np.array(d[k], dtype=np.float64)

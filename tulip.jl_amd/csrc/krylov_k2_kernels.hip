@@ -18,12 +18,14 @@
 //
 // Rows and columns of an LP hold a handful of entries: 8 lanes per row, 4 per column, handed out round by round.  A row or column with more than
 // CG_LONG entries is listed at create and gets a whole workgroup in the same launch, behind those of the short ones.
+// The gather itself is krylov_spmv.hpp's: a kernel here supplies the addend of an entry and what one lane does with a finished sum.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cfloat>
 
 #include "krylov_reduce.hpp"
+#include "krylov_spmv.hpp"
 #include "tlpk_device.hpp"
 
 namespace tlpk {
@@ -52,24 +54,10 @@ __global__ __launch_bounds__(CG_THREADS) void k_mr_jacobi(i64 n, i64 m, const i6
         if (j < n) Minv[j] = cg_minv(E[j]);
         return;
     }
-    if (blockIdx.x >= gs) {
-        const i64 i = long_rows[blockIdx.x - gs];
-        double s = 0.0;
-        for (i64 q = Tp[i] + threadIdx.x; q < Tp[i + 1]; q += CG_THREADS) { const double e = E[Tj[q]]; if (e > 0.0) s += Tx[q] * Tx[q] / e; }
-        s = cg_block_sum(s, sh);
-        if (threadIdx.x == 0) Minv[n + i] = cg_minv(s + regD[i]);
-        return;
-    }
-    const i64 i = ((i64)blockIdx.x * CG_THREADS + threadIdx.x) >> 3;
-    const int lane = threadIdx.x & 7;
-    const bool live = i < m;
-    const i64 q0 = live ? Tp[i] : 0, q1 = live ? Tp[i + 1] : 0;
-    const bool mine = live && q1 - q0 <= CG_LONG;
-    double s = 0.0;
-    if (mine) for (i64 q = q0 + lane; q < q1; q += 8) { const double e = E[Tj[q]]; if (e > 0.0) s += Tx[q] * Tx[q] / e; }
-#pragma unroll
-    for (int off = 4; off > 0; off >>= 1) s += __shfl_down(s, off, 8);
-    if (mine && lane == 0) Minv[n + i] = cg_minv(s + regD[i]);
+    const auto term = [&](i64 q) { const double e = E[Tj[q]]; return e > 0.0 ? Tx[q] * Tx[q] / e : 0.0; };      // (adding 0.0 leaves the sum as it is)
+    const auto done = [&](i64 i, double s) { Minv[n + i] = cg_minv(s + regD[i]); };
+    if (blockIdx.x < gs) walk_short<CG_THREADS, 8>(m, Tp, blockIdx.x, gs, term, done);
+    else walk_long<CG_THREADS>(long_rows, n_long, blockIdx.x - gs, n_long, Tp, sh, term, done);
 }
 
 // r[0] = b = [xi_d; xi_p], z[0] = M^-1 b, x = w = 0, partial sums of b'z
@@ -116,85 +104,32 @@ __global__ __launch_bounds__(MR_OP_THREADS) void k_mr_op(const MrScalars *__rest
     const double beta = sc->st[par].beta, c1 = first ? 0.0 : beta / sc->st[par].oldb;
     const double *__restrict__ z1 = z, *__restrict__ z2 = z + n;
     double acc = 0.0;
-    unsigned b = blockIdx.x;
-    if (b < gc) {
-        const int lane = threadIdx.x & 3;
-        const i64 per_round = (i64)gc * (MR_OP_THREADS / 4);
-        for (i64 base = 0; base < n; base += per_round) {
-            const i64 j = base + (((i64)b * MR_OP_THREADS + threadIdx.x) >> 2);
-            const bool live = j < n;
-            const i64 q0 = live ? Ap[j] : 0, q1 = live ? Ap[j + 1] : 0;
-            const bool mine = live && q1 - q0 <= CG_LONG;
-            double s = 0.0;
-            if (mine) for (i64 q = q0 + lane; q < q1; q += 4) s += Ax[q] * (z2[Ai[q]] / beta);
-            s += __shfl_down(s, 2, 4);
-            s += __shfl_down(s, 1, 4);
-            if (mine && lane == 0) {
-                const double vj = z1[j] / beta;
-                double uj = s - E[j] * vj;
-                if (!first) uj -= c1 * r1[j];
-                u[j] = uj; acc += vj * uj;
-            }
-        }
+    const auto col_term = [&](i64 q) { return Ax[q] * (z2[Ai[q]] / beta); };
+    const auto col_done = [&](i64 j, double s) {
+        const double vj = z1[j] / beta;
+        double uj = s - E[j] * vj;
+        if (!first) uj -= c1 * r1[j];
+        u[j] = uj; acc += vj * uj;
+    };
+    const auto row_term = [&](i64 q) { return Tx[q] * (z1[Tj[q]] / beta); };
+    const auto row_done = [&](i64 i, double s) {
+        const double vi = z2[i] / beta;
+        double ui = s + regD[i] * vi;
+        if (!first) ui -= c1 * r1[n + i];
+        u[n + i] = ui; acc += vi * ui;
+    };
+    // acc: this workgroup's part of v'u, spread over the lanes of the short items, on the first thread of the long ones
+    const unsigned b = blockIdx.x;
+    if (b < gc + gr) {
+        if (b < gc) walk_short<MR_OP_THREADS, 4>(n, Ap, b, gc, col_term, col_done);
+        else walk_short<MR_OP_THREADS, 8>(m, Tp, b - gc, gr, row_term, row_done);
         acc = cg_block_sum<MR_OP_THREADS>(acc, sh);
-        if (threadIdx.x == 0) slots_a[blockIdx.x] = acc;
-        return;
+    } else if (b < gc + gr + glc) {
+        walk_long<MR_OP_THREADS>(long_cols, n_long_cols, b - gc - gr, glc, Ap, sh, col_term, col_done);
+    } else {
+        walk_long<MR_OP_THREADS>(long_rows, n_long_rows, b - gc - gr - glc, glr, Tp, sh, row_term, row_done);
     }
-    b -= gc;
-    if (b < gr) {
-        const int lane = threadIdx.x & 7;
-        const i64 per_round = (i64)gr * (MR_OP_THREADS / 8);
-        for (i64 base = 0; base < m; base += per_round) {
-            const i64 i = base + (((i64)b * MR_OP_THREADS + threadIdx.x) >> 3);
-            const bool live = i < m;
-            const i64 q0 = live ? Tp[i] : 0, q1 = live ? Tp[i + 1] : 0;
-            const bool mine = live && q1 - q0 <= CG_LONG;
-            double s = 0.0;
-            if (mine) for (i64 q = q0 + lane; q < q1; q += 8) s += Tx[q] * (z1[Tj[q]] / beta);
-#pragma unroll
-            for (int off = 4; off > 0; off >>= 1) s += __shfl_down(s, off, 8);
-            if (mine && lane == 0) {
-                const double vi = z2[i] / beta;
-                double ui = s + regD[i] * vi;
-                if (!first) ui -= c1 * r1[n + i];
-                u[n + i] = ui; acc += vi * ui;
-            }
-        }
-        acc = cg_block_sum<MR_OP_THREADS>(acc, sh);
-        if (threadIdx.x == 0) slots_a[blockIdx.x] = acc;
-        return;
-    }
-    b -= gr;
-    if (b < glc) {
-        for (i64 k = b; k < n_long_cols; k += glc) {
-            const i64 j = long_cols[k];
-            double s = 0.0;
-            for (i64 q = Ap[j] + threadIdx.x; q < Ap[j + 1]; q += MR_OP_THREADS) s += Ax[q] * (z2[Ai[q]] / beta);
-            s = cg_block_sum<MR_OP_THREADS>(s, sh);
-            if (threadIdx.x == 0) {
-                const double vj = z1[j] / beta;
-                double uj = s - E[j] * vj;
-                if (!first) uj -= c1 * r1[j];
-                u[j] = uj; acc += vj * uj;
-            }
-        }
-        if (threadIdx.x == 0) slots_a[blockIdx.x] = acc;
-        return;
-    }
-    b -= glc;
-    for (i64 k = b; k < n_long_rows; k += glr) {
-        const i64 i = long_rows[k];
-        double s = 0.0;
-        for (i64 q = Tp[i] + threadIdx.x; q < Tp[i + 1]; q += MR_OP_THREADS) s += Tx[q] * (z1[Tj[q]] / beta);
-        s = cg_block_sum<MR_OP_THREADS>(s, sh);
-        if (threadIdx.x == 0) {
-            const double vi = z2[i] / beta;
-            double ui = s + regD[i] * vi;
-            if (!first) ui -= c1 * r1[n + i];
-            u[n + i] = ui; acc += vi * ui;
-        }
-    }
-    if (threadIdx.x == 0) slots_a[blockIdx.x] = acc;
+    if (threadIdx.x == 0) slots_a[b] = acc;
 }
 
 // The Lanczos step: alpha from the slots; r_new = u - (alpha / beta) r2, written over r1 (dead since k_mr_op); z_new = M^-1 r_new; partial sums of r_new'z_new
@@ -256,8 +191,6 @@ __global__ __launch_bounds__(CG_THREADS) void k_mr_rot(MrScalars *__restrict__ s
     }
 }
 
-inline unsigned nblk(i64 n, int b) { return (unsigned)((n + b - 1) / b); }
-
 }  // namespace
 
 void launch_mr_diag(hipStream_t st, i64 n, const double *theta, const double *regP, double *E) {
@@ -267,29 +200,29 @@ void launch_mr_diag(hipStream_t st, i64 n, const double *theta, const double *re
 void launch_mr_jacobi(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *E, const double *regD) {
     if (a.m + a.n <= 0 || !c.Minv) return;
     const unsigned gs = a.m > 0 ? nblk(a.m * 8, CG_THREADS) : 0, gcol = a.n > 0 ? nblk(a.n, CG_THREADS) : 0;
-    hipLaunchKernelGGL(k_mr_jacobi, dim3(gs + (unsigned)c.n_long_rows + gcol), dim3(CG_THREADS), 0, st, a.n, a.m, a.Tp, a.Tj, a.Tx, E, regD, c.Minv, gs,
-                       (unsigned)c.n_long_rows, c.long_rows);
+    hipLaunchKernelGGL(k_mr_jacobi, dim3(gs + (unsigned)c.geo.n_long_rows + gcol), dim3(CG_THREADS), 0, st, a.n, a.m, a.Tp, a.Tj, a.Tx, E, regD, c.Minv, gs,
+                       (unsigned)c.geo.n_long_rows, c.geo.long_rows);
 }
 
 void launch_mr_init(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *xi_p, const double *xi_d, double atol, double rtol, i64 itmax) {
     const i64 N = a.n + a.m;
     if (N > 0)
-        hipLaunchKernelGGL(k_mr_init, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, a.n, N, xi_d, xi_p, c.Minv, c.r[0], c.z[0], c.x, c.w[0], c.w[1], c.slots_g);
-    hipLaunchKernelGGL(k_mr_init_scalars, dim3(1), dim3(CG_THREADS), 0, st, c.sc, c.slots_g, N > 0 ? c.g_vec : 0, atol, rtol, (long long)itmax);
+        hipLaunchKernelGGL(k_mr_init, dim3((unsigned)c.geo.g_vec), dim3(CG_THREADS), 0, st, a.n, N, xi_d, xi_p, c.Minv, c.r[0], c.z[0], c.x, c.w[0], c.w[1], c.slots_g);
+    hipLaunchKernelGGL(k_mr_init_scalars, dim3(1), dim3(CG_THREADS), 0, st, c.sc, c.slots_g, N > 0 ? c.geo.g_vec : 0, atol, rtol, (long long)itmax);
 }
 
 int launch_mr_iter(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *E, const double *regD, i64 k) {
     const i64 N = a.n + a.m;
     if (N <= 0) return 0;
     const int par = (int)(k & 1);
-    const int ns_a = c.g_cols + c.g_rows + c.g_lcols + c.g_lrows;
+    const int ns_a = c.geo.g_cols + c.geo.g_rows + c.geo.g_lcols + c.geo.g_lrows;
     hipLaunchKernelGGL(k_mr_op, dim3((unsigned)ns_a), dim3(MR_OP_THREADS), 0, st, c.sc, par, k == 0 ? 1 : 0, a.n, a.m, a.Ap, a.Ai, a.Ax, a.Tp, a.Tj, a.Tx, E, regD,
-                       c.z[par], c.r[par ^ 1], c.u, c.slots_a, (unsigned)c.g_cols, (unsigned)c.g_rows, (unsigned)c.g_lcols, (unsigned)c.g_lrows, c.long_cols,
-                       c.n_long_cols, c.long_rows, c.n_long_rows);
-    hipLaunchKernelGGL(k_mr_step, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, N, c.u, c.r[par], c.r[par ^ 1], c.z[par ^ 1], c.Minv, c.slots_a, ns_a,
+                       c.z[par], c.r[par ^ 1], c.u, c.slots_a, (unsigned)c.geo.g_cols, (unsigned)c.geo.g_rows, (unsigned)c.geo.g_lcols, (unsigned)c.geo.g_lrows, c.geo.long_cols,
+                       c.geo.n_long_cols, c.geo.long_rows, c.geo.n_long_rows);
+    hipLaunchKernelGGL(k_mr_step, dim3((unsigned)c.geo.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, N, c.u, c.r[par], c.r[par ^ 1], c.z[par ^ 1], c.Minv, c.slots_a, ns_a,
                        c.slots_g);
-    hipLaunchKernelGGL(k_mr_rot, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, (long long)k, N, c.z[par], c.w[par], c.w[par ^ 1], c.x, c.slots_g,
-                       c.g_vec);
+    hipLaunchKernelGGL(k_mr_rot, dim3((unsigned)c.geo.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, (long long)k, N, c.z[par], c.w[par], c.w[par ^ 1], c.x, c.slots_g,
+                       c.geo.g_vec);
     return 3;
 }
 

@@ -14,11 +14,13 @@
 //
 // Rows and columns of an LP hold a handful of entries: 8 lanes per row, 4 per column.  A row or column with more than CG_LONG entries (a linking
 // row, a dense column) is listed at create and gets a whole workgroup in the same launch (the blocks behind those of the short ones).
+// The gather itself is krylov_spmv.hpp's: a kernel here supplies the addend of an entry and what one lane does with a finished sum.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "krylov_reduce.hpp"
+#include "krylov_spmv.hpp"
 #include "tlpk_device.hpp"
 
 namespace tlpk {
@@ -33,24 +35,11 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_jacobi(i64 m, const i64 *__re
                                                           const double *__restrict__ D, const double *__restrict__ regD, double *__restrict__ Minv,
                                                           unsigned gs, const i32 *__restrict__ long_rows) {
     __shared__ double sh[CG_THREADS / 64];
-    if (blockIdx.x >= gs) {
-        const i64 i = long_rows[blockIdx.x - gs];
-        double s = 0.0;
-        for (i64 q = Tp[i] + threadIdx.x; q < Tp[i + 1]; q += CG_THREADS) s += Tx[q] * Tx[q] * D[Tj[q]];
-        s = cg_block_sum(s, sh);
-        if (threadIdx.x == 0) Minv[i] = cg_minv(s + regD[i]);
-        return;
-    }
-    const i64 i = ((i64)blockIdx.x * CG_THREADS + threadIdx.x) >> 3;
-    const int lane = threadIdx.x & 7;
-    const bool live = i < m;
-    const i64 q0 = live ? Tp[i] : 0, q1 = live ? Tp[i + 1] : 0;
-    const bool mine = live && q1 - q0 <= CG_LONG;
-    double s = 0.0;
-    if (mine) for (i64 q = q0 + lane; q < q1; q += 8) s += Tx[q] * Tx[q] * D[Tj[q]];
-#pragma unroll
-    for (int off = 4; off > 0; off >>= 1) s += __shfl_down(s, off, 8);
-    if (mine && lane == 0) Minv[i] = cg_minv(s + regD[i]);
+    const auto term = [&](i64 q) { return Tx[q] * Tx[q] * D[Tj[q]]; };
+    const auto done = [&](i64 i, double s) { Minv[i] = cg_minv(s + regD[i]); };
+    const unsigned n_long = gridDim.x - gs;
+    if (blockIdx.x < gs) walk_short<CG_THREADS, 8>(m, Tp, blockIdx.x, gs, term, done);
+    else walk_long<CG_THREADS>(long_rows, n_long, blockIdx.x - gs, n_long, Tp, sh, term, done);
 }
 
 // x = 0, p = z = M^-1 r, partial sums of r'z
@@ -85,24 +74,11 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_cols(const CgScalars *__restr
                                                         double *__restrict__ t, unsigned gs, const i32 *__restrict__ long_cols) {
     __shared__ double sh[CG_THREADS / 64];
     if (sc->outcome != CG_RUNNING) return;
-    if (blockIdx.x >= gs) {
-        const i64 j = long_cols[blockIdx.x - gs];
-        double s = 0.0;
-        for (i64 q = Ap[j] + threadIdx.x; q < Ap[j + 1]; q += CG_THREADS) s += Ax[q] * p[Ai[q]];
-        s = cg_block_sum(s, sh);
-        if (threadIdx.x == 0) t[j] = D[j] * s;
-        return;
-    }
-    const i64 j = ((i64)blockIdx.x * CG_THREADS + threadIdx.x) >> 2;
-    const int lane = threadIdx.x & 3;
-    const bool live = j < n;
-    const i64 q0 = live ? Ap[j] : 0, q1 = live ? Ap[j + 1] : 0;
-    const bool mine = live && q1 - q0 <= CG_LONG;
-    double s = 0.0;
-    if (mine) for (i64 q = q0 + lane; q < q1; q += 4) s += Ax[q] * p[Ai[q]];
-    s += __shfl_down(s, 2, 4);
-    s += __shfl_down(s, 1, 4);
-    if (mine && lane == 0) t[j] = D[j] * s;
+    const auto term = [&](i64 q) { return Ax[q] * p[Ai[q]]; };
+    const auto done = [&](i64 j, double s) { t[j] = D[j] * s; };
+    const unsigned n_long = gridDim.x - gs;
+    if (blockIdx.x < gs) walk_short<CG_THREADS, 4>(n, Ap, blockIdx.x, gs, term, done);
+    else walk_long<CG_THREADS>(long_cols, n_long, blockIdx.x - gs, n_long, Ap, sh, term, done);
 }
 
 // q = A t + Rd .* p and the partial sums of p'q.  Blocks [0, gs): 8 lanes per row, rows handed out round by round (every wave makes the same number
@@ -113,31 +89,15 @@ __global__ __launch_bounds__(CG_ROW_THREADS) void k_cg_rows(const CgScalars *__r
                                                         unsigned gl, const i32 *__restrict__ long_rows, i64 n_long) {
     __shared__ double sh[CG_ROW_THREADS / 64];
     if (sc->outcome != CG_RUNNING) return;
-    double acc = 0.0;
-    if (blockIdx.x >= gs) {
-        for (i64 k = blockIdx.x - gs; k < n_long; k += gl) {
-            const i64 i = long_rows[k];
-            double s = 0.0;
-            for (i64 q = Tp[i] + threadIdx.x; q < Tp[i + 1]; q += CG_ROW_THREADS) s += Tx[q] * t[Tj[q]];
-            s = cg_block_sum<CG_ROW_THREADS>(s, sh);
-            if (threadIdx.x == 0) { const double pi = p[i], qi = s + regD[i] * pi; qv[i] = qi; acc += pi * qi; }
-        }
+    double acc = 0.0;      // this workgroup's part of p'q: spread over the lanes of the short rows, on the first thread of the long ones
+    const auto term = [&](i64 q) { return Tx[q] * t[Tj[q]]; };
+    const auto done = [&](i64 i, double s) { const double pi = p[i], qi = s + regD[i] * pi; qv[i] = qi; acc += pi * qi; };
+    if (blockIdx.x >= gs) {          // (the long rows first and on a path of their own: testing the short ones first measured 0.5 us per iteration slower)
+        walk_long<CG_ROW_THREADS>(long_rows, n_long, blockIdx.x - gs, gl, Tp, sh, term, done);
         if (threadIdx.x == 0) slots_r[blockIdx.x] = acc;
         return;
     }
-    const int lane = threadIdx.x & 7;
-    const i64 per_round = (i64)gs * (CG_ROW_THREADS / 8);
-    for (i64 base = 0; base < m; base += per_round) {
-        const i64 i = base + (((i64)blockIdx.x * CG_ROW_THREADS + threadIdx.x) >> 3);
-        const bool live = i < m;
-        const i64 q0 = live ? Tp[i] : 0, q1 = live ? Tp[i + 1] : 0;
-        const bool mine = live && q1 - q0 <= CG_LONG;
-        double s = 0.0;
-        if (mine) for (i64 q = q0 + lane; q < q1; q += 8) s += Tx[q] * t[Tj[q]];
-#pragma unroll
-        for (int off = 4; off > 0; off >>= 1) s += __shfl_down(s, off, 8);
-        if (mine && lane == 0) { const double pi = p[i], qi = s + regD[i] * pi; qv[i] = qi; acc += pi * qi; }
-    }
+    walk_short<CG_ROW_THREADS, 8>(m, Tp, blockIdx.x, gs, term, done);
     acc = cg_block_sum<CG_ROW_THREADS>(acc, sh);
     if (threadIdx.x == 0) slots_r[blockIdx.x] = acc;
 }
@@ -194,19 +154,17 @@ __global__ __launch_bounds__(CG_THREADS) void k_cg_dir(CgScalars *__restrict__ s
     }
 }
 
-inline unsigned nblk(i64 n, int b) { return (unsigned)((n + b - 1) / b); }
-
 }  // namespace
 
 void launch_cg_jacobi(hipStream_t st, const DevArrays &a, const CgArrays &c, const double *D, const double *regD) {
     if (a.m <= 0 || !c.Minv) return;
     const unsigned gs = nblk(a.m * 8, CG_THREADS);
-    hipLaunchKernelGGL(k_cg_jacobi, dim3(gs + (unsigned)c.n_long_rows), dim3(CG_THREADS), 0, st, a.m, a.Tp, a.Tj, a.Tx, D, regD, c.Minv, gs, c.long_rows);
+    hipLaunchKernelGGL(k_cg_jacobi, dim3(gs + (unsigned)c.geo.n_long_rows), dim3(CG_THREADS), 0, st, a.m, a.Tp, a.Tj, a.Tx, D, regD, c.Minv, gs, c.geo.long_rows);
 }
 
 void launch_cg_init(hipStream_t st, const DevArrays &a, const CgArrays &c, double atol, double rtol, i64 itmax) {
-    if (a.m > 0) hipLaunchKernelGGL(k_cg_init, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, a.m, a.ctx.xw, c.Minv, c.x, c.p, c.slots_v);
-    hipLaunchKernelGGL(k_cg_init_scalars, dim3(1), dim3(CG_THREADS), 0, st, c.sc, c.slots_v, a.m > 0 ? c.g_vec : 0, atol, rtol, (long long)itmax);
+    if (a.m > 0) hipLaunchKernelGGL(k_cg_init, dim3((unsigned)c.geo.g_vec), dim3(CG_THREADS), 0, st, a.m, a.ctx.xw, c.Minv, c.x, c.p, c.slots_v);
+    hipLaunchKernelGGL(k_cg_init_scalars, dim3(1), dim3(CG_THREADS), 0, st, c.sc, c.slots_v, a.m > 0 ? c.geo.g_vec : 0, atol, rtol, (long long)itmax);
 }
 
 int launch_cg_iter(hipStream_t st, const DevArrays &a, const CgArrays &c, const double *D, const double *regD, i64 k) {
@@ -215,14 +173,14 @@ int launch_cg_iter(hipStream_t st, const DevArrays &a, const CgArrays &c, const 
     int nl = 3;
     if (a.n > 0) {
         const unsigned gs = nblk(a.n * 4, CG_THREADS);
-        hipLaunchKernelGGL(k_cg_cols, dim3(gs + (unsigned)c.n_long_cols), dim3(CG_THREADS), 0, st, c.sc, a.n, a.Ap, a.Ai, a.Ax, D, c.p, c.t, gs, c.long_cols);
+        hipLaunchKernelGGL(k_cg_cols, dim3(gs + (unsigned)c.geo.n_long_cols), dim3(CG_THREADS), 0, st, c.sc, a.n, a.Ap, a.Ai, a.Ax, D, c.p, c.t, gs, c.geo.long_cols);
         ++nl;
     }
-    hipLaunchKernelGGL(k_cg_rows, dim3((unsigned)(c.g_rows + c.g_long)), dim3(CG_ROW_THREADS), 0, st, c.sc, a.m, a.Tp, a.Tj, a.Tx, c.t, regD, c.p, c.q, c.slots_r,
-                       (unsigned)c.g_rows, (unsigned)c.g_long, c.long_rows, c.n_long_rows);
-    hipLaunchKernelGGL(k_cg_step, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, a.m, c.x, a.ctx.xw, c.p, c.q, c.Minv, c.slots_r, c.g_rows + c.g_long,
+    hipLaunchKernelGGL(k_cg_rows, dim3((unsigned)(c.geo.g_rows + c.geo.g_lrows)), dim3(CG_ROW_THREADS), 0, st, c.sc, a.m, a.Tp, a.Tj, a.Tx, c.t, regD, c.p, c.q, c.slots_r,
+                       (unsigned)c.geo.g_rows, (unsigned)c.geo.g_lrows, c.geo.long_rows, c.geo.n_long_rows);
+    hipLaunchKernelGGL(k_cg_step, dim3((unsigned)c.geo.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, a.m, c.x, a.ctx.xw, c.p, c.q, c.Minv, c.slots_r, c.geo.g_rows + c.geo.g_lrows,
                        c.slots_v);
-    hipLaunchKernelGGL(k_cg_dir, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, (long long)k, a.m, a.ctx.xw, c.Minv, c.p, c.slots_v, c.g_vec);
+    hipLaunchKernelGGL(k_cg_dir, dim3((unsigned)c.geo.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, (long long)k, a.m, a.ctx.xw, c.Minv, c.p, c.slots_v, c.geo.g_vec);
     return nl;
 }
 

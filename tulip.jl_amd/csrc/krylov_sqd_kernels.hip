@@ -20,12 +20,14 @@
 //
 // Rows and columns of an LP hold a handful of entries: 8 lanes per row, 4 per column, handed out round by round.  A row or column with more than
 // CG_LONG entries is listed at create and gets a whole workgroup in the same launch, behind those of the short ones.
+// The gather itself is krylov_spmv.hpp's: a kernel here supplies the addend of an entry and what one lane does with a finished sum.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
 
 #include "krylov_reduce.hpp"
+#include "krylov_spmv.hpp"
 #include "tlpk_device.hpp"
 
 namespace tlpk {
@@ -106,70 +108,26 @@ __global__ __launch_bounds__(TC_OP_THREADS) void k_tc_op(const TcScalars *__rest
     const double beta = sc->st[par].beta, gamma = sc->st[par].gamma;
     const double *__restrict__ u = w, *__restrict__ v = w + n;
     double acc = 0.0;
-    unsigned b = blockIdx.x;
+    const auto col_term = [&](i64 q) { return Ax[q] * v[Ai[q]]; };
+    const auto col_done = [&](i64 j, double s) { t[j] = s - beta * (W[j] * wo[j]); };
+    const auto row_term = [&](i64 q) { return Tx[q] * u[Tj[q]]; };
+    const auto row_done = [&](i64 i, double s) {
+        const double qi = s - gamma * (W[n + i] * wo[n + i]);
+        t[n + i] = qi; acc += v[i] * qi;
+    };
+    // acc: this workgroup's part of alpha, spread over the lanes of the short rows, on the first thread of the long ones; the columns leave it zero
+    const unsigned b = blockIdx.x;
     if (b < gc) {
-        const int lane = threadIdx.x & 3;
-        const i64 per_round = (i64)gc * (TC_OP_THREADS / 4);
-        for (i64 base = 0; base < n; base += per_round) {
-            const i64 j = base + (((i64)b * TC_OP_THREADS + threadIdx.x) >> 2);
-            const bool live = j < n;
-            const i64 q0 = live ? Ap[j] : 0, q1 = live ? Ap[j + 1] : 0;
-            const bool mine = live && q1 - q0 <= CG_LONG;
-            double s = 0.0;
-            if (mine) for (i64 q = q0 + lane; q < q1; q += 4) s += Ax[q] * v[Ai[q]];
-            s += __shfl_down(s, 2, 4);
-            s += __shfl_down(s, 1, 4);
-            if (mine && lane == 0) t[j] = s - beta * (W[j] * wo[j]);
-        }
-        if (threadIdx.x == 0) slots_a[blockIdx.x] = 0.0;
-        return;
-    }
-    b -= gc;
-    if (b < gr) {
-        const int lane = threadIdx.x & 7;
-        const i64 per_round = (i64)gr * (TC_OP_THREADS / 8);
-        for (i64 base = 0; base < m; base += per_round) {
-            const i64 i = base + (((i64)b * TC_OP_THREADS + threadIdx.x) >> 3);
-            const bool live = i < m;
-            const i64 q0 = live ? Tp[i] : 0, q1 = live ? Tp[i + 1] : 0;
-            const bool mine = live && q1 - q0 <= CG_LONG;
-            double s = 0.0;
-            if (mine) for (i64 q = q0 + lane; q < q1; q += 8) s += Tx[q] * u[Tj[q]];
-#pragma unroll
-            for (int off = 4; off > 0; off >>= 1) s += __shfl_down(s, off, 8);
-            if (mine && lane == 0) {
-                const double qi = s - gamma * (W[n + i] * wo[n + i]);
-                t[n + i] = qi; acc += v[i] * qi;
-            }
-        }
+        walk_short<TC_OP_THREADS, 4>(n, Ap, b, gc, col_term, col_done);
+    } else if (b < gc + gr) {
+        walk_short<TC_OP_THREADS, 8>(m, Tp, b - gc, gr, row_term, row_done);
         acc = cg_block_sum<TC_OP_THREADS>(acc, sh);
-        if (threadIdx.x == 0) slots_a[blockIdx.x] = acc;
-        return;
+    } else if (b < gc + gr + glc) {
+        walk_long<TC_OP_THREADS>(long_cols, n_long_cols, b - gc - gr, glc, Ap, sh, col_term, col_done);
+    } else {
+        walk_long<TC_OP_THREADS>(long_rows, n_long_rows, b - gc - gr - glc, glr, Tp, sh, row_term, row_done);
     }
-    b -= gr;
-    if (b < glc) {
-        for (i64 k = b; k < n_long_cols; k += glc) {
-            const i64 j = long_cols[k];
-            double s = 0.0;
-            for (i64 q = Ap[j] + threadIdx.x; q < Ap[j + 1]; q += TC_OP_THREADS) s += Ax[q] * v[Ai[q]];
-            s = cg_block_sum<TC_OP_THREADS>(s, sh);
-            if (threadIdx.x == 0) t[j] = s - beta * (W[j] * wo[j]);
-        }
-        if (threadIdx.x == 0) slots_a[blockIdx.x] = 0.0;
-        return;
-    }
-    b -= glc;
-    for (i64 k = b; k < n_long_rows; k += glr) {
-        const i64 i = long_rows[k];
-        double s = 0.0;
-        for (i64 q = Tp[i] + threadIdx.x; q < Tp[i + 1]; q += TC_OP_THREADS) s += Tx[q] * u[Tj[q]];
-        s = cg_block_sum<TC_OP_THREADS>(s, sh);
-        if (threadIdx.x == 0) {
-            const double qi = s - gamma * (W[n + i] * wo[n + i]);
-            t[n + i] = qi; acc += v[i] * qi;
-        }
-    }
-    if (threadIdx.x == 0) slots_a[blockIdx.x] = acc;
+    if (threadIdx.x == 0) slots_a[b] = acc;
 }
 
 // alpha from the slots; t -= alpha W.w; the partial sums of p' E^-1 p (slots_g) and q' Rd^-1 q (slots_b)
@@ -243,8 +201,6 @@ __global__ __launch_bounds__(CG_THREADS) void k_tc_upd(TcScalars *__restrict__ s
     }
 }
 
-inline unsigned nblk(i64 n, int b) { return (unsigned)((n + b - 1) / b); }
-
 }  // namespace
 
 void launch_tc_diag(hipStream_t st, const DevArrays &a, const TcArrays &c, const double *theta, const double *regP, const double *regD) {
@@ -254,22 +210,22 @@ void launch_tc_diag(hipStream_t st, const DevArrays &a, const TcArrays &c, const
 
 void launch_tc_init(hipStream_t st, const DevArrays &a, const TcArrays &c, const double *xi_p, const double *xi_d, double atol, double rtol, i64 itmax) {
     const i64 N = a.n + a.m;
-    if (N > 0) hipLaunchKernelGGL(k_tc_init, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, a.n, N, xi_d, xi_p, c.Winv, c.t, c.slots_g, c.slots_b);
-    hipLaunchKernelGGL(k_tc_start, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, c.sc, a.n, N, c.Winv, c.t, c.w[0], c.w[1], c.x, c.g[0], c.g[1], c.slots_g,
-                       c.slots_b, N > 0 ? c.g_vec : 0, atol, rtol, (long long)itmax);
+    if (N > 0) hipLaunchKernelGGL(k_tc_init, dim3((unsigned)c.geo.g_vec), dim3(CG_THREADS), 0, st, a.n, N, xi_d, xi_p, c.Winv, c.t, c.slots_g, c.slots_b);
+    hipLaunchKernelGGL(k_tc_start, dim3((unsigned)c.geo.g_vec), dim3(CG_THREADS), 0, st, c.sc, a.n, N, c.Winv, c.t, c.w[0], c.w[1], c.x, c.g[0], c.g[1], c.slots_g,
+                       c.slots_b, N > 0 ? c.geo.g_vec : 0, atol, rtol, (long long)itmax);
 }
 
 int launch_tc_iter(hipStream_t st, const DevArrays &a, const TcArrays &c, i64 k) {
     const i64 N = a.n + a.m;
     if (N <= 0) return 0;
     const int par = (int)(k & 1);
-    const int ns_a = c.g_cols + c.g_rows + c.g_lcols + c.g_lrows;
+    const int ns_a = c.geo.g_cols + c.geo.g_rows + c.geo.g_lcols + c.geo.g_lrows;
     hipLaunchKernelGGL(k_tc_op, dim3((unsigned)ns_a), dim3(TC_OP_THREADS), 0, st, c.sc, par, a.n, a.m, a.Ap, a.Ai, a.Ax, a.Tp, a.Tj, a.Tx, c.W, c.w[par], c.w[par ^ 1],
-                       c.t, c.slots_a, (unsigned)c.g_cols, (unsigned)c.g_rows, (unsigned)c.g_lcols, (unsigned)c.g_lrows, c.long_cols, c.n_long_cols, c.long_rows,
-                       c.n_long_rows);
-    hipLaunchKernelGGL(k_tc_step, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, c.sc, a.n, N, c.W, c.Winv, c.w[par], c.t, c.slots_a, ns_a, c.slots_g, c.slots_b);
-    hipLaunchKernelGGL(k_tc_upd, dim3((unsigned)c.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, k == 0 ? 1 : 0, (long long)k, a.n, N, c.Winv, c.t, c.w[par],
-                       c.w[par ^ 1], c.g[0], c.g[1], c.x, c.slots_g, c.slots_b, c.g_vec);
+                       c.t, c.slots_a, (unsigned)c.geo.g_cols, (unsigned)c.geo.g_rows, (unsigned)c.geo.g_lcols, (unsigned)c.geo.g_lrows, c.geo.long_cols, c.geo.n_long_cols, c.geo.long_rows,
+                       c.geo.n_long_rows);
+    hipLaunchKernelGGL(k_tc_step, dim3((unsigned)c.geo.g_vec), dim3(CG_THREADS), 0, st, c.sc, a.n, N, c.W, c.Winv, c.w[par], c.t, c.slots_a, ns_a, c.slots_g, c.slots_b);
+    hipLaunchKernelGGL(k_tc_upd, dim3((unsigned)c.geo.g_vec), dim3(CG_THREADS), 0, st, c.sc, par, k == 0 ? 1 : 0, (long long)k, a.n, N, c.Winv, c.t, c.w[par],
+                       c.w[par ^ 1], c.g[0], c.g[1], c.x, c.slots_g, c.slots_b, c.geo.g_vec);
     return 3;
 }
 

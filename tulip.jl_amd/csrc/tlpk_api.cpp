@@ -21,9 +21,11 @@
 #include <optional>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 #include <condition_variable>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 
 #include "../../include/tlpk.h"
@@ -525,7 +527,7 @@ int tlpk_device_count(void) {
 
 int tlpk_host_copy_threads(void) { return host_copy_threads(); }
 
-// ---- matrix-free K1 (tlpk_options.krylov): set-up ----
+// ---- matrix-free handles (tlpk_options.krylov): set-up ----
 // device memory of such a handle: the CSC copy of A and two row-wise copies (36 nnz), the vectors of every handle and of the iteration
 static inline bool krylov_k2(const tlpk_handle *h) { return h->krylov == TLPK_KRYLOV_MINRES || h->krylov == TLPK_KRYLOV_TRICG; }
 static double krylov_bytes(const tlpk_handle *h) {
@@ -536,7 +538,6 @@ static double krylov_bytes(const tlpk_handle *h) {
     if (h->krylov == TLPK_KRYLOV_MINRES) return 36.0 * (double)h->S.nnzA + 144.0 * (double)h->S.n + 176.0 * (double)h->S.m + 65536.0;
     return 36.0 * (double)h->S.nnzA + 80.0 * (double)h->S.n + 136.0 * (double)h->S.m + 65536.0;
 }
-// the options of a matrix-free handle: nullptr, or the sentence that says what is wrong
 // the memory gate of a matrix-free handle, with or without a device
 static int krylov_gate(tlpk_handle *h, double budget) {
     const double need = krylov_bytes(h);
@@ -546,6 +547,7 @@ static int krylov_gate(tlpk_handle *h, double budget) {
     return TLPK_TOO_LARGE;
 }
 
+// the options of a matrix-free handle: nullptr, or the sentence that says what is wrong
 static const char *krylov_check(const tlpk_options &def) {
     if (def.krylov != TLPK_KRYLOV_CG && def.krylov != TLPK_KRYLOV_MINRES && def.krylov != TLPK_KRYLOV_TRICG)
         return "krylov: TLPK_KRYLOV_NONE (0), TLPK_KRYLOV_CG (1), TLPK_KRYLOV_MINRES (16) or TLPK_KRYLOV_TRICG (32)";
@@ -567,73 +569,71 @@ static const char *krylov_check(const tlpk_options &def) {
     if (def.user_perm) return "krylov: user_perm does not apply (there is no factor to order)";
     return nullptr;
 }
-// the vectors and scalars of the iteration, the lists of the long rows / columns, the launch geometry
-static int krylov_upload(tlpk_handle *h) {
+// The lists of the long rows / columns and the launch geometry.  The gather kernels of an iteration (k_cg_rows, k_mr_op, k_tc_op) have 1024 threads, 4 lanes per
+// column and 8 per row: at most CG_MAX_SLOTS workgroups of either kind, and CG_MAX_LONG share the long ones.  Conjugate gradients launch k_cg_rows on every
+// m (at least one workgroup) and their vectors have order m.
+static int krylov_geometry(tlpk_handle *h, KrylovGeom &g) {
     const Symbolic &S = h->S;
-    CgArrays &c = h->cg;
     const i64 m = S.m, n = S.n;
+    const bool cg = h->krylov == TLPK_KRYLOV_CG;
     std::vector<i32> lr, lc;
     for (i64 i = 0; i < m; ++i) if (S.Tp[(size_t)i + 1] - S.Tp[(size_t)i] > CG_LONG) lr.push_back((i32)i);
     for (i64 j = 0; j < n; ++j) if (S.Ap[(size_t)j + 1] - S.Ap[(size_t)j] > CG_LONG) lc.push_back((i32)j);
-    c.n_long_rows = (i64)lr.size(); c.n_long_cols = (i64)lc.size();
+    g.n_long_rows = (i64)lr.size(); g.n_long_cols = (i64)lc.size();
     int rc;
-    if ((rc = dev_upload(h, &c.long_rows, lr)) != TLPK_OK) return rc;
-    if ((rc = dev_upload(h, &c.long_cols, lc)) != TLPK_OK) return rc;
+    if ((rc = dev_upload(h, &g.long_rows, lr)) != TLPK_OK) return rc;
+    if ((rc = dev_upload(h, &g.long_cols, lc)) != TLPK_OK) return rc;
+    g.g_cols = (int)std::min<i64>((n * 4 + 1023) / 1024, CG_MAX_SLOTS);
+    g.g_rows = (int)std::max<i64>(cg ? 1 : 0, std::min<i64>((m * 8 + 1023) / 1024, CG_MAX_SLOTS));
+    g.g_lcols = (int)std::min<i64>(g.n_long_cols, CG_MAX_LONG);
+    g.g_lrows = (int)std::min<i64>(g.n_long_rows, CG_MAX_LONG);
+    g.g_vec = (int)std::max<i64>(1, std::min<i64>(((cg ? m : n + m) + 255) / 256, CG_MAX_SLOTS));
+    return TLPK_OK;
+}
+static int alloc_doubles(tlpk_handle *h, std::initializer_list<std::pair<double **, i64>> list) {
+    for (const auto &pc : list) if (int rc = dev_alloc(h, pc.first, pc.second)) return rc;
+    return TLPK_OK;
+}
+// the geometry, the vectors and scalars of the iteration, the pinned block, the event
+static int krylov_upload(tlpk_handle *h) {
+    const i64 m = h->S.m, n = h->S.n, N = n + m;
+    const bool jac = h->krylov_precond == TLPK_PRECOND_JACOBI;
+    int rc;
     if (h->krylov == TLPK_KRYLOV_TRICG) {
-        // k_tc_op has the geometry of k_mr_op; the vector kernels write two partial sums per workgroup (the n-part and the m-part)
+        // the vector kernels write two partial sums per workgroup (the n-part and the m-part)
         TcArrays &r = h->tc;
-        const i64 N = n + m;
-        r.long_rows = c.long_rows; r.long_cols = c.long_cols; r.n_long_rows = c.n_long_rows; r.n_long_cols = c.n_long_cols;
-        r.g_cols = n > 0 ? (int)std::min<i64>((n * 4 + 1023) / 1024, CG_MAX_SLOTS) : 0;
-        r.g_rows = m > 0 ? (int)std::min<i64>((m * 8 + 1023) / 1024, CG_MAX_SLOTS) : 0;
-        r.g_lcols = (int)std::min<i64>(r.n_long_cols, CG_MAX_LONG);
-        r.g_lrows = (int)std::min<i64>(r.n_long_rows, CG_MAX_LONG);
-        r.g_vec = (int)std::max<i64>(1, std::min<i64>((N + 255) / 256, CG_MAX_SLOTS));
-        if ((rc = dev_alloc(h, &r.W, N)) != TLPK_OK || (rc = dev_alloc(h, &r.Winv, N)) != TLPK_OK || (rc = dev_alloc(h, &r.w[0], N)) != TLPK_OK ||
-            (rc = dev_alloc(h, &r.w[1], N)) != TLPK_OK || (rc = dev_alloc(h, &r.t, N)) != TLPK_OK || (rc = dev_alloc(h, &r.x, N)) != TLPK_OK ||
-            (rc = dev_alloc(h, &r.g[0], N)) != TLPK_OK || (rc = dev_alloc(h, &r.g[1], N)) != TLPK_OK ||
-            (rc = dev_alloc(h, &r.slots_a, std::max(1, r.g_cols + r.g_rows + r.g_lcols + r.g_lrows))) != TLPK_OK ||
-            (rc = dev_alloc(h, &r.slots_g, r.g_vec)) != TLPK_OK || (rc = dev_alloc(h, &r.slots_b, r.g_vec)) != TLPK_OK ||
+        const KrylovGeom &g = r.geo;
+        if ((rc = krylov_geometry(h, r.geo)) != TLPK_OK ||
+            (rc = alloc_doubles(h, {{&r.W, N}, {&r.Winv, N}, {&r.w[0], N}, {&r.w[1], N}, {&r.t, N}, {&r.x, N}, {&r.g[0], N}, {&r.g[1], N},
+                                    {&r.slots_a, std::max(1, g.g_cols + g.g_rows + g.g_lcols + g.g_lrows)}, {&r.slots_g, g.g_vec}, {&r.slots_b, g.g_vec}})) != TLPK_OK ||
             (rc = dev_alloc(h, &r.sc, 1)) != TLPK_OK || (rc = dev_alloc(h, &r.bad, 1)) != TLPK_OK) return rc;
         HIPCHK(h, hipMemset(r.sc, 0, sizeof(TcScalars)));
-        HIPCHK(h, hipHostMalloc((void **)&h->tc_pin, sizeof(TcScalars) + sizeof(long long), hipHostMallocDefault));
-        std::memset(h->tc_pin, 0, sizeof(TcScalars) + sizeof(long long));
     } else if (h->krylov == TLPK_KRYLOV_MINRES) {
-        // k_mr_op: 1024 threads, 4 lanes per column and 8 per row; at most CG_MAX_SLOTS workgroups of either kind, CG_MAX_LONG share the long ones
         MrArrays &r = h->mr;
-        const i64 N = n + m;
-        r.long_rows = c.long_rows; r.long_cols = c.long_cols; r.n_long_rows = c.n_long_rows; r.n_long_cols = c.n_long_cols;
-        r.g_cols = n > 0 ? (int)std::min<i64>((n * 4 + 1023) / 1024, CG_MAX_SLOTS) : 0;
-        r.g_rows = m > 0 ? (int)std::min<i64>((m * 8 + 1023) / 1024, CG_MAX_SLOTS) : 0;
-        r.g_lcols = (int)std::min<i64>(r.n_long_cols, CG_MAX_LONG);
-        r.g_lrows = (int)std::min<i64>(r.n_long_rows, CG_MAX_LONG);
-        r.g_vec = (int)std::max<i64>(1, std::min<i64>((N + 255) / 256, CG_MAX_SLOTS));
-        const bool jac = h->krylov_precond == TLPK_PRECOND_JACOBI;
-        if ((rc = dev_alloc(h, &r.r[0], N)) != TLPK_OK || (rc = dev_alloc(h, &r.r[1], N)) != TLPK_OK || (rc = dev_alloc(h, &r.u, N)) != TLPK_OK ||
-            (rc = dev_alloc(h, &r.x, N)) != TLPK_OK || (rc = dev_alloc(h, &r.w[0], N)) != TLPK_OK || (rc = dev_alloc(h, &r.w[1], N)) != TLPK_OK ||
-            (rc = dev_alloc(h, &r.slots_a, std::max(1, r.g_cols + r.g_rows + r.g_lcols + r.g_lrows))) != TLPK_OK ||
-            (rc = dev_alloc(h, &r.slots_g, r.g_vec)) != TLPK_OK || (rc = dev_alloc(h, &r.sc, 1)) != TLPK_OK) return rc;
-        if (jac && ((rc = dev_alloc(h, &r.z[0], N)) != TLPK_OK || (rc = dev_alloc(h, &r.z[1], N)) != TLPK_OK || (rc = dev_alloc(h, &r.Minv, N)) != TLPK_OK)) return rc;
+        const KrylovGeom &g = r.geo;
+        if ((rc = krylov_geometry(h, r.geo)) != TLPK_OK ||
+            (rc = alloc_doubles(h, {{&r.r[0], N}, {&r.r[1], N}, {&r.u, N}, {&r.x, N}, {&r.w[0], N}, {&r.w[1], N},
+                                    {&r.slots_a, std::max(1, g.g_cols + g.g_rows + g.g_lcols + g.g_lrows)}, {&r.slots_g, g.g_vec}})) != TLPK_OK ||
+            (rc = dev_alloc(h, &r.sc, 1)) != TLPK_OK) return rc;
+        if (jac && (rc = alloc_doubles(h, {{&r.z[0], N}, {&r.z[1], N}, {&r.Minv, N}})) != TLPK_OK) return rc;
         if (!jac) { r.z[0] = r.r[0]; r.z[1] = r.r[1]; }
         HIPCHK(h, hipMemset(r.sc, 0, sizeof(MrScalars)));
-        HIPCHK(h, hipHostMalloc((void **)&h->mr_pin, sizeof(MrScalars), hipHostMallocDefault));
-        std::memset(h->mr_pin, 0, sizeof(MrScalars));
     } else {
-        c.g_rows = (int)std::max<i64>(1, std::min<i64>((m * 8 + 1023) / 1024, CG_MAX_SLOTS));      // (k_cg_rows: 1024 threads, 8 lanes per row)
-        c.g_long = (int)std::min<i64>(c.n_long_rows, CG_MAX_LONG);
-        c.g_vec = (int)std::max<i64>(1, std::min<i64>((m + 255) / 256, CG_MAX_SLOTS));
-        if ((rc = dev_alloc(h, &c.x, m)) != TLPK_OK || (rc = dev_alloc(h, &c.p, m)) != TLPK_OK || (rc = dev_alloc(h, &c.q, m)) != TLPK_OK ||
-            (rc = dev_alloc(h, &c.t, n)) != TLPK_OK || (rc = dev_alloc(h, &c.slots_r, c.g_rows + c.g_long)) != TLPK_OK ||
-            (rc = dev_alloc(h, &c.slots_v, c.g_vec)) != TLPK_OK || (rc = dev_alloc(h, &c.sc, 1)) != TLPK_OK) return rc;
-        if (h->krylov_precond == TLPK_PRECOND_JACOBI && (rc = dev_alloc(h, &c.Minv, m)) != TLPK_OK) return rc;
+        CgArrays &c = h->cg;
+        const KrylovGeom &g = c.geo;
+        if ((rc = krylov_geometry(h, c.geo)) != TLPK_OK ||
+            (rc = alloc_doubles(h, {{&c.x, m}, {&c.p, m}, {&c.q, m}, {&c.t, n}, {&c.slots_r, g.g_rows + g.g_lrows}, {&c.slots_v, g.g_vec}})) != TLPK_OK ||
+            (rc = dev_alloc(h, &c.sc, 1)) != TLPK_OK) return rc;
+        if (jac && (rc = dev_alloc(h, &c.Minv, m)) != TLPK_OK) return rc;
         HIPCHK(h, hipMemset(c.sc, 0, sizeof(CgScalars)));
-        HIPCHK(h, hipHostMalloc((void **)&h->cg_pin, sizeof(CgScalars), hipHostMallocDefault));
-        std::memset(h->cg_pin, 0, sizeof(CgScalars));
     }
-    HIPCHK(h, hipEventCreateWithFlags(&h->cg_ev, hipEventDisableTiming));
+    static_assert(sizeof(CgScalars) <= sizeof(TcScalars) && sizeof(MrScalars) <= sizeof(TcScalars), "krylov_pin holds the largest scalar block");
+    HIPCHK(h, hipHostMalloc(&h->krylov_pin, sizeof(TcScalars) + sizeof(long long), hipHostMallocDefault));
+    std::memset(h->krylov_pin, 0, sizeof(TcScalars) + sizeof(long long));
+    HIPCHK(h, hipEventCreateWithFlags(&h->krylov_ev, hipEventDisableTiming));
     if (const char *e = std::getenv("TLPK_CG_CHUNK")) {
         long long a = 0, b = 0;
-        if (std::sscanf(e, "%lld,%lld", &a, &b) == 2 && a >= 1 && b >= a) { h->cg_chunk0 = a; h->cg_chunk_max = b; }
+        if (std::sscanf(e, "%lld,%lld", &a, &b) == 2 && a >= 1 && b >= a) { h->krylov_chunk0 = a; h->krylov_chunk_max = b; }
     }
     return TLPK_OK;
 }
@@ -962,10 +962,8 @@ void tlpk_destroy(tlpk_handle *h) {
         if (h->h_info) hipHostFree(h->h_info);
         if (h->pin_in) hipHostFree(h->pin_in);
         if (h->pin_out) hipHostFree(h->pin_out);
-        if (h->cg_pin) hipHostFree(h->cg_pin);
-        if (h->mr_pin) hipHostFree(h->mr_pin);
-        if (h->tc_pin) hipHostFree(h->tc_pin);
-        if (h->cg_ev) hipEventDestroy(h->cg_ev);
+        if (h->krylov_pin) hipHostFree(h->krylov_pin);
+        if (h->krylov_ev) hipEventDestroy(h->krylov_ev);
         for (hipEvent_t e : h->io_events) hipEventDestroy(e);
         for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
         if (h->ev0) hipEventDestroy(h->ev0);
@@ -1225,7 +1223,7 @@ static int update_async_wait(tlpk_handle *h) {
     return rc;
 }
 
-// ---- matrix-free K1 (tlpk_options.krylov): update and solve ----
+// ---- matrix-free handles (tlpk_options.krylov): update ----
 // update: D = 1 / (theta^-1 + Rp) and, with Jacobi, the inverted diagonal of S; there is no factor that could fail
 static int krylov_update(tlpk_handle *h, const double *d_theta, const double *d_regP, const double *d_regD) {
     if (int rc = update_begin(h, d_theta, d_regP, d_regD)) return rc;
@@ -1233,7 +1231,7 @@ static int krylov_update(tlpk_handle *h, const double *d_theta, const double *d_
     if (h->krylov == TLPK_KRYLOV_TRICG) {
         // W = [E; Rd] and 1 / W in one launch; the status word (the smallest node whose entry is not positive) comes back behind it
         ProfScope ps(h, TLPK_KC_SPMV);
-        tc_bad = reinterpret_cast<long long *>(h->tc_pin + 1);
+        tc_bad = reinterpret_cast<long long *>(static_cast<TcScalars *>(h->krylov_pin) + 1);
         *tc_bad = LLONG_MAX;
         HIPCHK(h, hipMemcpyAsync(h->tc.bad, tc_bad, sizeof(long long), hipMemcpyHostToDevice, h->stream));
         launch_tc_diag(h->stream, h->d, h->tc, h->d_theta, h->d_regP, h->d_regD);
@@ -1252,7 +1250,7 @@ static int krylov_update(tlpk_handle *h, const double *d_theta, const double *d_
     HIPCHK(h, hipGetLastError());
     float ms = 0.f; hipEventElapsedTime(&ms, h->ev0, h->ev1); h->ms_update = ms;
     prof_collect(h);
-    h->cg_iters_total = 0;
+    h->krylov_iters_total = 0;
     if (tc_bad && *tc_bad != LLONG_MAX) {          // (factored stays false: the handle takes the next update)
         h->fail_col = *tc_bad;
         h->last_error = "TriCG: K2 is not quasi-definite: theta^-1 + Rp (nodes 0 .. n - 1) and Rd (nodes n .. n + m - 1) must be positive, node " +
@@ -1573,131 +1571,81 @@ static int solve_composed(tlpk_handle *h, const SolveIo &io, bool whole) {
     return solve_whole(h, io);
 }
 
-// ---- matrix-free K1 / K2 (tlpk_options.krylov) ----
-// MINRES on K2: b = [xi_d; xi_p] (KKT.jl:70-75, what the reference's run_ls_tests checks; src/KKT/Krylov/sid.jl:96-97 packs [xi_p; xi_d] against an operator
-// ordered [n; m], which its all-ones fixture cannot tell apart -- the system of KKT.jl is the one solved here).  The same chunked enqueue as conjugate
-// gradients; launches: 2 (init) + 3 per enqueued iteration; dx = x[0:n], dy = x[n:n+m] are two device copies behind the last chunk.
-static int minres_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
-    const i64 m = h->S.m, n = h->S.n, N = m + n, itmax = h->krylov_itmax;
-    i64 launches = 2;
-    { ProfScope ps(h, TLPK_KC_SPMV); launch_mr_init(h->stream, h->d, h->mr, d_xip, d_xid, h->krylov_atol, h->krylov_rtol, itmax); }
-    i64 enq = 0, chunk = h->cg_chunk0;
+// ---- matrix-free handles (tlpk_options.krylov): solve ----
+// The driver of the three methods.  init() and then iterations in chunks: enqueue a chunk, copy the scalar block (Sc: CgScalars, MrScalars or TcScalars) to
+// pinned memory, wait, and decide whether another chunk is needed (the kernels of a chunk enqueued past the end of the solve return at once).  The first
+// chunk goes out before the first look (a zero right-hand side is settled by init(), and the chunk behind it returns at once), so a solve that fits the
+// first chunk costs one host round trip.  BLOCKS until the outcome is known and fills the statistics of the solve.  order: of the system, 0 = nothing to
+// iterate on; launches: those the caller accounts for outside iter(k), which returns its own.
+extern "C++" template <class Sc, class Init, class Iter>
+static int krylov_run(tlpk_handle *h, const Sc *d_sc, i64 order, const char *method, i64 launches, Init init, Iter iter) {
+    const i64 itmax = h->krylov_itmax;
+    const Sc &sc = *static_cast<const Sc *>(h->krylov_pin);
+    { ProfScope ps(h, TLPK_KC_SPMV); init(); }
+    i64 enq = 0, chunk = h->krylov_chunk0;
     for (;;) {
-        const i64 cnt = N > 0 ? std::min(chunk, itmax - enq) : 0;
+        const i64 cnt = order > 0 ? std::min(chunk, itmax - enq) : 0;
         {
             ProfScope ps(h, TLPK_KC_SPMV);
-            for (i64 k = enq; k < enq + cnt; ++k) launches += launch_mr_iter(h->stream, h->d, h->mr, h->d_D, h->d_regD, k);
+            for (i64 k = enq; k < enq + cnt; ++k) launches += iter(k);
         }
         HIPCHK(h, hipGetLastError());
         enq += cnt;
-        chunk = std::min(chunk * 2, h->cg_chunk_max);
-        HIPCHK(h, hipMemcpyAsync(h->mr_pin, h->mr.sc, sizeof(MrScalars), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipEventRecord(h->cg_ev, h->stream));
-        HIPCHK(h, hipEventSynchronize(h->cg_ev));
-        if (h->mr_pin->outcome != CG_RUNNING || enq >= itmax || N <= 0) break;
+        chunk = std::min(chunk * 2, h->krylov_chunk_max);
+        HIPCHK(h, hipMemcpyAsync(h->krylov_pin, d_sc, sizeof(Sc), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipEventRecord(h->krylov_ev, h->stream));
+        HIPCHK(h, hipEventSynchronize(h->krylov_ev));
+        if (sc.outcome != CG_RUNNING || enq >= itmax || order <= 0) break;
     }
-    const MrScalars &sc = *h->mr_pin;
-    h->cg_iters = sc.iters; h->cg_iters_total += sc.iters; h->cg_converged = mr_outcome(sc) == CG_SOLVED ? 1 : 0;
-    if (!h->cg_converged) ++h->cg_unsolved;
-    h->cg_resid0 = sc.resid0; h->cg_resid = sc.resid; h->cg_launches = launches;
+    // (MINRES and TriCG stamp the deciding iteration into the word above the code)
+    h->krylov_iters = sc.iters; h->krylov_iters_total += sc.iters; h->krylov_converged = (sc.outcome & 0xff) == CG_SOLVED ? 1 : 0;
+    if (!h->krylov_converged) ++h->krylov_unsolved;
+    h->krylov_resid0 = sc.resid0; h->krylov_resid = sc.resid; h->krylov_launches = launches;
     if (sc.outcome == CG_RUNNING) {
         solve_end(h);
-        h->last_error = "MINRES: every iteration was enqueued and the outcome word is still unset";
+        h->last_error = std::string(method) + ": every iteration was enqueued and the outcome word is still unset";
         return TLPK_INTERNAL;
     }
-    {
-        ProfScope ps(h, TLPK_KC_SPMV);
-        if (n > 0) HIPCHK(h, hipMemcpyAsync(d_dx, h->mr.x, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
-        if (m > 0) HIPCHK(h, hipMemcpyAsync(d_dy, h->mr.x + n, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
-    }
-    return solve_end(h);
+    return TLPK_OK;
 }
 
-// TriCG on the quasi-definite form of K2: the same chunked enqueue; launches: 2 (init) + 3 per enqueued iteration; x = [dx; dy]
-static int tricg_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
-    const i64 m = h->S.m, n = h->S.n, N = m + n, itmax = h->krylov_itmax;
-    i64 launches = 2;
-    { ProfScope ps(h, TLPK_KC_SPMV); launch_tc_init(h->stream, h->d, h->tc, d_xip, d_xid, h->krylov_atol, h->krylov_rtol, itmax); }
-    i64 enq = 0, chunk = h->cg_chunk0;
-    for (;;) {
-        const i64 cnt = N > 0 ? std::min(chunk, itmax - enq) : 0;
-        {
-            ProfScope ps(h, TLPK_KC_SPMV);
-            for (i64 k = enq; k < enq + cnt; ++k) launches += launch_tc_iter(h->stream, h->d, h->tc, k);
-        }
-        HIPCHK(h, hipGetLastError());
-        enq += cnt;
-        chunk = std::min(chunk * 2, h->cg_chunk_max);
-        HIPCHK(h, hipMemcpyAsync(h->tc_pin, h->tc.sc, sizeof(TcScalars), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipEventRecord(h->cg_ev, h->stream));
-        HIPCHK(h, hipEventSynchronize(h->cg_ev));
-        if (h->tc_pin->outcome != CG_RUNNING || enq >= itmax || N <= 0) break;
-    }
-    const TcScalars &sc = *h->tc_pin;
-    h->cg_iters = sc.iters; h->cg_iters_total += sc.iters; h->cg_converged = tc_outcome(sc) == CG_SOLVED ? 1 : 0;
-    if (!h->cg_converged) ++h->cg_unsolved;
-    h->cg_resid0 = sc.resid0; h->cg_resid = sc.resid; h->cg_launches = launches;
-    if (sc.outcome == CG_RUNNING) {
-        solve_end(h);
-        h->last_error = "TriCG: every iteration was enqueued and the outcome word is still unset";
-        return TLPK_INTERNAL;
-    }
-    {
-        ProfScope ps(h, TLPK_KC_SPMV);
-        if (n > 0) HIPCHK(h, hipMemcpyAsync(d_dx, h->tc.x, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
-        if (m > 0) HIPCHK(h, hipMemcpyAsync(d_dy, h->tc.x + n, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
-    }
-    return solve_end(h);
-}
-
-// solve: b into xw, conjugate gradients from x = 0 in chunks of iterations -- after each chunk the scalar block comes back through pinned memory and the
-// host decides whether another chunk is needed (the kernels of a chunk enqueued past the end of the solve return at once) --, then dy = x and dx.
-// BLOCKS until the outcome is known; dy / dx are enqueued behind it.
+// K2 (MINRES, TriCG): b = [xi_d; xi_p] (KKT.jl:70-75, what the reference's run_ls_tests checks; src/KKT/Krylov/sid.jl:96-97 packs [xi_p; xi_d] against an operator
+// ordered [n; m], which its all-ones fixture cannot tell apart -- the system of KKT.jl is the one solved here).  Launches: 2 (init) + 3 per enqueued iteration;
+// dx = x[0:n], dy = x[n:n+m] are two device copies behind the last chunk.
+// K1 (conjugate gradients): b into xw, the iteration from x = 0, then dy = x and dx.  Launches: 2 (b) + 2 (init) + 3 or 4 per enqueued iteration + 1 (dx).
 static int krylov_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
     if (!d_dx || !d_dy) return TLPK_BADARG;
     if (int g = refuse(h, d_xip && d_xid, R_MULTI | R_DEVICE | R_FACTORED)) return g;
     if (int rc = solve_begin(h)) return rc;
-    if (h->krylov == TLPK_KRYLOV_MINRES) return minres_solve(h, d_dx, d_dy, d_xip, d_xid);
-    if (h->krylov == TLPK_KRYLOV_TRICG) return tricg_solve(h, d_dx, d_dy, d_xip, d_xid);
-    const double *xp[2] = {d_xip, d_xip}, *xd[2] = {d_xid, d_xid};
+    const i64 m = h->S.m, n = h->S.n, itmax = h->krylov_itmax;
+    const double atol = h->krylov_atol, rtol = h->krylov_rtol;
+    const double *xp[2] = {d_xip, d_xip}, *xd[2] = {d_xid, d_xid};      // (conjugate gradients: launch_rhs and launch_dx take a pair)
     double *dy[2] = {d_dy, d_dy}, *dx[2] = {d_dx, d_dx};
-    const i64 m = h->S.m, itmax = h->krylov_itmax;
-    i64 launches = 4;
+    const double *x = nullptr;          // K2: the iterate [dx; dy]
+    int rc;
+    if (h->krylov == TLPK_KRYLOV_MINRES) {
+        x = h->mr.x;
+        rc = krylov_run(h, h->mr.sc, n + m, "MINRES", 2, [&] { launch_mr_init(h->stream, h->d, h->mr, d_xip, d_xid, atol, rtol, itmax); },
+                        [&](i64 k) { return launch_mr_iter(h->stream, h->d, h->mr, h->d_D, h->d_regD, k); });
+    } else if (h->krylov == TLPK_KRYLOV_TRICG) {
+        x = h->tc.x;
+        rc = krylov_run(h, h->tc.sc, n + m, "TriCG", 2, [&] { launch_tc_init(h->stream, h->d, h->tc, d_xip, d_xid, atol, rtol, itmax); },
+                        [&](i64 k) { return launch_tc_iter(h->stream, h->d, h->tc, k); });
+    } else {
+        rc = krylov_run(h, h->cg.sc, m, "conjugate gradients", 4 + 1,
+                        [&] { launch_rhs(h->stream, h->d, h->d_D, xp, xd, 0, 1); launch_cg_init(h->stream, h->d, h->cg, atol, rtol, itmax); },
+                        [&](i64 k) { return launch_cg_iter(h->stream, h->d, h->cg, h->d_D, h->d_regD, k); });
+    }
+    if (rc != TLPK_OK) return rc;
     {
         ProfScope ps(h, TLPK_KC_SPMV);
-        launch_rhs(h->stream, h->d, h->d_D, xp, xd, 0, 1);
-        launch_cg_init(h->stream, h->d, h->cg, h->krylov_atol, h->krylov_rtol, itmax);
-    }
-    // enqueue a chunk, copy the scalars, wait: the first chunk goes out before the first look (a zero right-hand side is settled by cg_init, and the
-    // chunk behind it returns at once), so a solve that fits the first chunk costs one host round trip
-    i64 enq = 0, chunk = h->cg_chunk0;
-    for (;;) {
-        const i64 cnt = m > 0 ? std::min(chunk, itmax - enq) : 0;
-        {
-            ProfScope ps(h, TLPK_KC_SPMV);
-            for (i64 k = enq; k < enq + cnt; ++k) launches += launch_cg_iter(h->stream, h->d, h->cg, h->d_D, h->d_regD, k);
+        if (x) {
+            if (n > 0) HIPCHK(h, hipMemcpyAsync(d_dx, x, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
+            if (m > 0) HIPCHK(h, hipMemcpyAsync(d_dy, x + n, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
+        } else {
+            if (m > 0) HIPCHK(h, hipMemcpyAsync(d_dy, h->cg.x, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
+            launch_dx(h->stream, h->d, h->d_D, dy, xd, dx, 0, 1);
         }
-        HIPCHK(h, hipGetLastError());
-        enq += cnt;
-        chunk = std::min(chunk * 2, h->cg_chunk_max);
-        HIPCHK(h, hipMemcpyAsync(h->cg_pin, h->cg.sc, sizeof(CgScalars), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipEventRecord(h->cg_ev, h->stream));
-        HIPCHK(h, hipEventSynchronize(h->cg_ev));
-        if (h->cg_pin->outcome != CG_RUNNING || enq >= itmax || m <= 0) break;
-    }
-    const CgScalars &sc = *h->cg_pin;
-    h->cg_iters = sc.iters; h->cg_iters_total += sc.iters; h->cg_converged = sc.outcome == CG_SOLVED ? 1 : 0;
-    if (!h->cg_converged) ++h->cg_unsolved;
-    h->cg_resid0 = sc.resid0; h->cg_resid = sc.resid; h->cg_launches = launches + 1;
-    if (sc.outcome == CG_RUNNING) {
-        solve_end(h);
-        h->last_error = "conjugate gradients: every iteration was enqueued and the outcome word is still unset";
-        return TLPK_INTERNAL;
-    }
-    {
-        ProfScope ps(h, TLPK_KC_SPMV);
-        if (m > 0) HIPCHK(h, hipMemcpyAsync(d_dy, h->cg.x, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
-        launch_dx(h->stream, h->d, h->d_D, dy, xd, dx, 0, 1);
     }
     return solve_end(h);
 }
@@ -2637,9 +2585,9 @@ int tlpk_info(const tlpk_handle *h, tlpk_stats *out) {
     out->ms_last_set_values = h->ms_set_values; out->set_values_bytes = h->set_values_bytes;
     if (h->krylov) {
         out->launches_update = 1 + (h->krylov_precond == TLPK_PRECOND_JACOBI ? 1 : 0);      // (TriCG: the one kernel of W, 1 / W and the check)
-        out->launches_solve = h->cg_launches;                   // of the last solve: the number depends on the data
-        out->krylov_iters = h->cg_iters; out->krylov_iters_total = h->cg_iters_total; out->krylov_converged = h->cg_converged;
-        out->krylov_resid0 = h->cg_resid0; out->krylov_resid = h->cg_resid;
+        out->launches_solve = h->krylov_launches;                   // of the last solve: the number depends on the data
+        out->krylov_iters = h->krylov_iters; out->krylov_iters_total = h->krylov_iters_total; out->krylov_converged = h->krylov_converged;
+        out->krylov_resid0 = h->krylov_resid0; out->krylov_resid = h->krylov_resid;
     }
     return TLPK_OK;
 }
@@ -2726,7 +2674,7 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
     else if (w == "reduce_tasks") { for (auto &t : S.reduce_tasks) { tmp.push_back(t.front); tmp.push_back(t.k0); tmp.push_back(t.kw); tmp.push_back(t.i0); tmp.push_back(t.j0); tmp.push_back(t.jlim); tmp.push_back(t.beta0); tmp.push_back(t.pad1); } }
     else if (w == "chain_items") { for (auto &t : S.chain_items) { for (i32 v : {t.role, t.task, t.sub, t.w0, t.n0, t.need0, t.w1, t.n1, t.need1, t.w2, t.need2, t.sig}) tmp.push_back(v); } }
     else if (w == "chain_counters") tmp.assign(1, S.chain_counters);
-    else if (w == "krylov_unsolved") tmp.assign(1, h->cg_unsolved);         // matrix-free handles: solves since create that did NOT meet the stopping rule
+    else if (w == "krylov_unsolved") tmp.assign(1, h->krylov_unsolved);         // matrix-free handles: solves since create that did NOT meet the stopping rule
     else if (w == "chain_retries") tmp.assign(1, h->chain_retries);           // updates of this handle that were replayed after a dependency-driven launch gave up waiting (tlpk_update)
     else if (w == "chain_trace") {                               // diagnostics: the time stamps of the last update (the caller has synchronised)
         if (!h->d.chain_trace) return -1;

@@ -125,7 +125,7 @@ void launch_dense_gemv_n(hipStream_t st, const DevArrays &a, const double *D, co
 // out[r] = D .* (A' y[r] - xi_d[r])  (D null: A' y[r]), r < nrhs <= 2: one pass over A
 void launch_dense_gemv_t(hipStream_t st, const DevArrays &a, const double *D, const double *const *y, const double *const *xi_d, double *const *out, int nrhs);
 
-// ---- matrix-free K1: conjugate gradients on (A D A' + Rd) dy = b (krylov_kernels.hip; DESIGN.md section 1b'''') ----
+// ---- matrix-free handles (tlpk_options.krylov).  K1: conjugate gradients on (A D A' + Rd) dy = b (krylov_kernels.hip; DESIGN.md section 1b'''') ----
 // The scalars of a solve, in device memory: read by every kernel, written by ONE thread of the kernel that owns the field.  The host copies the block to
 // pinned memory after every chunk of iterations.
 struct CgScalars {
@@ -143,13 +143,20 @@ enum : long long { CG_RUNNING = 0, CG_SOLVED = 1, CG_ITMAX = 2, CG_BREAKDOWN = 3
 constexpr int CG_LONG = 512;        // a row / column with more entries gets a workgroup of its own (binned at create); shorter ones 8 / 4 lanes
 constexpr int CG_MAX_SLOTS = 256;   // workgroups (= partial sums) of the short rows / of the vector kernels
 constexpr int CG_MAX_LONG = 64;     // workgroups that share the long rows
+// The lists of the long rows / columns and the launch geometry, shared by the three methods and fixed at create (tlpk_api.cpp: krylov_geometry).  The workgroup
+// counts are the slot counts of the partial sums, so they fix the order of the additions.
+struct KrylovGeom {
+    i32 *long_rows = nullptr, *long_cols = nullptr; i64 n_long_rows = 0, n_long_cols = 0;
+    int g_cols = 0, g_rows = 0;       // workgroups of the short columns (4 lanes each) and of the short rows (8 lanes each) of a 1024-thread gather kernel
+    int g_lcols = 0, g_lrows = 0;     // workgroups that share the long columns / the long rows
+    int g_vec = 0;                    // workgroups of the vector kernels (order m for conjugate gradients, n + m for MINRES and TriCG)
+};
 struct CgArrays {
     CgScalars *sc = nullptr;
     double *x = nullptr, *p = nullptr, *q = nullptr, *t = nullptr;
     double *Minv = nullptr;                       // Jacobi: 1 / diag(A D A' + Rd); nullptr = no preconditioner
     double *slots_r = nullptr, *slots_v = nullptr;   // partial sums of p'q (row kernel) and of r'z (vector kernels), one per workgroup, added in slot order by the consumer
-    i32 *long_rows = nullptr, *long_cols = nullptr; i64 n_long_rows = 0, n_long_cols = 0;
-    int g_rows = 0, g_long = 0, g_vec = 0;        // workgroups of the short rows, of the long rows, of the vector kernels
+    KrylovGeom geo;                               // k_cg_rows: g_rows (at least 1) + g_lrows workgroups; k_cg_cols and k_cg_jacobi size their own grids
 };
 void launch_cg_jacobi(hipStream_t st, const DevArrays &a, const CgArrays &c, const double *D, const double *regD);
 // r (= a.ctx.xw) holds b: x = 0, p = M^-1 r, gamma, tolerance, outcome (a zero right-hand side is solved at once)
@@ -165,13 +172,12 @@ struct MrScalars {
     double tol;           // atol + rtol beta1
     double resid0, resid; // beta1 = sqrt(b' M^-1 b) / phibar after the last completed iteration
     double alpha;         // of the running iteration: written by k_mr_step, read by k_mr_rot
-    long long outcome;    // CG_RUNNING until a kernel decides, then (outcome code) | (deciding iteration, 1-based) << 8; tlpk_device.hpp: mr_outcome
+    long long outcome;    // CG_RUNNING until a kernel decides, then (outcome code) | (deciding iteration, 1-based) << 8
     long long iters;      // completed iterations
     long long itmax;
     long long pad[9];
 };
 static_assert(sizeof(MrScalars) == 256, "MrScalars layout");
-inline long long mr_outcome(const MrScalars &sc) { return sc.outcome & 0xff; }
 struct MrArrays {
     MrScalars *sc = nullptr;
     double *r[2] = {nullptr, nullptr};            // r1 / r2 of the Lanczos recurrence, rotating by parity; order N = n + m, stored [n-part; m-part] like every vector here
@@ -180,8 +186,7 @@ struct MrArrays {
     double *w[2] = {nullptr, nullptr};
     double *Minv = nullptr;                       // Jacobi: 1 / diag(E_j, s_i); nullptr = no preconditioner
     double *slots_a = nullptr, *slots_g = nullptr;   // partial sums of v'u (k_mr_op) and of r'z (k_mr_init, k_mr_step), one per workgroup
-    i32 *long_rows = nullptr, *long_cols = nullptr; i64 n_long_rows = 0, n_long_cols = 0;
-    int g_cols = 0, g_rows = 0, g_lcols = 0, g_lrows = 0, g_vec = 0;   // workgroups of k_mr_op (short columns, short rows, long columns, long rows) / of the vector kernels
+    KrylovGeom geo;                               // k_mr_op: g_cols + g_rows + g_lcols + g_lrows workgroups, in this order
 };
 void launch_mr_diag(hipStream_t st, i64 n, const double *theta, const double *regP, double *E);
 void launch_mr_jacobi(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *E, const double *regD);
@@ -205,7 +210,6 @@ struct TcScalars {
     long long pad[9];
 };
 static_assert(sizeof(TcScalars) == 256, "TcScalars layout");
-inline long long tc_outcome(const TcScalars &sc) { return sc.outcome & 0xff; }
 struct TcArrays {
     TcScalars *sc = nullptr;
     long long *bad = nullptr;                     // update: the smallest node with a non-positive or non-finite diagonal entry, LLONG_MAX = none
@@ -214,8 +218,7 @@ struct TcArrays {
     double *t = nullptr, *x = nullptr;            // [p; q] of the iteration; the iterate [dx; dy]
     double *g[2] = {nullptr, nullptr};            // the two columns of G = [Gy; Gx], updated in place row by row
     double *slots_a = nullptr, *slots_g = nullptr, *slots_b = nullptr;   // partial sums of alpha (k_tc_op), of p'E^-1 p and of q'Rd^-1 q (k_tc_init, k_tc_step)
-    i32 *long_rows = nullptr, *long_cols = nullptr; i64 n_long_rows = 0, n_long_cols = 0;
-    int g_cols = 0, g_rows = 0, g_lcols = 0, g_lrows = 0, g_vec = 0;   // workgroups of k_tc_op (short columns, short rows, long columns, long rows) / of the vector kernels
+    KrylovGeom geo;                               // k_tc_op: g_cols + g_rows + g_lcols + g_lrows workgroups, in this order
 };
 // W, 1 / W and the quasi-definiteness check (one launch; *c.bad must hold LLONG_MAX before it)
 void launch_tc_diag(hipStream_t st, const DevArrays &a, const TcArrays &c, const double *theta, const double *regP, const double *regD);

@@ -98,22 +98,18 @@ struct tlpk_handle {
     i64 set_values_bytes = 0;           // device memory of the maps (tlpk_stats.set_values_bytes)
     double ms_set_values = 0;           // tlpk_stats.ms_last_set_values
     hipEvent_t sv_ev0 = nullptr, sv_ev1 = nullptr; bool sv_pending = false;   // ... of an enqueued refresh: read when the events have completed
-    // matrix-free K1 (tlpk_options.krylov = TLPK_KRYLOV_CG; tlpk_api.cpp: krylov_*, krylov_kernels.hip): no factor, conjugate gradients per solve
+    // matrix-free handles (tlpk_options.krylov; tlpk_api.cpp: krylov_*): no factor, an iteration per solve.  One of the three sets of arrays is in use:
+    // conjugate gradients on K1 (krylov_kernels.hip), MINRES on K2 (krylov_k2_kernels.hip), TriCG on the quasi-definite form of K2 (krylov_sqd_kernels.hip)
     int krylov = 0, krylov_precond = 0;
     i64 krylov_itmax = 0; double krylov_atol = 0, krylov_rtol = 0;      // as resolved at create (0 -> 2 m, sqrt(eps))
     CgArrays cg;
-    CgScalars *cg_pin = nullptr;        // pinned copy of the scalar block, read after every chunk of iterations
-    hipEvent_t cg_ev = nullptr;
-    i64 cg_chunk0 = 4, cg_chunk_max = 32;   // iterations enqueued before the first look at the outcome / at most between two looks (TLPK_CG_CHUNK=first,max)
-    i64 cg_iters = 0, cg_iters_total = 0, cg_converged = 0, cg_launches = 0, cg_unsolved = 0;
-    double cg_resid0 = 0, cg_resid = 0;
-    // matrix-free K2 (tlpk_options.krylov = TLPK_KRYLOV_MINRES; krylov_k2_kernels.hip): the same handle with MINRES on the augmented system; the chunking, the
-    // event and the counters above serve both methods
     MrArrays mr;
-    MrScalars *mr_pin = nullptr;
-    // the quasi-definite form of K2 (TLPK_KRYLOV_TRICG; krylov_sqd_kernels.hip); tc_pin: the scalar block, behind it the update's status word
     TcArrays tc;
-    TcScalars *tc_pin = nullptr;
+    void *krylov_pin = nullptr;         // pinned copy of the method's scalar block, read after every chunk of iterations; behind sizeof(TcScalars): TriCG's update status word
+    hipEvent_t krylov_ev = nullptr;
+    i64 krylov_chunk0 = 4, krylov_chunk_max = 32;   // iterations enqueued before the first look at the outcome / at most between two looks (TLPK_CG_CHUNK=first,max)
+    i64 krylov_iters = 0, krylov_iters_total = 0, krylov_converged = 0, krylov_launches = 0, krylov_unsolved = 0;
+    double krylov_resid0 = 0, krylov_resid = 0;
     std::string last_error;
 };
 
