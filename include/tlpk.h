@@ -359,7 +359,12 @@ int tlpk_set_profile(tlpk_handle *h, int on);   /* toggle per-launch HIP-event t
 int tlpk_get_perm(const tlpk_handle *h, int64_t *perm /*m, 0-based, perm[new] = old*/);   /* dense_cols: the constraint nodes in their order
                                                    (the whole order-(m + k) permutation: tlpk_symbolic_get(h, "perm"), node m + t = dense column t) */
 /* Symbolic structures, for tests and tools.  `what` selects an array; returns its length and,
- * if buf != NULL, copies min(len, cap) int64 entries.  One key is a counter, not a structure: "krylov_unsolved" (matrix-free handles; see tlpk_stats). */
+ * if buf != NULL, copies min(len, cap) int64 entries.  One key is a counter, not a structure: "krylov_unsolved" (matrix-free handles; see tlpk_stats).
+ * Read-only diagnostics of the launch schedule (tests/test_schedule_identity.py):
+ *   "launch_meta"  (stream group, side, pad) of every entry of "factor_launches", then of "fwd_launches", then of "bwd_launches"
+ *   "zero_tasks"   (front, first column) of every 64-column panel slice the zero-fill clears
+ *   "zero_small"   the fronts whose whole panel one wave clears
+ *   "singles"      panel offsets, inverted-diagonal offsets and columns of the isolated 1 x 1 fronts, concatenated; then n_zero_lower and spart_len */
 int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, int64_t cap);
 int64_t tlpk_symbolic_get_f64(const tlpk_handle *h, const char *what, double *buf, int64_t cap);
 /* Copy the numeric factor panels (device -> host), nnzL_stored doubles.  Layout: front s (symbolic arrays front_f, front_ns, front_loff,

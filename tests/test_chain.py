@@ -1,4 +1,4 @@
-"""The dependency-driven form of the blocked factorisation (LK_CHAIN launches, kernels.hip: k_chain; symbolic.cpp: build_chain), on the CPU: the
+"""The dependency-driven form of the blocked factorisation (LK_CHAIN launches, kernels.hip: k_chain; schedule.cpp: build_chain), on the CPU: the
 schedule the library builds is executed by the numpy emulator (tests/emulate.py) -- in ticket order, which asserts that an item only ever waits for
 items with SMALLER tickets (the no-deadlock property), and in adversarial orders in which any item whose counters have arrived may run next, which
 must give the SAME BITS (the waits alone order every pair of items that touch the same data).  The launch form (TLPK_CHAIN=0) must give those bits

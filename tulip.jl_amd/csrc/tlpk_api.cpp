@@ -450,7 +450,7 @@ inline bool graph_usable(const tlpk_handle *h) {
     return h->use_graph && !h->profile && !h->serial && (h->S.ngroups <= 1 || h->force_graph);
 }
 
-// Solves: since round 5 the solve schedule of a block-angular LP is ONE schedule on the main stream (symbolic.cpp: solve_one_group), so a solve can be
+// Solves: since round 5 the solve schedule of a block-angular LP is ONE schedule on the main stream (schedule.cpp: solve_one_group), so a solve can be
 // captured whatever the number of stream groups the factorisation uses.  What it buys there is host time: the blocking host-pointer solve
 // (tlpk_solve) starts with ~25 short launches.  MEASURED (profiles/r05_host_path.txt) and OFF by default: config C4 52.85 vs 52.66 ms per step, north-star LP
 // 139.0 vs 139.9, host-pointer path 157.3 vs 155.4 -- the host enqueues a solve in 20 - 70 us, there is nothing to hide.  TLPK_GRAPH_SOLVE=1 turns it on; never
@@ -2703,6 +2703,13 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
     else if (w == "factor_launches") { for (auto &L : S.factor_launches) { tmp.push_back(L.kind); tmp.push_back(L.first); tmp.push_back(L.count); } }
     else if (w == "fwd_launches") { for (auto &L : S.fwd_launches) { tmp.push_back(L.kind); tmp.push_back(L.first); tmp.push_back(L.count); } }
     else if (w == "bwd_launches") { for (auto &L : S.bwd_launches) { tmp.push_back(L.kind); tmp.push_back(L.first); tmp.push_back(L.count); } }
+    else if (w == "launch_meta") { for (auto *v : {&S.factor_launches, &S.fwd_launches, &S.bwd_launches}) for (auto &L : *v) { tmp.push_back(L.group); tmp.push_back(L.side); tmp.push_back(L.pad); } }
+    else if (w == "zero_tasks") from32(S.zero_tasks);
+    else if (w == "zero_small") from32(S.zero_small);
+    else if (w == "singles") {
+        tmp = S.single_loff; tmp.insert(tmp.end(), S.single_dinvoff.begin(), S.single_dinvoff.end()); tmp.insert(tmp.end(), S.single_col.begin(), S.single_col.end());
+        tmp.push_back(S.n_zero_lower); tmp.push_back(S.spart_len);
+    }
     else return -1;
     const i64 len = (i64)tmp.size();
     if (buf) std::copy(tmp.begin(), tmp.begin() + std::min(len, cap), buf);

@@ -108,7 +108,7 @@ enum LaunchKind : i32 {
                         // diagonal blocks, triangular solves and split-K reductions are ITEMS drawn from a ticket counter, released by completion counters
     , LK_UPDATE_T64     // round 6: the LAST partial round of the preceding LK_UPDATE launch as 64 x 64 tiles (UpdateTask.pad2 = 1; k_update64: 4 waves per workgroup)
 };
-// ---- dependency-driven factorisation (LK_CHAIN, symbolic.cpp: build_schedule / kernels.hip: k_chain) ----
+// ---- dependency-driven factorisation (LK_CHAIN, schedule.cpp: build_chain / kernels.hip: k_chain) ----
 // An item is one task of the ordinary kernels (an update tile, the diagonal block of a block column, a 64-row strip of a triangular solve, one eighth of a
 // split-K reduction).  It starts when the counters it names have reached their values -- every one of them is raised by items with SMALLER tickets, so a
 // workgroup only ever waits for workgroups that already run -- and raises ONE counter when its stores are published (agent-scope release).
