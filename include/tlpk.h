@@ -444,7 +444,8 @@ int tlpk_ipm_get(tlpk_handle *h, int what, double *host, int64_t len);
  *   Krylov and dense_cols handles are refused); nothing is loaded yet (either load after the other: TLPK_BADARG).  Then TLPK_NO_DEVICE on
  *   an analyse-only handle.
  *   tlpk_ipm_reset, tlpk_ipm_reload and tlpk_ipm_get serve a batch-loaded handle unchanged (stacked vectors); every other tlpk_ipm_* /
- *   tlpk_mpc_* call on it returns TLPK_BADARG, as does every tlpk_ipm_batch_* call on a handle loaded with tlpk_ipm_load (or not loaded).
+ *   unbatched tlpk_mpc_* call on it returns TLPK_BADARG, as does every tlpk_ipm_batch_* / tlpk_mpc_batch_* call on a handle loaded with
+ *   tlpk_ipm_load (or not loaded).
  *   tlpk_ipm_batch_factor: regP[k] / regD[k] are uniform within LP k.  An LP with active[k] = 0 is PARKED: theta_inv = 1, Rp = Rd = 1 on
  *   its block (the matrix the handle is analysed with), so a finished or failed LP cannot fail the update of the others.  On
  *   TLPK_NOT_POSDEF *fail_lp is the LP that owns tlpk_stats.fail_col (through the permutation; K2: node j < n is a column, n + i a row),
@@ -474,6 +475,23 @@ int tlpk_mpc_newton(tlpk_handle *h, int mode, double gmu, double *out);
 int tlpk_mpc_gap(tlpk_handle *h, double ap, double ad, double *out);
 int tlpk_mpc_targets(tlpk_handle *h, double ap_, double ad_, double tmin, double tmax);      /* step.jl:329-358 */
 int tlpk_mpc_advance(tlpk_handle *h, double ap, double ad, double *out);                     /* step.jl:112-123; out[0] = xl'zl + xu'zu */
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched device-resident MPC: the tlpk_mpc_* calls above on a handle loaded with tlpk_ipm_load_batch, with PER-LP scalars and the
+ * `active` masks of the tlpk_ipm_batch_* calls (an LP with active[k] = 0 is not touched and its outputs are 0; with nlp = 1 every call
+ * returns what its unbatched counterpart returns, bit for bit).  Shared with the HSD batch as they are: tlpk_ipm_batch_residuals with
+ * tau[k] = 1, tlpk_ipm_batch_factor (parking included), tlpk_ipm_batch_accept, tlpk_ipm_get, tlpk_ipm_reset / tlpk_ipm_reload.
+ * Refusals as the tlpk_ipm_batch_* calls: TLPK_BADARG with a sentence in tlpk_last_error on a handle that is not loaded or loaded with
+ * tlpk_ipm_load, on NULL pointers, on a mode outside 0 .. 2 and after tlpk_set_values without tlpk_ipm_reload; TLPK_NO_DEVICE on an
+ * analyse-only handle.
+ *   tlpk_mpc_batch_start: every LP is active; a failed update returns its code, as tlpk_mpc_start does.
+ * --------------------------------------------------------------------------------------------- */
+int tlpk_mpc_batch_start(tlpk_handle *h, double *out /*nlp: xl'zl + xu'zu*/);
+/* one mode for the call; out[2 k ..] = largest primal / dual step to the boundary of LP k's written direction (inf if unbounded) */
+int tlpk_mpc_batch_newton(tlpk_handle *h, int mode, const uint8_t *active, const double *gmu /*nlp*/, double *out /*2 nlp*/);
+int tlpk_mpc_batch_gap(tlpk_handle *h, const uint8_t *active, const double *ap /*nlp*/, const double *ad /*nlp*/, double *out /*2 nlp*/);
+int tlpk_mpc_batch_targets(tlpk_handle *h, const uint8_t *active, const double *par /*4 nlp: ap_, ad_, tmin, tmax*/);
+int tlpk_mpc_batch_advance(tlpk_handle *h, const uint8_t *active, const double *ap /*nlp*/, const double *ad /*nlp*/, double *out /*nlp*/);
 
 const char *tlpk_strerror(int code);
 const char *tlpk_last_error(const tlpk_handle *h);

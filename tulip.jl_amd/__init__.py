@@ -4,7 +4,7 @@ Only what the hot path needs lives here:
   csrc/      hand-written HIP kernels (gfx950) + the C-ABI library (include/tlpk.h)
   _lib.py    ctypes binding of libtlpk.so
   kkt.py     host-side mirror of Tulip's KKT interface (setup / update! / solve!)
-  hsd_batch.py  the HSD loop on a stack of small LPs, per-LP scalars and masks (tlpk_ipm_batch_*)
+  hsd_batch.py / mpc_batch.py  the HSD and MPC loops on a stack of small LPs, per-LP scalars and masks (tlpk_ipm_batch_* / tlpk_mpc_batch_*)
   hsd_device.py / mpc_device.py  optional: Tulip's HSD and MPC loops with the iterate resident in HBM (tlpk_ipm_* / tlpk_mpc_*), scalars only over PCIe
   problem.py / presolve.py / model.py  front end: free-MPS reader, standard form, presolve + scaling + postsolve, Model
   julia/     the Julia glue a Tulip maintainer adds (HIPNormalEquations <: AbstractKKTSolver)
@@ -26,6 +26,7 @@ from .kkt import (K1, K2, Backend, DenseBackend, DimensionMismatch, HIPDenseNorm
                   PosDefException, arithmetic, backend, linear_system, run_ls_tests, setup,
                   set_values, set_values_device, solve, update)
 from .hsd_batch import BatchedDeviceHSD  # noqa: F401,E402
+from .mpc_batch import BatchedDeviceMPC  # noqa: F401,E402
 from .model import Model  # noqa: F401,E402
 from .presolve import Presolve, PresolveOptions  # noqa: F401,E402
 from .problem import LP, read_free_mps, standard_form  # noqa: F401,E402

@@ -1,5 +1,5 @@
-// ipm_batch_kernels.hip -- the homogeneous self-dual kernels of ipm_kernels.hip for a STACK of LPs on one handle
-// (tlpk_ipm_load_batch; DESIGN.md section 4b').  B LPs stacked into one block-diagonal A are an ordinary handle; what
+// ipm_batch_kernels.hip -- the homogeneous self-dual and the Mehrotra kernels of ipm_kernels.hip for a STACK of LPs on one handle
+// (tlpk_ipm_load_batch; DESIGN.md sections 4b' and 4b'').  B LPs stacked into one block-diagonal A are an ordinary handle; what
 // differs per LP is every scalar of the interior-point loop (tau, eta, gamma mu, delta, dtau, the step length, the
 // regularisations) and whether the LP is still being iterated at all.
 //
@@ -139,12 +139,14 @@ __global__ __launch_bounds__(IPM_T) void k_ipmb_hdots(IpmVecs v, IpmBatch B, dou
     r = blk_sum(s1, sh); if (threadIdx.x == 0) P[1] = r;
 }
 
-// sc[0] = a_ (one trial step length for both sides), sc[1] = mu_l, sc[2] = mu_u
+// HSD (TWO = false): sc[0] = a_ (one trial step length for both sides), sc[1] = mu_l, sc[2] = mu_u
+// MPC (TWO = true):  sc[0] = ap_, sc[1] = ad_ (primal and dual trial step lengths), sc[2] = tmin, sc[3] = tmax
+template <bool TWO>
 __global__ __launch_bounds__(IPM_T) void k_ipmb_targets(IpmVecs v, IpmDir D, IpmBatch B, double *__restrict__ partials) {
     __shared__ double sh[IPM_T];
     const Seg g = seg_of(B, B.tc);
     if (!g.active) return;
-    const double a_p = g.sc[0], a_d = g.sc[0], mu_l = g.sc[1], mu_u = g.sc[2];
+    const double a_p = g.sc[0], a_d = TWO ? g.sc[1] : g.sc[0], mu_l = TWO ? g.sc[2] : g.sc[1], mu_u = TWO ? g.sc[3] : g.sc[2];
     double s0 = 0, s1 = 0;
     const i64 stride = (i64)g.nbk * blockDim.x;
     for (i64 jj = (i64)g.lb * blockDim.x + threadIdx.x; jj < g.nk; jj += stride) ipm_targets_col(v, D, g.c0 + jj, a_p, a_d, mu_l, mu_u, s0, s1);
@@ -199,12 +201,13 @@ __global__ __launch_bounds__(IPM_T) void k_ipmb_newton_post(IpmVecs v, IpmDir D,
     r = blk_min(amin_d, sh);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 1] = r;
 }
-// sc[0] = alpha (both sides)
+// HSD (TWO = false): sc[0] = alpha (both sides).  MPC (TWO = true): sc[0] = alpha_p (primal side), sc[1] = alpha_d (dual side)
+template <bool TWO>
 __global__ __launch_bounds__(IPM_T) void k_ipmb_advance(IpmVecs v, IpmDir D, IpmBatch B, double *__restrict__ partials) {
     __shared__ double sh[IPM_T];
     const Seg g = seg_of(B, B.tb);
     if (!g.active) return;
-    const double alpha = g.sc[0], alpha_d = g.sc[0];
+    const double alpha = g.sc[0], alpha_d = TWO ? g.sc[1] : g.sc[0];
     double s0 = 0;
     const i64 stride = (i64)g.nbk * blockDim.x, t0 = (i64)g.lb * blockDim.x + threadIdx.x;
     for (i64 jj = t0; jj < g.nk; jj += stride) ipm_advance_col(v, D, g.c0 + jj, alpha, alpha_d, s0);
@@ -233,6 +236,80 @@ __global__ void k_ipmb_take(double *__restrict__ dx, double *__restrict__ dy, co
 }
 
 // ---------------------------------------------------------------------------------------------
+// Mehrotra predictor-corrector on a stack of LPs (tlpk_mpc_batch_*): the segmented twins of k_mpc_fill, k_mpc_start1 .. 4 and k_mpc_gap.
+// The Newton systems go through k_ipmb_newton_pre (eta = 1, delta = 0) and k_ipmb_newton_post (dtau = 0), the targets and the
+// advance through the TWO = true forms above.
+// ---------------------------------------------------------------------------------------------
+__global__ void k_mpcb_fill(IpmVecs v, IpmBatch B, double *__restrict__ theta, double *__restrict__ regP, double *__restrict__ regD) {
+    const Seg g = seg_of(B, B.tb);
+    if (!g.active) return;
+    const i64 stride = (i64)g.nbk * blockDim.x, t0 = (i64)g.lb * blockDim.x + threadIdx.x;
+    for (i64 jj = t0; jj < g.nk; jj += stride) { const i64 j = g.c0 + jj; theta[j] = 0.0; regP[j] = 1.0; v.xid[j] = 0.0; v.hx[j] = 0.0; }
+    for (i64 ii = t0; ii < g.mk; ii += stride) { const i64 i = g.r0 + ii; regD[i] = 1e-6; v.xip[i] = 0.0; v.hy[i] = 0.0; }
+}
+__global__ __launch_bounds__(IPM_T) void k_mpcb_start1(IpmVecs v, IpmBatch B, double *__restrict__ partials) {
+    __shared__ double sh[IPM_T];
+    const Seg g = seg_of(B, B.tc);
+    if (!g.active) return;
+    double m0 = 0.0, m1 = 0.0;
+    const i64 stride = (i64)g.nbk * blockDim.x;
+    for (i64 jj = (i64)g.lb * blockDim.x + threadIdx.x; jj < g.nk; jj += stride) mpc_start1_col(v, g.c0 + jj, m0, m1);
+    double r = blk_min(m0, sh); if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 0] = r;
+    r = blk_min(m1, sh); if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 1] = r;
+}
+// sc[0] = dxs
+__global__ __launch_bounds__(IPM_T) void k_mpcb_start2(IpmVecs v, IpmBatch B, double *__restrict__ partials) {
+    __shared__ double sh[IPM_T];
+    const Seg g = seg_of(B, B.tc);
+    if (!g.active) return;
+    const double dxs = g.sc[0];
+    double m0 = 0.0, m1 = 0.0;
+    const i64 stride = (i64)g.nbk * blockDim.x;
+    for (i64 jj = (i64)g.lb * blockDim.x + threadIdx.x; jj < g.nk; jj += stride) mpc_start2_col(v, g.c0 + jj, dxs, m0, m1);
+    double r = blk_min(m0, sh); if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 0] = r;
+    r = blk_min(m1, sh); if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 1] = r;
+}
+// sc[0] = dzs
+__global__ __launch_bounds__(IPM_T) void k_mpcb_start3(IpmVecs v, IpmBatch B, double *__restrict__ partials) {
+    __shared__ double sh[IPM_T];
+    const Seg g = seg_of(B, B.tc);
+    if (!g.active) return;
+    const double dzs = g.sc[0];
+    double s0 = 0, s1 = 0, s2 = 0;
+    const i64 stride = (i64)g.nbk * blockDim.x;
+    for (i64 jj = (i64)g.lb * blockDim.x + threadIdx.x; jj < g.nk; jj += stride) mpc_start3_col(v, g.c0 + jj, dzs, s0, s1, s2);
+    double *P = partials + (size_t)blockIdx.x * IPM_SLOTS;
+    double r = blk_sum(s0, sh); if (threadIdx.x == 0) P[0] = r;
+    r = blk_sum(s1, sh); if (threadIdx.x == 0) P[1] = r;
+    r = blk_sum(s2, sh); if (threadIdx.x == 0) P[2] = r;
+}
+// sc[0] = ddx, sc[1] = ddz
+__global__ __launch_bounds__(IPM_T) void k_mpcb_start4(IpmVecs v, IpmBatch B, double *__restrict__ partials) {
+    __shared__ double sh[IPM_T];
+    const Seg g = seg_of(B, B.tc);
+    if (!g.active) return;
+    const double ddx = g.sc[0], ddz = g.sc[1];
+    double s0 = 0;
+    const i64 stride = (i64)g.nbk * blockDim.x;
+    for (i64 jj = (i64)g.lb * blockDim.x + threadIdx.x; jj < g.nk; jj += stride) mpc_start4_col(v, g.c0 + jj, ddx, ddz, s0);
+    const double r = blk_sum(s0, sh);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 0] = r;
+}
+// sc[0] = ap, sc[1] = ad
+__global__ __launch_bounds__(IPM_T) void k_mpcb_gap(IpmVecs v, IpmDir D, IpmBatch B, double *__restrict__ partials) {
+    __shared__ double sh[IPM_T];
+    const Seg g = seg_of(B, B.tc);
+    if (!g.active) return;
+    const double ap = g.sc[0], ad = g.sc[1];
+    double s0 = 0, s1 = 0;
+    const i64 stride = (i64)g.nbk * blockDim.x;
+    for (i64 jj = (i64)g.lb * blockDim.x + threadIdx.x; jj < g.nk; jj += stride) mpc_gap_col(v, D, g.c0 + jj, ap, ad, s0, s1);
+    double *P = partials + (size_t)blockIdx.x * IPM_SLOTS;
+    double r = blk_sum(s0, sh); if (threadIdx.x == 0) P[0] = r;
+    r = blk_sum(s1, sh); if (threadIdx.x == 0) P[1] = r;
+}
+
+// ---------------------------------------------------------------------------------------------
 void ipmb_launch_finalize(hipStream_t st, const IpmBatch &B, const IpmBlockTab &t, int nsum, int nmax, int nmin, const double *partials, double *out) {
     hipLaunchKernelGGL(k_ipmb_finalize, dim3((unsigned)B.nlp), dim3(64 * (nsum + nmax + nmin)), 0, st, B, t, nsum, nmax, nmin, partials, out);
 }
@@ -244,7 +321,7 @@ void ipmb_launch_theta(hipStream_t st, const IpmVecs &v, const IpmBatch &B, doub
 void ipmb_launch_hrhs(hipStream_t st, const IpmVecs &v, const IpmBatch &B) { hipLaunchKernelGGL(k_ipmb_hrhs, dim3(B.tc.nblocks), dim3(IPM_T), 0, st, v, B); }
 void ipmb_launch_hdots(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *partials) { hipLaunchKernelGGL(k_ipmb_hdots, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, B, partials); }
 void ipmb_launch_targets(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials) {
-    hipLaunchKernelGGL(k_ipmb_targets, dim3(B.tc.nblocks), dim3(IPM_T), 0, st, v, D, B, partials);
+    hipLaunchKernelGGL(k_ipmb_targets<false>, dim3(B.tc.nblocks), dim3(IPM_T), 0, st, v, D, B, partials);
 }
 void ipmb_launch_newton_pre(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, int mode, double *partials) {
     hipLaunchKernelGGL(k_ipmb_newton_pre, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, D, B, mode, partials);
@@ -256,11 +333,30 @@ void ipmb_launch_newton_post(hipStream_t st, const IpmVecs &v, const IpmDir &D, 
     hipLaunchKernelGGL(k_ipmb_newton_post, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, D, Add, B, add, partials);
 }
 void ipmb_launch_advance(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials) {
-    hipLaunchKernelGGL(k_ipmb_advance, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, D, B, partials);
+    hipLaunchKernelGGL(k_ipmb_advance<false>, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, D, B, partials);
 }
 void ipmb_launch_take(hipStream_t st, double *dx, double *dy, const double *sx, const double *sy, const IpmBatch &B) {
     hipLaunchKernelGGL(k_ipmb_take, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, dx, dy, sx, sy, B);
 }
 void ipmb_launch_accept(hipStream_t st, const IpmDir &dst, const IpmDir &src, const IpmBatch &B) { hipLaunchKernelGGL(k_ipmb_accept, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, dst, src, B); }
+
+void mpcb_launch_fill(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD) {
+    hipLaunchKernelGGL(k_mpcb_fill, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, B, theta, regP, regD);
+}
+void mpcb_launch_start(hipStream_t st, const IpmVecs &v, const IpmBatch &B, int stage, double *partials) {
+    if (stage == 1) hipLaunchKernelGGL(k_mpcb_start1, dim3(B.tc.nblocks), dim3(IPM_T), 0, st, v, B, partials);
+    else if (stage == 2) hipLaunchKernelGGL(k_mpcb_start2, dim3(B.tc.nblocks), dim3(IPM_T), 0, st, v, B, partials);
+    else if (stage == 3) hipLaunchKernelGGL(k_mpcb_start3, dim3(B.tc.nblocks), dim3(IPM_T), 0, st, v, B, partials);
+    else hipLaunchKernelGGL(k_mpcb_start4, dim3(B.tc.nblocks), dim3(IPM_T), 0, st, v, B, partials);
+}
+void mpcb_launch_gap(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials) {
+    hipLaunchKernelGGL(k_mpcb_gap, dim3(B.tc.nblocks), dim3(IPM_T), 0, st, v, D, B, partials);
+}
+void mpcb_launch_targets(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials) {
+    hipLaunchKernelGGL(k_ipmb_targets<true>, dim3(B.tc.nblocks), dim3(IPM_T), 0, st, v, D, B, partials);
+}
+void mpcb_launch_advance(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials) {
+    hipLaunchKernelGGL(k_ipmb_advance<true>, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, D, B, partials);
+}
 
 }  // namespace tlpk

@@ -191,10 +191,7 @@ __global__ __launch_bounds__(IPM_T) void k_mpc_start1(IpmVecs v, double *__restr
     __shared__ double sh[IPM_T];
     double m0 = 0.0, m1 = 0.0;
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) {
-        if (v.lflag[j] != 0.0) m0 = fmin(m0, v.x[j] - v.lz[j]);
-        if (v.uflag[j] != 0.0) m1 = fmin(m1, v.uz[j] - v.x[j]);
-    }
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) mpc_start1_col(v, j, m0, m1);
     double r = blk_min(m0, sh); if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 0] = r;
     r = blk_min(m1, sh); if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 1] = r;
 }
@@ -203,18 +200,7 @@ __global__ __launch_bounds__(IPM_T) void k_mpc_start2(IpmVecs v, double dxs, dou
     __shared__ double sh[IPM_T];
     double m0 = 0.0, m1 = 0.0;
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) {
-        const double lf = v.lflag[j], uf = v.uflag[j], x = v.x[j];
-        v.xl[j] = (lf != 0.0) ? (x - v.lz[j]) + dxs : 0.0;
-        v.xu[j] = (uf != 0.0) ? (v.uz[j] - x) + dxs : 0.0;
-        double aty = 0.0;
-        if (v.aty) aty = v.aty[j];
-        else for (i64 p = v.Ap[j]; p < v.Ap[j + 1]; ++p) aty += v.Ax[p] * v.y[v.Ai[p]];
-        const double z = v.c[j] - aty, nb = lf + uf;
-        const double zl = (lf != 0.0) ? z / nb : 0.0, zu = (uf != 0.0) ? -z / nb : 0.0;
-        v.zl[j] = zl; v.zu[j] = zu;
-        m0 = fmin(m0, zl); m1 = fmin(m1, zu);
-    }
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) mpc_start2_col(v, j, dxs, m0, m1);
     double r = blk_min(m0, sh); if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 0] = r;
     r = blk_min(m1, sh); if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 1] = r;
 }
@@ -223,12 +209,7 @@ __global__ __launch_bounds__(IPM_T) void k_mpc_start3(IpmVecs v, double dzs, dou
     __shared__ double sh[IPM_T];
     double s0 = 0, s1 = 0, s2 = 0;
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) {
-        const double zl = (v.lflag[j] != 0.0) ? v.zl[j] + dzs : v.zl[j], zu = (v.uflag[j] != 0.0) ? v.zu[j] + dzs : v.zu[j];
-        v.zl[j] = zl; v.zu[j] = zu;
-        const double xl = v.xl[j], xu = v.xu[j];
-        s0 += xl * zl + xu * zu; s1 += zl + zu; s2 += xl + xu;
-    }
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) mpc_start3_col(v, j, dzs, s0, s1, s2);
     double *P = partials + (size_t)blockIdx.x * IPM_SLOTS;
     double r = blk_sum(s0, sh); if (threadIdx.x == 0) P[0] = r;
     r = blk_sum(s1, sh); if (threadIdx.x == 0) P[1] = r;
@@ -239,13 +220,7 @@ __global__ __launch_bounds__(IPM_T) void k_mpc_start4(IpmVecs v, double ddx, dou
     __shared__ double sh[IPM_T];
     double s0 = 0;
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) {
-        double xl = v.xl[j], xu = v.xu[j], zl = v.zl[j], zu = v.zu[j];
-        if (v.lflag[j] != 0.0) { xl += ddx; zl += ddz; }
-        if (v.uflag[j] != 0.0) { xu += ddx; zu += ddz; }
-        v.xl[j] = xl; v.xu[j] = xu; v.zl[j] = zl; v.zu[j] = zu;
-        s0 += xl * zl + xu * zu;
-    }
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) mpc_start4_col(v, j, ddx, ddz, s0);
     const double r = blk_sum(s0, sh);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.x * IPM_SLOTS + 0] = r;
 }
@@ -254,11 +229,7 @@ __global__ __launch_bounds__(IPM_T) void k_mpc_gap(IpmVecs v, IpmDir D, double a
     __shared__ double sh[IPM_T];
     double s0 = 0, s1 = 0;
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) {
-        const double xl = v.xl[j], xu = v.xu[j], zl = v.zl[j], zu = v.zu[j];
-        s0 += ((xl + ap * D.xl[j]) * v.lflag[j]) * (zl + ad * D.zl[j]) + ((xu + ap * D.xu[j]) * v.uflag[j]) * (zu + ad * D.zu[j]);
-        s1 += xl * zl + xu * zu;
-    }
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < v.n; j += stride) mpc_gap_col(v, D, j, ap, ad, s0, s1);
     double *P = partials + (size_t)blockIdx.x * IPM_SLOTS;
     double r = blk_sum(s0, sh); if (threadIdx.x == 0) P[0] = r;
     r = blk_sum(s1, sh); if (threadIdx.x == 0) P[1] = r;

@@ -129,4 +129,45 @@ __device__ __forceinline__ void ipm_advance_col(const IpmVecs &v, const IpmDir &
     s0 += xl * zl + xu * zu;
 }
 
+// ---- Mehrotra predictor-corrector: the starting point (MPC.jl:365-405) and the complementarity after a trial step (MPC/step.jl:246-258) ----
+// minima of (x - l) lflag and (u - x) uflag (entries without the bound contribute 0, as `false * Inf` does there)
+__device__ __forceinline__ void mpc_start1_col(const IpmVecs &v, i64 j, double &m0, double &m1) {
+    if (v.lflag[j] != 0.0) m0 = fmin(m0, v.x[j] - v.lz[j]);
+    if (v.uflag[j] != 0.0) m1 = fmin(m1, v.uz[j] - v.x[j]);
+}
+// xl, xu shifted by dxs; z = c - A'y split over the finite bounds; minima of zl, zu
+__device__ __forceinline__ void mpc_start2_col(const IpmVecs &v, i64 j, double dxs, double &m0, double &m1) {
+    const double lf = v.lflag[j], uf = v.uflag[j], x = v.x[j];
+    v.xl[j] = (lf != 0.0) ? (x - v.lz[j]) + dxs : 0.0;
+    v.xu[j] = (uf != 0.0) ? (v.uz[j] - x) + dxs : 0.0;
+    double aty = 0.0;
+    if (v.aty) aty = v.aty[j];
+    else for (i64 p = v.Ap[j]; p < v.Ap[j + 1]; ++p) aty += v.Ax[p] * v.y[v.Ai[p]];
+    const double z = v.c[j] - aty, nb = lf + uf;
+    const double zl = (lf != 0.0) ? z / nb : 0.0, zu = (uf != 0.0) ? -z / nb : 0.0;
+    v.zl[j] = zl; v.zu[j] = zu;
+    m0 = fmin(m0, zl); m1 = fmin(m1, zu);
+}
+// zl, zu shifted by dzs; sums {xl'zl + xu'zu, sum zl + sum zu, sum xl + sum xu}
+__device__ __forceinline__ void mpc_start3_col(const IpmVecs &v, i64 j, double dzs, double &s0, double &s1, double &s2) {
+    const double zl = (v.lflag[j] != 0.0) ? v.zl[j] + dzs : v.zl[j], zu = (v.uflag[j] != 0.0) ? v.zu[j] + dzs : v.zu[j];
+    v.zl[j] = zl; v.zu[j] = zu;
+    const double xl = v.xl[j], xu = v.xu[j];
+    s0 += xl * zl + xu * zu; s1 += zl + zu; s2 += xl + xu;
+}
+// balanced products: xl, xu += ddx, zl, zu += ddz on the finite bounds; sum xl'zl + xu'zu
+__device__ __forceinline__ void mpc_start4_col(const IpmVecs &v, i64 j, double ddx, double ddz, double &s0) {
+    double xl = v.xl[j], xu = v.xu[j], zl = v.zl[j], zu = v.zu[j];
+    if (v.lflag[j] != 0.0) { xl += ddx; zl += ddz; }
+    if (v.uflag[j] != 0.0) { xu += ddx; zu += ddz; }
+    v.xl[j] = xl; v.xu[j] = xu; v.zl[j] = zl; v.zu[j] = zu;
+    s0 += xl * zl + xu * zu;
+}
+// {((xl + ap dxl) lflag)'(zl + ad dzl) + ((xu + ap dxu) uflag)'(zu + ad dzu), xl'zl + xu'zu}
+__device__ __forceinline__ void mpc_gap_col(const IpmVecs &v, const IpmDir &D, i64 j, double ap, double ad, double &s0, double &s1) {
+    const double xl = v.xl[j], xu = v.xu[j], zl = v.zl[j], zu = v.zu[j];
+    s0 += ((xl + ap * D.xl[j]) * v.lflag[j]) * (zl + ad * D.zl[j]) + ((xu + ap * D.xu[j]) * v.uflag[j]) * (zu + ad * D.zu[j]);
+    s1 += xl * zl + xu * zu;
+}
+
 }  // namespace tlpk

@@ -1139,4 +1139,115 @@ int tlpk_ipm_batch_advance(tlpk_handle *h, const uint8_t *active, const double *
     return TLPK_OK;
 }
 
+/* ---- Mehrotra predictor-corrector on a stack of LPs (include/tlpk.h, "Batched device-resident MPC"; DESIGN.md section 4b'') -------------
+ * The tlpk_mpc_* calls with per-LP scalars and `active` masks.  tlpk_ipm_batch_residuals (tau[k] = 1), tlpk_ipm_batch_factor and
+ * tlpk_ipm_batch_accept are shared with the HSD batch as they are. */
+
+/* tlpk_mpc_start per LP, stage by stage (every LP is active): out[k] = xl'zl + xu'zu of LP k's starting point */
+int tlpk_mpc_batch_start(tlpk_handle *h, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!out) { h->last_error = "tlpk_mpc_batch_start: a NULL pointer"; return TLPK_BADARG; }
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm; const i64 nlp = bs.nlp;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, nullptr, [](i64, int) { return 0.0; })) return rc;
+    mpcb_launch_fill(h->stream, s.v, bs.B, h->d_theta, h->d_regP, h->d_regD);
+    int rc = tlpk_update_device(h, h->d_theta, h->d_regP, h->d_regD);
+    if (rc != TLPK_OK) return rc;
+    if ((rc = tlpk_solve_device(h, s.D[0].x, s.v.y, s.v.xip, s.v.c)) != TLPK_OK) return rc;      // y  (xip == 0 here)
+    if ((rc = tlpk_solve_device(h, s.v.x, s.D[0].y, s.v.b, s.v.xid)) != TLPK_OK) return rc;      // x  (xid == 0 here)
+    const double *q = bs.h_out;
+    // one stage: the scalars sc(k, slot) of every LP, the kernel, the per-LP reductions
+    auto stage = [&](int st, auto &&sc, int nsum, int nmin) -> int {
+        if (st > 1) if (int r = batch_scalars(h, bs, nullptr, sc)) return r;
+        mpcb_launch_start(h->stream, s.v, bs.B, st, bs.partials[0]);
+        ipmb_launch_finalize(h->stream, bs.B, bs.B.tc, nsum, 0, nmin, bs.partials[0], bs.d_out);
+        return batch_gather(h, bs, 1);
+    };
+    std::vector<double> a((size_t)nlp), b((size_t)nlp);
+    if ((rc = stage(1, [](i64, int) { return 0.0; }, 0, 2)) != TLPK_OK) return rc;
+    if ((rc = tlpk_sync(h)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) { const double *r = q + (size_t)k * IPM_SLOTS; a[(size_t)k] = 1.0 + std::fmax(0.0, std::fmax(-1.5 * r[0], -1.5 * r[1])); }      // dxs
+    if ((rc = stage(2, [&](i64 k, int slot) { return slot == 0 ? a[(size_t)k] : 0.0; }, 0, 2)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) { const double *r = q + (size_t)k * IPM_SLOTS; a[(size_t)k] = 1.0 + std::fmax(0.0, std::fmax(-1.5 * r[0], -1.5 * r[1])); }      // dzs
+    if ((rc = stage(3, [&](i64 k, int slot) { return slot == 0 ? a[(size_t)k] : 0.0; }, 3, 0)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) {
+        const double *r = q + (size_t)k * IPM_SLOTS;
+        const double mu = r[0];
+        a[(size_t)k] = mu / (2.0 * r[1]); b[(size_t)k] = mu / (2.0 * r[2]);      // ddx, ddz
+    }
+    if ((rc = stage(4, [&](i64 k, int slot) { return slot == 0 ? a[(size_t)k] : (slot == 1 ? b[(size_t)k] : 0.0); }, 1, 0)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) out[k] = q[(size_t)k * IPM_SLOTS];
+    s.cur = 0;
+    return TLPK_OK;
+}
+
+/* tlpk_mpc_newton per LP (one mode for the call): gmu[k]; out[2 k ..] = { primal, dual step to the boundary }; inactive LPs: out = 0 */
+int tlpk_mpc_batch_newton(tlpk_handle *h, int mode, const uint8_t *active, const double *gmu, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!active || !gmu || !out) { h->last_error = "tlpk_mpc_batch_newton: a NULL pointer"; return TLPK_BADARG; }
+    if (mode < 0 || mode > 2) { h->last_error = "tlpk_mpc_batch_newton: mode must be 0, 1 or 2"; return TLPK_BADARG; }
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm; const i64 nlp = bs.nlp;
+    const IpmDir &acc = s.D[s.cur];
+    const IpmDir &dst = (mode == 2) ? s.D[1 - s.cur] : s.D[s.cur];
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q == 0 ? 1.0 : (q == 1 ? gmu[k] : 0.0); })) return rc;      // eta = 1, gamma mu, delta = 0
+    ipmb_launch_newton_pre(h->stream, s.v, acc, bs.B, mode, bs.partials[0]);
+    int rc = tlpk_solve_device(h, bs.sx[0], bs.sy[0], s.v.xip, s.v.xid);
+    if (rc != TLPK_OK) return rc;
+    ipmb_launch_take(h->stream, dst.x, dst.y, bs.sx[0], bs.sy[0], bs.B);        // an inactive LP keeps its direction
+    if ((rc = tlpk_sync(h)) != TLPK_OK) return rc;                              // the kernels above have read this call's first scalars
+    if ((rc = batch_scalars(h, bs, active, [](i64, int) { return 0.0; })) != TLPK_OK) return rc;      // dtau = 0: hx, hy (zeros) unused
+    ipmb_launch_newton_post(h->stream, s.v, dst, acc, bs.B, mode == 2 ? 1 : 0, bs.partials[1]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 0, 0, 2, bs.partials[1], bs.d_out);
+    if ((rc = batch_gather(h, bs, 1)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) { const double *q = bs.h_out + (size_t)k * IPM_SLOTS; out[2 * k] = q[0]; out[2 * k + 1] = q[1]; }
+    return TLPK_OK;
+}
+
+/* tlpk_mpc_gap per LP: out[2 k ..] = { complementarity of LP k moved by (ap[k], ad[k]) along its accepted direction, at the point itself } */
+int tlpk_mpc_batch_gap(tlpk_handle *h, const uint8_t *active, const double *ap, const double *ad, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!active || !ap || !ad || !out) { h->last_error = "tlpk_mpc_batch_gap: a NULL pointer"; return TLPK_BADARG; }
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q == 0 ? ap[k] : (q == 1 ? ad[k] : 0.0); })) return rc;
+    mpcb_launch_gap(h->stream, s.v, s.D[s.cur], bs.B, bs.partials[0]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tc, 2, 0, 0, bs.partials[0], bs.d_out);
+    if (int rc = batch_gather(h, bs, 1)) return rc;
+    for (i64 k = 0; k < bs.nlp; ++k) { const double *q = bs.h_out + (size_t)k * IPM_SLOTS; out[2 * k] = q[0]; out[2 * k + 1] = q[1]; }
+    return TLPK_OK;
+}
+
+/* tlpk_mpc_targets per LP: par[4 k ..] = { ap_, ad_, tmin, tmax }; the targets stay on the device for tlpk_mpc_batch_newton(mode 2) */
+int tlpk_mpc_batch_targets(tlpk_handle *h, const uint8_t *active, const double *par) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!active || !par) { h->last_error = "tlpk_mpc_batch_targets: a NULL pointer"; return TLPK_BADARG; }
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q < 4 ? par[4 * k + q] : 0.0; })) return rc;
+    mpcb_launch_targets(h->stream, s.v, s.D[s.cur], bs.B, bs.partials[0]);
+    HIPCHK(h, hipStreamSynchronize(h->stream));                      // the next call rewrites the pinned scalars
+    HIPCHK(h, hipGetLastError());
+    return TLPK_OK;
+}
+
+/* tlpk_mpc_advance per LP: primal side += ap[k] D_k, dual side += ad[k] D_k; out[k] = xl'zl + xu'zu of the new point (0 for an inactive LP) */
+int tlpk_mpc_batch_advance(tlpk_handle *h, const uint8_t *active, const double *ap, const double *ad, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;
+    if (!active || !ap || !ad || !out) { h->last_error = "tlpk_mpc_batch_advance: a NULL pointer"; return TLPK_BADARG; }
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q == 0 ? ap[k] : (q == 1 ? ad[k] : 0.0); })) return rc;
+    mpcb_launch_advance(h->stream, s.v, s.D[s.cur], bs.B, bs.partials[0]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 1, 0, 0, bs.partials[0], bs.d_out);
+    if (int rc = batch_gather(h, bs, 1)) return rc;
+    for (i64 k = 0; k < bs.nlp; ++k) out[k] = bs.h_out[(size_t)k * IPM_SLOTS];
+    return TLPK_OK;
+}
+
 }  // extern "C"

@@ -77,5 +77,12 @@ void ipmb_launch_newton_post(hipStream_t st, const IpmVecs &v, const IpmDir &D, 
 void ipmb_launch_advance(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
 void ipmb_launch_accept(hipStream_t st, const IpmDir &dst, const IpmDir &src, const IpmBatch &B);
 void ipmb_launch_take(hipStream_t st, double *dx, double *dy, const double *sx, const double *sy, const IpmBatch &B);
+// Mehrotra on a stack: fill / start stages 1 .. 4 / gap as mpc_launch_*; targets and advance with separate primal and dual lengths
+// (B.sc of the call: start2 dxs | start3 dzs | start4 ddx, ddz | gap ap, ad | targets ap_, ad_, tmin, tmax | advance ap, ad)
+void mpcb_launch_fill(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD);
+void mpcb_launch_start(hipStream_t st, const IpmVecs &v, const IpmBatch &B, int stage, double *partials);
+void mpcb_launch_gap(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
+void mpcb_launch_targets(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
+void mpcb_launch_advance(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
 
 }  // namespace tlpk

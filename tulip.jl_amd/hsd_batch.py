@@ -219,11 +219,22 @@ class BatchedDeviceHSD:
     # step.jl:10-151 for the LPs of `act`; an LP that runs into the three-bump rule gets Trm_NumericalProblem and is parked
     def compute_step(self, act):
         o = self._o
-        B = self.nlp
         step = act.copy()
         self._set(self.regP, step, np.maximum(o["PRegMin"], self.regP / 10))
         self._set(self.regD, step, np.maximum(o["DRegMin"], self.regD / 10))
         self._set(self.regG, step, np.maximum(o["PRegMin"], self.regG / 10))
+        step = self._factor(step)
+        if not step.any():
+            return step
+        with np.errstate(all="ignore"):
+            return self._direction_and_move(step)
+
+    _bumped = ("regD", "regP", "regG")                                       # what a failed update multiplies by 100
+
+    def _factor(self, step):
+        """The per-LP retry loop of the update (step.jl:35-51) for the LPs of `step`; returns the LPs that hold a factor."""
+        B = self.nlp
+        step = step.copy()
         nbump = np.zeros(B, dtype=np.int64)
         fail = C.c_int64(-1)
         while step.any():                                                    # step.jl:35-51, per LP
@@ -240,17 +251,15 @@ class BatchedDeviceHSD:
                 bad[k] = True                                                # the update reports one failure at a time
             else:
                 bad[:] = step                                                # the pivot cannot be attributed: every LP of the update retries
-            self.regD[bad] *= 100; self.regP[bad] *= 100; self.regG[bad] *= 100
+            for name in self._bumped:
+                getattr(self, name)[bad] *= 100
             nbump[bad] += 1
             self.timers["n_bump"][bad] += 1
             gone = bad & ~(nbump < 3)                                        # step.jl:51 (the reference's off-by-one is kept)
             self.status[gone] = "Trm_NumericalProblem"
             step &= ~gone
         self.timers["max_bumps_in_a_step"] = np.maximum(self.timers["max_bumps_in_a_step"], nbump)
-        if not step.any():
-            return step
-        with np.errstate(all="ignore"):
-            return self._direction_and_move(step)
+        return step
 
     def _direction_and_move(self, step):
         o, B = self._o, self.nlp

@@ -119,13 +119,20 @@ class Model:
 
     @classmethod
     def optimize_batch(cls, models, **kw):
-        """`optimize()` of many models in one set of launches (hsd_batch.BatchedDeviceHSD): each model is presolved and brought to standard
-        form on its own, ONE batched homogeneous self-dual run solves the LPs presolve did not already finish, each is postsolved, and every
-        model ends as after its own `optimize()`.  kw: the backend's keywords (system=, device=, ...; default: those of the first model)."""
-        from .hsd_batch import BatchedDeviceHSD
+        """`optimize()` of many models in one set of launches (hsd_batch.BatchedDeviceHSD, or mpc_batch.BatchedDeviceMPC where every model
+        has algorithm="mpc"): each model is presolved and brought to standard form on its own, ONE batched interior-point run solves the LPs
+        presolve did not already finish, each is postsolved, and every model ends as after its own `optimize()`.
+        kw: the backend's keywords (system=, device=, ...; default: those of the first model)."""
         models = list(models)
-        if any(mdl.algorithm != "hsd" for mdl in models):
-            raise ValueError("optimize_batch runs the homogeneous self-dual loop: every model must have algorithm='hsd'")
+        algorithms = {mdl.algorithm for mdl in models}
+        if len(algorithms) > 1:
+            raise ValueError(f"optimize_batch runs ONE interior-point loop for the whole batch: the models mix the algorithms {sorted(algorithms)}")
+        if not algorithms <= {"hsd", "mpc"}:
+            raise ValueError("optimize_batch runs the homogeneous self-dual loop or Mehrotra's: every model must have algorithm='hsd', or every model algorithm='mpc'")
+        if algorithms == {"mpc"}:
+            from .mpc_batch import BatchedDeviceMPC as Batched
+        else:
+            from .hsd_batch import BatchedDeviceHSD as Batched
         pending = []
         for mdl in models:
             lp_inner = mdl.lp
@@ -139,7 +146,7 @@ class Model:
                 lp_inner = ps.reduced_problem()
             pending.append((mdl, lp_inner))
         if pending:
-            opt = BatchedDeviceHSD([standard_form(lp) for _, lp in pending], **(kw or models[0].backend_kw)).optimize()
+            opt = Batched([standard_form(lp) for _, lp in pending], **(kw or models[0].backend_kw)).optimize()
             for k, (mdl, lp_inner) in enumerate(pending):
                 res = mdl.inner = InnerResult(str(opt.status[k]), str(opt.primal_status[k]), str(opt.dual_status[k]), opt._get(k, 0), opt._get(k, 5),
                                               opt._get(k, 3), opt._get(k, 4), float(opt.tau[k]), float(opt.primal_objective[k]),
