@@ -464,6 +464,30 @@ int tlpk_ipm_batch_targets(tlpk_handle *h, const uint8_t *active, const double *
 int tlpk_ipm_batch_accept(tlpk_handle *h, const uint8_t *active);
 int tlpk_ipm_batch_advance(tlpk_handle *h, const uint8_t *active, const double *alpha /*nlp*/, double *out /*nlp*/);
 
+/* ---------------------------------------------------------------------------------------------
+ * Refilling slots: a batch that keeps going.  A batch-loaded handle has nlp SLOTS; when the LP of a slot is decided, the next LP of the
+ * caller's queue with the same pattern takes the slot while every other slot continues, so N LPs stream through one analysed handle
+ * (tulip.jl_amd/hsd_batch.py: BatchedDeviceHSD.optimize_stream).
+ *   tlpk_ipm_batch_refill replaces the LPs of the slots with slots[k] != 0: tlpk_set_values + tlpk_ipm_reload restricted to those LPs.
+ *   nzval (nnzA, the STACKED matrix in the caller's CSC order) or NULL = keep A; b (m), c, l, u (n) stacked, each may be NULL = keep.  Only
+ *   the selected LPs' segments of the arrays are read, and only those reach the device.  For the selected LPs it rewrites the values of
+ *   their columns of A and everything derived from them (the products of the assembly lists, the value arrays of every copy of A the handle
+ *   keeps; K2: the incidence copy and the copies the loops keep), their segments of b, c, l, u, their finite-bound flags (bounds may change
+ *   between finite and infinite) and their iterate, which becomes the HSD starting point of tlpk_ipm_reset.  Their parts of the handle then
+ *   equal, bit for bit, those of a handle created and batch-loaded on the stacked data with these LPs in place.  An LP that is not
+ *   selected keeps every bit: its segment of every vector tlpk_ipm_get reads, its columns' values, its derived arrays.  With new values
+ *   the handle is analysed but not factored afterwards, as after tlpk_set_values: the next tlpk_ipm_batch_factor factorises.
+ *   Checks, in this order (TLPK_BADARG): h NULL; not batch-loaded (the "load first" sentence of the tlpk_ipm_batch_* calls); slots NULL;
+ *   nzval given with len != nnzA; the handle is stale after a whole-handle tlpk_set_values* without tlpk_ipm_reload.  A failed check leaves
+ *   the handle as it was; no slot selected: TLPK_OK and nothing happens.  K1 and K2; refine_steps and row_block are fine, as at load.
+ *   The Mehrotra batch has no refill (its starting point needs a factorisation and two solves per LP).
+ *   tlpk_ipm_get_lp is tlpk_ipm_get for ONE LP of a batch-loaded handle: LP k's segment of vector `what` (the codes of tlpk_ipm_get), len =
+ *   that segment's length.  Refusals as tlpk_ipm_get, plus TLPK_BADARG on a handle that is not batch-loaded, k out of range, a wrong len.
+ * --------------------------------------------------------------------------------------------- */
+int tlpk_ipm_batch_refill(tlpk_handle *h, const uint8_t *slots /*nlp*/, const double *nzval, int64_t len,
+                          const double *b, const double *c, const double *l, const double *u);
+int tlpk_ipm_get_lp(tlpk_handle *h, int what, int64_t k, double *host, int64_t len);
+
 /* ---- Mehrotra predictor-corrector with the iterate in HBM (/root/reference/src/IPM/MPC/MPC.jl:218-410,
  * MPC/step.jl:10-358).  Same vectors as above: tlpk_ipm_load once, tlpk_ipm_residuals with tau = 1 (MPC.jl:101-141),
  * tlpk_ipm_factor (step.jl:24-51), tlpk_ipm_accept and tlpk_ipm_get are shared. */

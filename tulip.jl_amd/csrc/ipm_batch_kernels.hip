@@ -61,6 +61,16 @@ __global__ __launch_bounds__(64 * IPM_SLOTS) void k_ipmb_finalize(IpmBatch B, Ip
     if (lane == 0) o[k] = r;
 }
 
+// tlpk_ipm_batch_refill: the starting point of k_ipm_init for the LPs whose flag is set (the slots that take a new LP); a workgroup of any
+// other LP returns before it touches anything
+__global__ void k_ipmb_init(IpmVecs v, IpmBatch B) {
+    const Seg g = seg_of(B, B.tb);
+    if (!g.active) return;
+    const i64 stride = (i64)g.nbk * blockDim.x, t0 = (i64)g.lb * blockDim.x + threadIdx.x;
+    for (i64 jj = t0; jj < g.nk; jj += stride) ipm_init_col(v, g.c0 + jj);
+    for (i64 ii = t0; ii < g.mk; ii += stride) v.y[g.r0 + ii] = 0.0;
+}
+
 // sc[0] = tau
 __global__ __launch_bounds__(IPM_T) void k_ipmb_res_cols(IpmVecs v, IpmBatch B, double *__restrict__ partials) {
     __shared__ double sh[IPM_T];
@@ -313,6 +323,7 @@ __global__ __launch_bounds__(IPM_T) void k_mpcb_gap(IpmVecs v, IpmDir D, IpmBatc
 void ipmb_launch_finalize(hipStream_t st, const IpmBatch &B, const IpmBlockTab &t, int nsum, int nmax, int nmin, const double *partials, double *out) {
     hipLaunchKernelGGL(k_ipmb_finalize, dim3((unsigned)B.nlp), dim3(64 * (nsum + nmax + nmin)), 0, st, B, t, nsum, nmax, nmin, partials, out);
 }
+void ipmb_launch_init(hipStream_t st, const IpmVecs &v, const IpmBatch &B) { hipLaunchKernelGGL(k_ipmb_init, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, B); }
 void ipmb_launch_res_cols(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *partials) { hipLaunchKernelGGL(k_ipmb_res_cols, dim3(B.tc.nblocks), dim3(IPM_T), 0, st, v, B, partials); }
 void ipmb_launch_res_rows(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *partials) { hipLaunchKernelGGL(k_ipmb_res_rows, dim3(B.tr.nblocks), dim3(IPM_T), 0, st, v, B, partials); }
 void ipmb_launch_theta(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD) {

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(64 * IPM_SLOTS) void k_ipm_finalize(int nblocks, in
 
 __global__ void k_ipm_init(IpmVecs v) {                                     // HSD.jl:238-247
     const i64 stride = (i64)gridDim.x * blockDim.x, t0 = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    for (i64 j = t0; j < v.n; j += stride) { v.x[j] = 0.0; v.xl[j] = v.lflag[j]; v.xu[j] = v.uflag[j]; v.zl[j] = v.lflag[j]; v.zu[j] = v.uflag[j]; }
+    for (i64 j = t0; j < v.n; j += stride) ipm_init_col(v, j);
     for (i64 i = t0; i < v.m; i += stride) v.y[i] = 0.0;
 }
 

@@ -43,6 +43,8 @@ __device__ __forceinline__ double blk_min(double v, double *sh) {
 }
 
 // ---- per-entry bodies (citations into the reference: at the kernels of ipm_kernels.hip) ----
+// column j of the starting point
+__device__ __forceinline__ void ipm_init_col(const IpmVecs &v, i64 j) { v.x[j] = 0.0; v.xl[j] = v.lflag[j]; v.xu[j] = v.uflag[j]; v.zl[j] = v.lflag[j]; v.zu[j] = v.uflag[j]; }
 // column j of the residuals: rl, ru, rd + sums {c'x, lz'zl, uz'zu, xl'zl + xu'zu} + maxima {|rl|, |ru|, |rd|, |(x-xl) lflag|, |(x+xu) uflag|, |A'y + zl - zu|}
 __device__ __forceinline__ void ipm_res_col(const IpmVecs &v, i64 j, double tau, double &s0, double &s1, double &s2, double &s3,
                                             double &m0, double &m1, double &m2, double &m3, double &m4, double &m5) {

@@ -70,6 +70,32 @@ __global__ __launch_bounds__(RF_THREADS) void k_refresh_dense(i64 m, i64 n, cons
     for (i64 j = c; j < n; j += gridDim.y) dA[j * dlda + r] = (r < m) ? A[j * lda + r] : 0.0;
 }
 
+// ---- selected slots of a stack of LPs (tlpk_ipm_batch_refill) ----
+// The stacked matrix is block diagonal, so both factors of a product and the source of a copied entry belong to ONE LP: lp_of[p] is the LP
+// that owns entry p of the caller's nzval, flag[k * stride] != 0 selects LP k.  A thread rewrites its element only where that LP is
+// selected -- formed exactly as the passes above form it -- and leaves it alone otherwise; the constants (a unit entry, the -1 of a
+// diagonal) depend on no value and are never rewritten.  One writer per element, no atomics; only the selected LPs' ranges of nz are read.
+__device__ __forceinline__ bool rf_selected(const i32 *__restrict__ lp_of, const double *__restrict__ flag, int stride, i32 p) {
+    return p >= 0 && flag[(size_t)lp_of[p] * stride] != 0.0;
+}
+__global__ __launch_bounds__(RF_THREADS) void k_refresh_pairs_sel(i64 np, const i32 *__restrict__ a, const i32 *__restrict__ b, const double *__restrict__ nz,
+                                                                  double *__restrict__ w, const i32 *__restrict__ lp_of, const double *__restrict__ flag, int stride) {
+    const i64 t0 = ((i64)blockIdx.x * RF_THREADS + threadIdx.x) * RF_PER;
+    for (i64 t = t0; t < min(np, t0 + RF_PER); ++t) {
+        const i32 pa = a[t], pb = b[t];
+        if (!rf_selected(lp_of, flag, stride, pa >= 0 ? pa : pb)) continue;
+        w[t] = rf_value(nz, pa, nz[max(pa, 0)]) * rf_value(nz, pb, nz[max(pb, 0)]);
+    }
+}
+__global__ __launch_bounds__(RF_THREADS) void k_refresh_gather_sel(i64 n, const i32 *__restrict__ src, const double *__restrict__ nz, double *__restrict__ out,
+                                                                   const i32 *__restrict__ lp_of, const double *__restrict__ flag, int stride) {
+    const i64 q0 = ((i64)blockIdx.x * RF_THREADS + threadIdx.x) * RF_PER;
+    for (i64 q = q0; q < min(n, q0 + RF_PER); ++q) {
+        const i32 p = src[q];
+        if (rf_selected(lp_of, flag, stride, p)) out[q] = nz[p];
+    }
+}
+
 inline unsigned rf_blocks(i64 n) { return (unsigned)((n + (i64)RF_THREADS * RF_PER - 1) / ((i64)RF_THREADS * RF_PER)); }
 
 }  // namespace
@@ -79,6 +105,12 @@ void launch_refresh_pairs(hipStream_t st, i64 np, const i32 *a, const i32 *b, co
 }
 void launch_refresh_gather(hipStream_t st, i64 n, const i32 *src, const double *nz, double *out) {
     if (n > 0) hipLaunchKernelGGL(k_refresh_gather, dim3(rf_blocks(n)), dim3(RF_THREADS), 0, st, n, src, nz, out);
+}
+void launch_refresh_pairs_sel(hipStream_t st, i64 np, const i32 *a, const i32 *b, const double *nz, double *w, const i32 *lp_of, const double *flag, int stride) {
+    if (np > 0) hipLaunchKernelGGL(k_refresh_pairs_sel, dim3(rf_blocks(np)), dim3(RF_THREADS), 0, st, np, a, b, nz, w, lp_of, flag, stride);
+}
+void launch_refresh_gather_sel(hipStream_t st, i64 n, const i32 *src, const double *nz, double *out, const i32 *lp_of, const double *flag, int stride) {
+    if (n > 0) hipLaunchKernelGGL(k_refresh_gather_sel, dim3(rf_blocks(n)), dim3(RF_THREADS), 0, st, n, src, nz, out, lp_of, flag, stride);
 }
 void launch_refresh_dense(hipStream_t st, i64 m, i64 n, const double *A, i64 lda, double *dA, i64 dlda) {
     if (m <= 0 || n <= 0) return;

@@ -2529,6 +2529,27 @@ extern "C++" int sync_host_values(tlpk_handle *h) {
     return TLPK_OK;
 }
 
+// tlpk_ipm_batch_refill (tlpk_ipm.cpp): new values for the LPs of a stack whose flag is set.  ranges = (lo, hi) pairs: the selected LPs' entries of the
+// caller's nzval -- only those reach the device.  Enqueued on the handle's stream; the caller waits.  Afterwards analysed, not factored, as after tlpk_set_values.
+extern "C++" int set_values_slots(tlpk_handle *h, const double *nzval, const std::vector<i64> &ranges, const i32 *d_lp_of, const double *d_flag, int stride) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = ensure_value_maps(h)) return rc;
+    values_reset_state(h);
+    const Symbolic &S = h->S;
+    hipStream_t st = h->stream;
+    for (size_t r = 0; r + 1 < ranges.size(); r += 2) {
+        const i64 lo = ranges[r], hi = ranges[r + 1];
+        if (hi > lo) HIPCHK(h, hipMemcpyAsync(h->d_nz + lo, nzval + lo, (size_t)(hi - lo) * 8, hipMemcpyHostToDevice, st));
+    }
+    if (S.system == 1) launch_refresh_gather_sel(st, (i64)S.Ax.size(), h->d_ax_src, h->d_nz, h->d.Ax, d_lp_of, d_flag, stride);
+    launch_refresh_gather_sel(st, (i64)S.Tpos.size(), h->d_tx_src, h->d_nz, h->d.Tx, d_lp_of, d_flag, stride);
+    if (h->d.Px) launch_refresh_gather_sel(st, h->n_px_src, h->d_px_src, h->d_nz, h->d.Px, d_lp_of, d_flag, stride);
+    launch_refresh_pairs_sel(st, S.pair_ptr.empty() ? 0 : S.pair_ptr.back(), h->d_pair_a, h->d_pair_b, h->d_nz, h->d.pair_w, d_lp_of, d_flag, stride);
+    HIPCHK(h, hipGetLastError());
+    h->host_ax_stale = true;            // S.Ax is copied back when a host consumer asks
+    return TLPK_OK;
+}
+
 int tlpk_set_values(tlpk_handle *h, const double *nzval, int64_t len) { return set_values_common(h, nzval, len, false, "tlpk_set_values"); }
 int tlpk_set_values_device(tlpk_handle *h, const double *d_nzval, int64_t len) { return set_values_common(h, d_nzval, len, true, "tlpk_set_values_device"); }
 

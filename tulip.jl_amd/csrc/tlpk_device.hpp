@@ -231,5 +231,9 @@ int launch_tc_iter(hipStream_t st, const DevArrays &a, const TcArrays &c, i64 k)
 void launch_refresh_pairs(hipStream_t st, i64 np, const i32 *a, const i32 *b, const double *nz, double *w);
 void launch_refresh_gather(hipStream_t st, i64 n, const i32 *src, const double *nz, double *out);
 void launch_refresh_dense(hipStream_t st, i64 m, i64 n, const double *A, i64 lda, double *dA, i64 dlda);
+// ... for the selected LPs of a stack (tlpk_ipm_batch_refill): lp_of[p] = the LP that owns entry p of nz, flag[k * stride] != 0 selects LP k; an element whose
+// LP is not selected is left alone
+void launch_refresh_pairs_sel(hipStream_t st, i64 np, const i32 *a, const i32 *b, const double *nz, double *w, const i32 *lp_of, const double *flag, int stride);
+void launch_refresh_gather_sel(hipStream_t st, i64 n, const i32 *src, const double *nz, double *out, const i32 *lp_of, const double *flag, int stride);
 
 }  // namespace tlpk

@@ -115,6 +115,9 @@ struct tlpk_handle {
 
 void ipm_free(tlpk_handle *h);          // tlpk_ipm.cpp
 int sync_host_values(tlpk_handle *h);   // tlpk_api.cpp: S.Ax <- the device copy after a tlpk_set_values*_device
+// tlpk_api.cpp, for tlpk_ipm_batch_refill: the refresh of tlpk_set_values restricted to the LPs of a stack whose flag is set (d_flag[k * stride] != 0; d_lp_of: the LP of
+// every entry of nzval; ranges: (lo, hi) pairs, the entries of nzval that are read).  Enqueued on the handle's stream.
+int set_values_slots(tlpk_handle *h, const double *nzval, const std::vector<i64> &ranges, const i32 *d_lp_of, const double *d_flag, int stride);
 // tlpk_api.cpp, for the device-resident interior-point loops on a multi-device handle: KKT.update! from the theta / regP / regD every
 // shard holds on its device, and KKT.solve! with shard-resident vectors in the rank-local layout (every shard adds ITS xi_p on the
 // linking rows -- partial residuals --, the library's reduction completes them; nothing is gathered)

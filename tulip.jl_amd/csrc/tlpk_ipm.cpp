@@ -42,6 +42,11 @@ struct IpmBatchState {
     double *d_out = nullptr, *h_out = nullptr;    // 2 x nlp x IPM_SLOTS finalised scalars (device / pinned)
     double *d_sc = nullptr, *h_sc = nullptr;      // nlp x IPM_BSC scalars of the current call (device / pinned)
     double *sx[2] = {nullptr, nullptr}, *sy[2] = {nullptr, nullptr};      // what the solves write (n, m; two right-hand sides): the active LPs take their segments from here
+    // tlpk_ipm_batch_refill, built by its first call that brings new values: the LPs' contiguous ranges of the caller's nzval, the LP of every entry of it and -- K2,
+    // whose loops keep their own copies of A -- for every entry of the row-major copy the position in nzval it copies
+    bool refill_maps = false;
+    std::vector<i64> nz_off;
+    i32 *d_lp_of = nullptr, *d_ktx_src = nullptr;
 };
 
 // ---- one device or several ---------------------------------------------------------------------------------------------------
@@ -658,6 +663,18 @@ static int advance_all(tlpk_handle *h, double ap, double ad, double *out) {
 }
 int tlpk_ipm_advance(tlpk_handle *h, double alpha, double *out) { return advance_all(h, alpha, alpha, out); }
 
+// the device vector behind every code of tlpk_ipm_get on handle c, and whether a code names a vector of length m
+static void ipm_get_sources(const tlpk_handle *c, const double *src[36]) {
+    const IpmState &s = *c->ipm; const IpmVecs &v = s.v;
+    const IpmDir &acc = s.D[s.cur], &cand = s.D[1 - s.cur];
+    const double *all[36] = {v.x, v.xl, v.xu, v.zl, v.zu, v.y,
+                             acc.x, acc.xl, acc.xu, acc.zl, acc.zu, acc.y, cand.x, cand.xl, cand.xu, cand.zl, cand.zu, cand.y,
+                             v.rp, v.rl, v.ru, v.rd, v.thl, v.thu, v.hx, v.hy, v.hxid, v.xil, v.xiu, v.xzl, v.xzu, v.xid, v.xip,
+                             c->d_theta, c->d_regP, c->d_regD};
+    std::copy(all, all + 36, src);
+}
+static bool ipm_get_is_row(int what) { return what == 5 || what == 11 || what == 17 || what == 18 || what == 25 || what == 32 || what == 35; }
+
 /* download one device vector, read-only (nothing here writes device state):
  *   0-5    the iterate x, xl, xu, zl, zu (n), y (m)
  *   6-11   the accepted direction, same order (D[cur]);  12-17  the candidate direction (D[1 - cur])
@@ -670,18 +687,14 @@ int tlpk_ipm_get(tlpk_handle *h, int what, double *host, int64_t len) {
     if (!host || what < 0 || what > 35) return TLPK_BADARG;
     if (sh.multi && what > 5) { h->last_error = "tlpk_ipm_get: the codes 6 .. 35 (directions, residuals, right-hand sides, theta) need a single-device handle"; return TLPK_BADARG; }
     const IpmVecs &v0 = sh.c[0]->ipm->v;
-    const bool rows = what == 5 || what == 11 || what == 17 || what == 18 || what == 25 || what == 32 || what == 35;
-    const int64_t need = rows ? v0.m : v0.n;
+    const int64_t need = ipm_get_is_row(what) ? v0.m : v0.n;
     if (len != need) { h->last_error = "tlpk_ipm_get: wrong length"; return TLPK_BADARG; }
     std::vector<double> tmp;
     if (sh.multi) tmp.resize((size_t)std::max<int64_t>(need, 1));
     for (int r = 0; r < sh.n; ++r) {
-        tlpk_handle *c = sh.c[r]; const IpmState &s = *c->ipm; const IpmVecs &v = s.v;
-        const IpmDir &acc = s.D[s.cur], &cand = s.D[1 - s.cur];
-        const double *src[36] = {v.x, v.xl, v.xu, v.zl, v.zu, v.y,
-                                 acc.x, acc.xl, acc.xu, acc.zl, acc.zu, acc.y, cand.x, cand.xl, cand.xu, cand.zl, cand.zu, cand.y,
-                                 v.rp, v.rl, v.ru, v.rd, v.thl, v.thu, v.hx, v.hy, v.hxid, v.xil, v.xiu, v.xzl, v.xzu, v.xid, v.xip,
-                                 c->d_theta, c->d_regP, c->d_regD};
+        tlpk_handle *c = sh.c[r];
+        const double *src[36];
+        ipm_get_sources(c, src);
         HIPCHK(h, hipSetDevice(c->device));
         HIPCHK(h, hipStreamSynchronize(c->stream));
         if (need <= 0) continue;
@@ -1136,6 +1149,141 @@ int tlpk_ipm_batch_advance(tlpk_handle *h, const uint8_t *active, const double *
     ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 1, 0, 0, bs.partials[0], bs.d_out);
     if (int rc = batch_gather(h, bs, 1)) return rc;
     for (i64 k = 0; k < bs.nlp; ++k) out[k] = bs.h_out[(size_t)k * IPM_SLOTS];
+    return TLPK_OK;
+}
+
+/* ---- a batch that keeps going (include/tlpk.h, "Refilling slots"; DESIGN.md section 4b'-r) -------------------------------------------------
+ * tlpk_ipm_batch_refill gives the slots with slots[k] != 0 a new LP on the analysed pattern: tlpk_set_values + tlpk_ipm_reload restricted to those
+ * LPs.  Every other LP keeps every bit of its state.  tlpk_ipm_get_lp reads one LP's segment of a vector (the result of an LP that leaves). */
+}  // extern "C"
+
+namespace {
+
+// first refill with new values: where every LP's entries sit in the caller's nzval.  The stacked matrix is block diagonal in the caller's column-major order, so LP k owns
+// the contiguous range [nz_off[k], nz_off[k + 1]); that is verified here, entry by entry.  K2: the map of the loops' row-major copy of A (ipm_sub_matrix's order).
+int refill_maps(tlpk_handle *h, IpmBatchState &bs) {
+    if (bs.refill_maps) return TLPK_OK;
+    if (int rc = sync_host_values(h)) return rc;
+    const Symbolic &S = h->S;
+    const bool k2 = S.system == 1;
+    const i64 nnz = k2 ? S.n : S.nnzA, nlp = bs.nlp;
+    std::vector<i32> lp_of((size_t)nnz);
+    bs.nz_off.assign((size_t)nlp + 1, 0);
+    auto lp_of_col = [&](i64 j) { return (i64)(std::upper_bound(bs.col_off.begin(), bs.col_off.end(), j) - bs.col_off.begin()) - 1; };
+    if (!k2) {
+        for (i64 j = 0; j < S.n; ++j) { const i64 k = lp_of_col(j); for (i64 p = S.Ap[(size_t)j]; p < S.Ap[(size_t)j + 1]; ++p) lp_of[(size_t)p] = (i32)k; }
+    } else {
+        for (i64 p = 0; p < nnz; ++p) { const i64 q = S.Ap[(size_t)p]; lp_of[(size_t)p] = (i32)lp_of_col(std::min(S.Ai[(size_t)q], S.Ai[(size_t)q + 1])); }
+    }
+    for (i64 p = 0; p < nnz; ++p) {
+        const i64 k = lp_of[(size_t)p];
+        if (k < 0 || k >= nlp || (p > 0 && k < lp_of[(size_t)p - 1])) { h->last_error = "tlpk_ipm_batch_refill: the entries of an LP are not a contiguous range of nzval"; return TLPK_INTERNAL; }
+        ++bs.nz_off[(size_t)k + 1];
+    }
+    for (i64 k = 0; k < nlp; ++k) bs.nz_off[(size_t)k + 1] += bs.nz_off[(size_t)k];
+    i32 *di;
+    if (int rc = dev_upload(h, &di, lp_of)) return rc;
+    bs.d_lp_of = di;
+    if (k2) {
+        std::vector<i64> ap, tp; std::vector<i32> ai, tj, src; std::vector<double> ax, tx;
+        if (int rc = ipm_sub_matrix(h, false, ap, ai, ax, tp, tj, tx)) return rc;
+        if ((i64)ai.size() != nnz) { h->last_error = "tlpk_ipm_batch_refill: the loops' copy of A does not match nzval"; return TLPK_INTERNAL; }
+        src.resize(ai.size());
+        std::vector<i64> cur(tp.begin(), tp.end() - 1);
+        for (size_t q = 0; q < ai.size(); ++q) src[(size_t)cur[(size_t)ai[q]]++] = (i32)q;      // the order in which ipm_sub_matrix fills tx
+        if (int rc = dev_upload(h, &di, src)) return rc;
+        bs.d_ktx_src = di;
+    }
+    bs.refill_maps = true;
+    return TLPK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tlpk_ipm_batch_refill(tlpk_handle *h, const uint8_t *slots, const double *nzval, int64_t len,
+                          const double *b, const double *c, const double *l, const double *u) {
+    if (!h) return TLPK_BADARG;
+    if (!h->ipm) { h->last_error = "tlpk_ipm_load_batch has not been called (load first)"; return TLPK_BADARG; }
+    if (!h->ipm->bat) { h->last_error = "the handle holds one LP (tlpk_ipm_load): the tlpk_ipm_batch_* calls need tlpk_ipm_load_batch"; return TLPK_BADARG; }
+    if (!slots) { h->last_error = "tlpk_ipm_batch_refill: slots is NULL"; return TLPK_BADARG; }
+    const Symbolic &S = h->S;
+    const bool k2 = S.system == 1;
+    const i64 nnz = k2 ? S.n : S.nnzA;
+    if (nzval && len != nnz) { h->last_error = "tlpk_ipm_batch_refill: len = " + std::to_string(len) + ", the analysed matrix has " + std::to_string(nnz) + " entries"; return TLPK_BADARG; }
+    IpmBatchState *bp = nullptr;
+    if (int rc = batch_state(h, bp)) return rc;                       // (the stale handle; an analyse-only handle is never loaded)
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm; const IpmVecs &v = s.v; const i64 nlp = bs.nlp;
+    // runs of selected slots: neighbours share their copies
+    std::vector<i64> runs;
+    for (i64 k = 0; k < nlp; ++k) {
+        if (!slots[k]) continue;
+        if (!runs.empty() && runs.back() == k) runs.back() = k + 1;
+        else { runs.push_back(k); runs.push_back(k + 1); }
+    }
+    if (runs.empty()) return TLPK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                       // nothing of the previous call reads the vectors or the pinned scalars any more
+    if (nzval) if (int rc = refill_maps(h, bs)) return rc;
+    if (int rc = batch_scalars(h, bs, slots, [](i64, int) { return 0.0; })) return rc;      // the flags: what the kernels below select by
+    hipStream_t st = h->stream;
+    if (nzval) {
+        std::vector<i64> ranges;
+        for (size_t r = 0; r < runs.size(); r += 2) { ranges.push_back(bs.nz_off[(size_t)runs[r]]); ranges.push_back(bs.nz_off[(size_t)runs[r + 1]]); }
+        if (int rc = set_values_slots(h, nzval, ranges, bs.d_lp_of, bs.d_sc + (IPM_BSC - 1), IPM_BSC)) return rc;
+        if (k2) {
+            // the loops' own copies: column-major = nzval's order, row-major through its map
+            for (size_t r = 0; r < ranges.size(); r += 2)
+                if (ranges[r + 1] > ranges[r]) HIPCHK(h, hipMemcpyAsync(const_cast<double *>(v.Ax) + ranges[r], nzval + ranges[r], (size_t)(ranges[r + 1] - ranges[r]) * 8, hipMemcpyHostToDevice, st));
+            launch_refresh_gather_sel(st, nnz, bs.d_ktx_src, h->d_nz, const_cast<double *>(v.Tx), bs.d_lp_of, bs.d_sc + (IPM_BSC - 1), IPM_BSC);
+        }
+    }
+    // the vectors: the selected segments; flag and bound .* flag as tlpk_ipm_load forms them (ipmdata.jl:46-47).  The staging lives until the wait below.
+    std::vector<double> stage;
+    if (l || u) {
+        i64 total = 0;
+        for (size_t r = 0; r < runs.size(); r += 2) total += bs.col_off[(size_t)runs[r + 1]] - bs.col_off[(size_t)runs[r]];
+        stage.resize((size_t)(4 * total));
+    }
+    double *sp = stage.data();
+    for (size_t r = 0; r < runs.size(); r += 2) {
+        const i64 r0 = bs.row_off[(size_t)runs[r]], mk = bs.row_off[(size_t)runs[r + 1]] - r0;
+        const i64 c0 = bs.col_off[(size_t)runs[r]], nk = bs.col_off[(size_t)runs[r + 1]] - c0;
+        if (b) HIPCHK(h, hipMemcpyAsync(const_cast<double *>(v.b) + r0, b + r0, (size_t)mk * 8, hipMemcpyHostToDevice, st));
+        if (c) HIPCHK(h, hipMemcpyAsync(const_cast<double *>(v.c) + c0, c + c0, (size_t)nk * 8, hipMemcpyHostToDevice, st));
+        for (int side = 0; side < 2; ++side) {
+            const double *bd = side ? u : l;
+            if (!bd) continue;
+            double *w0 = sp, *w1 = sp + nk;
+            sp += 2 * nk;
+            for (i64 j = 0; j < nk; ++j) { const bool f = std::isfinite(bd[c0 + j]); w0[j] = f ? 1.0 : 0.0; w1[j] = f ? bd[c0 + j] : 0.0; }
+            HIPCHK(h, hipMemcpyAsync(const_cast<double *>(side ? v.uflag : v.lflag) + c0, w0, (size_t)nk * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(const_cast<double *>(side ? v.uz : v.lz) + c0, w1, (size_t)nk * 8, hipMemcpyHostToDevice, st));
+        }
+    }
+    ipmb_launch_init(st, v, bs.B);                                    // HSD.jl:238-247 on the selected LPs
+    HIPCHK(h, hipStreamSynchronize(st));
+    HIPCHK(h, hipGetLastError());
+    return TLPK_OK;
+}
+
+int tlpk_ipm_get_lp(tlpk_handle *h, int what, int64_t k, double *host, int64_t len) {
+    Shards sh;
+    if (int rc = ipm_shards(h, sh, true, true, true)) return rc;
+    if (!host || what < 0 || what > 35) return TLPK_BADARG;
+    IpmBatchState *bs = h->ipm->bat;
+    if (!bs) { h->last_error = "tlpk_ipm_get_lp: the handle holds one LP (tlpk_ipm_load): it needs tlpk_ipm_load_batch"; return TLPK_BADARG; }
+    if (k < 0 || k >= bs->nlp) { h->last_error = "tlpk_ipm_get_lp: LP " + std::to_string(k) + " of " + std::to_string(bs->nlp); return TLPK_BADARG; }
+    const std::vector<i64> &off = ipm_get_is_row(what) ? bs->row_off : bs->col_off;
+    const i64 need = off[(size_t)k + 1] - off[(size_t)k];
+    if (len != need) { h->last_error = "tlpk_ipm_get_lp: wrong length"; return TLPK_BADARG; }
+    const double *src[36];
+    ipm_get_sources(h, src);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!src[what]) { h->last_error = "tlpk_ipm_get_lp: the handle does not hold that vector"; return TLPK_BADARG; }
+    HIPCHK(h, hipMemcpy(host, src[what] + off[(size_t)k], (size_t)need * 8, hipMemcpyDeviceToHost));
     return TLPK_OK;
 }
 

@@ -65,6 +65,7 @@ struct IpmBatch {
 inline int ipm_seg_blocks(i64 len) { return (int)std::max<i64>(1, std::min<i64>(IPM_BLOCKS, (len + 255) / 256)); }
 
 void ipmb_launch_finalize(hipStream_t st, const IpmBatch &B, const IpmBlockTab &t, int nsum, int nmax, int nmin, const double *partials, double *out);
+void ipmb_launch_init(hipStream_t st, const IpmVecs &v, const IpmBatch &B);      // the starting point of the LPs whose flag is set (tlpk_ipm_batch_refill)
 void ipmb_launch_res_cols(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *partials);
 void ipmb_launch_res_rows(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *partials);
 void ipmb_launch_theta(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD);

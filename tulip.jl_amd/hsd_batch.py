@@ -10,6 +10,11 @@ decided and is never touched again; with B = 1 the run is `DeviceHSD`'s bit for 
     opt = BatchedDeviceHSD([standard_form(lp) for lp in lps], device=0)      # or tuples (A, b, c, l, u[, c0[, objsense_min]])
     opt.optimize()
     opt.status[k], opt.niter[k], opt.primal_objective[k], opt.solution(k)
+
+More LPs than slots (DESIGN.md section 4b'-r): the B LPs of the constructor are the first occupants of B slots, a queue streams through them --
+a slot whose LP is decided takes the next LP of its pattern (`refill`: tlpk_ipm_batch_refill) while the others continue.
+
+    records = opt.optimize_stream(more_lps)      # one record per LP of constructor + queue; opt.passes
 """
 import ctypes as C
 import time
@@ -33,6 +38,37 @@ def _fields(lp):
         sense = lp[6] if len(lp) > 6 else True
         return A, b, c, l, u, float(c0), bool(sense)
     return lp.A, lp.b, lp.c, lp.l, lp.u, float(getattr(lp, "c0", 0.0)), bool(getattr(lp, "objsense", True))
+
+
+def _csc(A):
+    """A as a canonical scipy CSC matrix (sorted row indices, duplicates summed); the caller's matrix is not modified."""
+    import scipy.sparse as sp
+    A = sp.csc_matrix(A, dtype=np.float64, copy=True) if sp.issparse(A) else sp.csc_matrix(np.asarray(A, dtype=np.float64))
+    A.sum_duplicates()
+    return A
+
+
+def pattern_key(A):
+    """What two LPs must share to take turns in one slot of an analysed handle: the shape, the column pointers and the row indices of A
+    (stored entries count, their values do not).  Equal patterns give equal keys; a moved entry or another shape gives another key."""
+    return _key(_csc(A))
+
+
+def _key(A):
+    return (tuple(int(v) for v in A.shape), A.indptr.astype(np.int64).tobytes(), A.indices.astype(np.int64).tobytes())
+
+
+def stream_assign(free_slots, slot_keys, queue_keys):
+    """The schedule of `optimize_stream` at the top of one pass: every free slot, in slot order, takes the FIRST LP of the queue whose pattern
+    is the slot's.  free_slots: slot numbers; slot_keys[k]: the pattern key of slot k; queue_keys: the keys of the LPs still waiting, in
+    queue order.  Returns [(slot, position in the queue)]; a slot with no matching LP left is not in the list (it stays parked)."""
+    taken, out = set(), []
+    for k in sorted(free_slots):
+        for pos, key in enumerate(queue_keys):
+            if pos not in taken and key == slot_keys[k]:
+                taken.add(pos); out.append((k, pos))
+                break
+    return out
 
 
 class BatchedDeviceHSD:
@@ -81,6 +117,9 @@ class BatchedDeviceHSD:
         self._host_norms()
         self._init_state()
         self.last_update_rc = None
+        self.passes = self.refills = 0                                           # optimize_stream: trips round the loop; refill calls, the time inside them and in reading records
+        self.refill_seconds = self.record_seconds = 0.0
+        self.corrector_rounds = 0
         self.loaded = False
         if load:
             self._call(self.L.tlpk_ipm_load_batch(self.kkt._h, B, _lib.as_p64(self.row_off), _lib.as_p64(self.col_off),
@@ -152,6 +191,132 @@ class BatchedDeviceHSD:
         self._host_norms()
         self._init_state()
         return self
+
+    def _slot_range(self, k):
+        """Where LP k's entries sit in the stacked matrix's value array (block-diagonal CSC: the columns of an LP are contiguous)."""
+        return int(self.A.indptr[self.col_off[k]]), int(self.A.indptr[self.col_off[k + 1]])
+
+    def slot_key(self, k):
+        """`pattern_key` of the LP slot k was analysed with."""
+        p0, p1 = self._slot_range(k)
+        indptr = self.A.indptr[self.col_off[k]:self.col_off[k + 1] + 1].astype(np.int64) - p0
+        indices = self.A.indices[p0:p1].astype(np.int64) - self.row_off[k]
+        shape = (int(self.row_off[k + 1] - self.row_off[k]), int(self.col_off[k + 1] - self.col_off[k]))
+        return (shape, indptr.tobytes(), indices.tobytes())
+
+    def _hsd_only(self, what):
+        if type(self).optimize is not BatchedDeviceHSD.optimize:             # (BatchedDeviceMPC: its starting point needs a factorisation and two solves per LP)
+            raise NotImplementedError(f"{what} serves the homogeneous self-dual loop only: {type(self).__name__} has no refill")
+
+    def _per_lp(self, options, count, what):
+        if options is None or isinstance(options, Options) or isinstance(options, type):
+            return [options or Options()] * count
+        options = list(options)
+        if len(options) != count:
+            raise ValueError(f"{what}: one Options object, or one per LP")
+        return options
+
+    def refill(self, slots, lps, options=None):
+        """New LPs for the listed slots of the analysed handle (tlpk_ipm_batch_refill): lps[i] replaces the LP of slots[i] -- matrix values, b, c, l,
+        u, c0, objective sense, options (default: `Options()`) -- and starts from the HSD starting point with its host state (tau, kappa, mu,
+        regularisations, niter, statuses, timers, recorded norms) re-initialised; every other slot continues untouched.  An LP whose pattern
+        (shape, column pointers, row indices) differs from its slot's raises ValueError, and nothing is changed."""
+        self._hsd_only("refill")
+        slots = [int(k) for k in slots]
+        lps = list(lps)
+        if len(slots) != len(lps) or len(set(slots)) != len(slots) or any(not 0 <= k < self.nlp for k in slots):
+            raise ValueError("refill: one LP per listed slot, every slot listed once, slots in 0 .. nlp - 1")
+        opts = self._per_lp(options, len(slots), "refill options")
+        staged = []
+        for k, lp in zip(slots, lps):
+            st = self._stage(lp, f"refill, slot {k}")
+            if st[0] != self.slot_key(k):
+                raise ValueError(f"refill: the pattern of the LP for slot {k} (shape, column pointers, row indices) differs from the slot's")
+            staged.append((k,) + st[1:])
+        if not self.loaded:
+            raise RuntimeError("BatchedDeviceHSD(load=False): nothing is loaded on the device")
+        return self._apply(staged, opts)
+
+    @staticmethod
+    def _stage(lp, where, memo=None):
+        """(pattern key, values in canonical CSC order, [b, c, l, u], c0, objsense) of one LP that is to enter a slot; the vectors are checked against A.
+        memo: LPs that share one matrix OBJECT (the same A under many costs) share its canonical copy and its key."""
+        A, b, c, l, u, c0, sense = _fields(lp)
+        if memo is not None and id(A) in memo:
+            A, key = memo[id(A)][1:]
+        else:
+            A0, A = A, _csc(A)
+            key = _key(A)
+            if memo is not None:
+                memo[id(A0)] = (A0, A, key)                                  # (holds A0: its id stays its own for the memo's lifetime)
+        mk, nk = A.shape
+        vecs = []
+        for v, length, what in ((b, mk, "b"), (c, nk, "c"), (l, nk, "l"), (u, nk, "u")):
+            a = np.asarray(v, dtype=np.float64)
+            if a.shape != (length,):
+                raise DimensionMismatch(f"{where}: {what} does not match A")
+            vecs.append(a)
+        return key, A.data, vecs, c0, sense
+
+    def _apply(self, staged, opts):
+        """`refill` behind its checks: staged = [(slot, values, [b, c, l, u], c0, objsense)] with the slots' own patterns."""
+        if not staged:
+            return self
+        sel = np.zeros(self.nlp, dtype=np.uint8)
+        # an array in which no selected LP changes a bit (the same matrix under new costs, the same bounds) is not sent: NULL = keep
+        same = lambda dst, src: np.array_equal(dst.view(np.int64), np.ascontiguousarray(src).view(np.int64))      # noqa: E731
+        new = dict.fromkeys(("A", "b", "c", "l", "u"), False)
+        for (k, data, vecs, c0, sense), o in zip(staged, opts):
+            p0, p1 = self._slot_range(k)
+            rs, cs = slice(self.row_off[k], self.row_off[k + 1]), slice(self.col_off[k], self.col_off[k + 1])
+            for name, dst, src in (("A", self.A.data[p0:p1], data), ("b", self._b[rs], vecs[0]), ("c", self._c[cs], vecs[1]),
+                                   ("l", self._l[cs], vecs[2]), ("u", self._u[cs], vecs[3])):
+                if not same(dst, src):
+                    new[name] = True
+                    dst[:] = src
+            self.c0[k] = c0; self.objsense[k] = sense
+            sel[k] = 1
+        nz = self.A.data
+        ptr = lambda name, a: _lib.as_pd(a) if new[name] else None           # noqa: E731
+        t0 = time.perf_counter()
+        self._call(self.L.tlpk_ipm_batch_refill(self.kkt._h, _lib.as_pu8(sel), ptr("A", nz), nz.shape[0],
+                                                ptr("b", self._b), ptr("c", self._c), ptr("l", self._l), ptr("u", self._u)))
+        self.refills += 1; self.refill_seconds += time.perf_counter() - t0     # (the call returns when the device has finished)
+        self.opts = list(self.opts)
+        for (k, *_rest), o in zip(staged, opts):
+            self._host_norms_of(k)
+            self._init_slot(k)
+            self.opts[k] = o
+            for name, arr in self._o.items():
+                arr[k] = float(getattr(o, name))
+            self.time_limit = min(self.time_limit, float(o.TimeLimit))
+        self._cache = {}
+        return self
+
+    def _host_norms_of(self, k):
+        """`_host_norms` for slot k alone."""
+        rs, cs = slice(self.row_off[k], self.row_off[k + 1]), slice(self.col_off[k], self.col_off[k + 1])
+        l, u = self._l[cs], self._u[cs]
+        lf, uf = np.isfinite(l), np.isfinite(u)
+        nrm = lambda v: float(np.abs(v).max(initial=0.0))                    # noqa: E731
+        self.p[k] = int(lf.sum()) + int(uf.sum())
+        self.nb[k], self.nc[k] = nrm(self._b[rs]), nrm(self._c[cs])
+        self.nlz[k], self.nuz[k] = nrm(np.where(lf, l, 0.0)), nrm(np.where(uf, u, 0.0))
+
+    def _init_slot(self, k):
+        """`_init_state` for slot k alone."""
+        for v in (self.regP, self.regD, self.regG, self.tau, self.kappa, self.mu):
+            v[k] = 1.0
+        self.rg[k] = self.h0[k] = 0.0
+        self.niter[k] = 0
+        self.status[k] = "Trm_Unknown"; self.primal_status[k] = "Sln_Unknown"; self.dual_status[k] = "Sln_Unknown"
+        self.active[k] = False
+        for v in self.timers.values():
+            v[k] = 0
+        self.rho[k] = 0.0
+        for name in ("rp_nrm", "rl_nrm", "ru_nrm", "rd_nrm", "cx", "xz", "ax_nrm", "xxl_nrm", "xxu_nrm", "delta_nrm", "dualsum", "rg_nrm",
+                     "primal_objective", "dual_objective"):
+            getattr(self, name)[k] = 0.0
 
     def _call(self, rc):
         _raise_for(rc, self.kkt._h, "tlpk_ipm_batch: ")
@@ -303,6 +468,7 @@ class BatchedDeviceHSD:
                 self._call(self.L.tlpk_ipm_batch_accept(self.kkt._h, self._mask(take)))
                 dtau = np.where(take, ctau, dtau); dkappa = np.where(take, ckappa, dkappa); alpha = np.where(take, ac, alpha)
             cor = cor & ~(ac < 1.1 * a_) & (ncor < o["CorrectionLimit"]) & (alpha < 0.999)      # an LP that breaks out is masked for the rest of the step
+        self.corrector_rounds += ncor                                        # (a statistic: rounds of the centrality corrector, summed over the steps)
         alpha = alpha * o["StepDampFactor"]
         xz = np.zeros(B)
         self._call(self.L.tlpk_ipm_batch_advance(self.kkt._h, self._mask(step), _lib.as_pd(np.ascontiguousarray(alpha)), _lib.as_pd(xz)))
@@ -354,15 +520,121 @@ class BatchedDeviceHSD:
         off = self.row_off if what in _lib.IPM_GET_ROWS else self.col_off
         return self._vec(what)[off[k]:off[k + 1]].copy()
 
+    # ---- a batch that keeps going (DESIGN.md section 4b'-r) ----
+    def optimize_stream(self, lps, options=None):
+        """N LPs through the B slots of this handle: the LPs of the constructor are the first occupants, `lps` is the queue.  When an LP leaves
+        (decided, iteration limit, numerical problem) its record is read through tlpk_ipm_get_lp and, at the top of the next pass, its slot takes
+        the first LP of the queue whose pattern is the slot's (`stream_assign`; `refill`) while every other slot continues untouched.  The
+        schedule is deterministic.  options: for the LPs of the queue (one `Options`, or one per LP; default `Options()`) -- options travel
+        with the LP, not with the slot.  IterationsLimit counts per LP, TimeLimit is global.  One pass is one trip round the loop of
+        `optimize()`; `self.passes` counts them.  Returns one record per LP of constructor + queue, in that order: what `solution(k)`
+        returns, plus zl, zu and the homogeneous iterate xh, yh as the device holds them, tau, timers, the slot the LP ran in and the
+        passes (1-based) in which it entered and left.  A queue LP that matches no slot raises ValueError before anything runs."""
+        self._hsd_only("optimize_stream")
+        B = self.nlp
+        memo = {}
+        queue = [self._stage(lp, f"optimize_stream, LP {q} of the queue", memo) for q, lp in enumerate(lps)]
+        N = len(queue)
+        qopts = self._per_lp(options, N, "optimize_stream options")
+        number = {}                                                          # pattern key -> a small integer: the schedule compares those
+        slot_keys = [number.setdefault(self.slot_key(k), len(number)) for k in range(B)]
+        qkeys = [number.get(st[0], -1) for st in queue]
+        for q, key in enumerate(qkeys):
+            if key < 0:
+                raise ValueError(f"optimize_stream: LP {q} of the queue has the pattern (shape, column pointers, row indices) of no slot")
+        if not self.loaded:
+            raise RuntimeError("BatchedDeviceHSD(load=False): nothing is loaded on the device")
+        tstart = time.perf_counter()
+        time_limit = min([self.time_limit] + [float(o.TimeLimit) for o in qopts])
+        self._call(self.L.tlpk_ipm_reset(self.kkt._h))
+        self._init_state()
+        act = self.active
+        act[:] = True
+        records = [None] * (B + N)
+        lp_of_slot, entered, free, waiting = list(range(B)), [1] * B, set(), list(range(N))
+        self.passes = self.refills = 0
+        self.refill_seconds = self.record_seconds = 0.0
+        self.corrector_rounds = 0
+        stopped = None
+
+        def leave(mask):
+            t0 = time.perf_counter()
+            for k in np.flatnonzero(mask):
+                records[lp_of_slot[k]] = self._record(int(k), entered[k], self.passes)
+                free.add(int(k))
+            self.record_seconds += time.perf_counter() - t0
+
+        with np.errstate(all="ignore"):
+            while True:
+                if free and waiting:
+                    pairs = stream_assign(free, slot_keys, [qkeys[q] for q in waiting])
+                    if pairs:
+                        qs = [waiting[pos] for _, pos in pairs]
+                        self._apply([(k,) + queue[q][1:] for (k, _), q in zip(pairs, qs)], [qopts[q] for q in qs])
+                        for (k, _), q in zip(pairs, qs):
+                            lp_of_slot[k], entered[k] = B + q, self.passes + 1
+                            free.discard(k); act[k] = True
+                        gone = set(qs)
+                        waiting = [q for q in waiting if q not in gone]
+                if not act.any():
+                    break
+                self.passes += 1
+                before = act.copy()
+                self.compute_residuals(act)
+                self.update_solver_status(act)
+                act &= ~np.isin(self.status, _DECIDED)
+                lim = act & (self.niter >= self._o["IterationsLimit"])
+                self.status[lim] = "Trm_IterationLimit"
+                act &= ~lim
+                leave(before & ~act)
+                if not act.any():
+                    continue
+                if time.perf_counter() - tstart >= time_limit:
+                    self.status[act] = stopped = "Trm_TimeLimit"; leave(act); act[:] = False; break
+                try:
+                    moved = self.compute_step(act)
+                except OutOfMemoryError:
+                    self.status[act] = stopped = "Trm_MemoryLimit"; leave(act); act[:] = False; break
+                failed = act & ~moved                                        # (Trm_NumericalProblem: the slot is free like any other)
+                act &= moved
+                leave(failed)
+                self.niter[act] += 1
+        for q in waiting:                                                    # (only after a global stop: these LPs never ran)
+            zn, zm = np.zeros(len(queue[q][2][1])), np.zeros(len(queue[q][2][0]))
+            records[B + q] = {"status": stopped, "niter": 0, "x": zn, "y": zm, "s": zn, "z_primal": 0.0, "z_dual": 0.0, "primal_status": "Sln_Unknown",
+                              "dual_status": "Sln_Unknown", "rho": (0.0, 0.0, 0.0), "zl": zn, "zu": zn, "xh": zn, "yh": zm, "tau": 1.0, "timers": {},
+                              "slot": None, "entered": None, "left": None, "primal_objective": 0.0, "dual_objective": 0.0}
+        self._cache = {}
+        self.seconds = time.perf_counter() - tstart
+        self.records = records
+        return records
+
+    def _get_lp(self, k, what):
+        """`_get` through tlpk_ipm_get_lp: LP k's segment alone crosses the bus."""
+        off = self.row_off if what in _lib.IPM_GET_ROWS else self.col_off
+        v = np.empty(int(off[k + 1] - off[k]))
+        self._call(self.L.tlpk_ipm_get_lp(self.kkt._h, what, k, _lib.as_pd(v), v.shape[0]))
+        return v
+
+    def _record(self, k, entered, left):
+        vec = {what: self._get_lp(k, what) for what in (0, 3, 4, 5)}
+        rec = self._solution(k, None, lambda _k, what: vec[what])
+        rec.update(zl=vec[3], zu=vec[4], xh=vec[0], yh=vec[5], tau=float(self.tau[k]), timers=self.timers_of(k), slot=k, entered=entered, left=left,
+                   primal_objective=float(self.primal_objective[k]), dual_objective=float(self.dual_objective[k]))
+        return rec
+
     def solution(self, k, nvar=None):
         """What `DeviceHSD.solution` returns, for LP k."""
+        return self._solution(k, nvar, self._get)
+
+    def _solution(self, k, nvar, get):
         ray = "Sln_InfeasibilityCertificate" in (self.primal_status[k], self.dual_status[k])
         t_ = 1.0 if ray else 1.0 / self.tau[k]
         nk = int(self.col_off[k + 1] - self.col_off[k])
         n = nk if nvar is None else nvar
-        x = self._get(k, 0)[:n] * t_
-        s = (self._get(k, 3)[:n] - self._get(k, 4)[:n]) * t_
-        y = self._get(k, 5) * t_
+        x = get(k, 0)[:n] * t_
+        s = (get(k, 3)[:n] - get(k, 4)[:n]) * t_
+        y = get(k, 5) * t_
         sgn = 1.0 if self.objsense[k] else -1.0
         return {"status": str(self.status[k]), "niter": int(self.niter[k]), "x": x, "y": y, "s": s,
                 "z_primal": sgn * float(self.primal_objective[k]), "z_dual": sgn * float(self.dual_objective[k]),

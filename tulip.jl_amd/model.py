@@ -118,12 +118,17 @@ class Model:
         return self
 
     @classmethod
-    def optimize_batch(cls, models, **kw):
+    def optimize_batch(cls, models, slots=None, **kw):
         """`optimize()` of many models in one set of launches (hsd_batch.BatchedDeviceHSD, or mpc_batch.BatchedDeviceMPC where every model
         has algorithm="mpc"): each model is presolved and brought to standard form on its own, ONE batched interior-point run solves the LPs
         presolve did not already finish, each is postsolved, and every model ends as after its own `optimize()`.
-        kw: the backend's keywords (system=, device=, ...; default: those of the first model)."""
+        kw: the backend's keywords (system=, device=, ...; default: those of the first model).
+        slots=B: the LPs STREAM through handles of at most B slots (BatchedDeviceHSD.optimize_stream) -- the models that reach the interior-point
+        method are grouped by the pattern of their standard form, each group runs through one handle of min(B, group size) slots, and a slot whose
+        LP is decided takes the group's next one.  The homogeneous self-dual loop only: algorithm="mpc" with slots raises ValueError."""
         models = list(models)
+        if slots is not None:
+            return cls._optimize_stream(models, int(slots), kw)
         algorithms = {mdl.algorithm for mdl in models}
         if len(algorithms) > 1:
             raise ValueError(f"optimize_batch runs ONE interior-point loop for the whole batch: the models mix the algorithms {sorted(algorithms)}")
@@ -151,6 +156,40 @@ class Model:
                 res = mdl.inner = InnerResult(str(opt.status[k]), str(opt.primal_status[k]), str(opt.dual_status[k]), opt._get(k, 0), opt._get(k, 5),
                                               opt._get(k, 3), opt._get(k, 4), float(opt.tau[k]), float(opt.primal_objective[k]),
                                               float(opt.dual_objective[k]), int(opt.niter[k]))
+                sol_inner = extract_solution(lp_inner, res)
+                mdl.solution = mdl.presolve.postsolve(sol_inner) if mdl.presolve_options.Level > 0 else sol_inner
+                mdl.status = res.status
+            opt.kkt.close()
+        return models
+
+    @classmethod
+    def _optimize_stream(cls, models, slots, kw):
+        from .hsd_batch import BatchedDeviceHSD, pattern_key
+        if slots < 1:
+            raise ValueError("optimize_batch: slots must be at least 1")
+        if any(mdl.algorithm != "hsd" for mdl in models):
+            raise ValueError("optimize_batch(slots=...) streams through the homogeneous self-dual loop: every model must have algorithm='hsd' "
+                             "(algorithm='mpc': the Mehrotra batch has no refill)")
+        groups = {}                                                          # pattern -> [(model, reduced LP, standard form)], in the order of `models`
+        for mdl in models:
+            lp_inner = mdl.lp
+            if mdl.presolve_options.Level > 0:
+                ps = mdl.presolve = Presolve(mdl.lp, mdl.presolve_options)
+                st = mdl.status = ps.run()
+                if st in (TRM_OPTIMAL, TRM_PRIMAL_INFEASIBLE, TRM_DUAL_INFEASIBLE):    # presolve solved the problem
+                    mdl.solution = ps.postsolve(ps.solution)
+                    mdl.inner = None
+                    continue
+                lp_inner = ps.reduced_problem()
+            d = standard_form(lp_inner)
+            groups.setdefault(pattern_key(d.A), []).append((mdl, lp_inner, d))
+        for group in groups.values():
+            nslots = min(slots, len(group))
+            opt = BatchedDeviceHSD([d for _, _, d in group[:nslots]], **(kw or models[0].backend_kw))
+            records = opt.optimize_stream([d for _, _, d in group[nslots:]])
+            for (mdl, lp_inner, _), r in zip(group, records):
+                res = mdl.inner = InnerResult(r["status"], r["primal_status"], r["dual_status"], r["xh"], r["yh"], r["zl"], r["zu"], r["tau"],
+                                              float(r["primal_objective"]), float(r["dual_objective"]), r["niter"])
                 sol_inner = extract_solution(lp_inner, res)
                 mdl.solution = mdl.presolve.postsolve(sol_inner) if mdl.presolve_options.Level > 0 else sol_inner
                 mdl.status = res.status
