@@ -374,6 +374,33 @@ int64_t tlpk_symbolic_get_f64(const tlpk_handle *h, const char *what, double *bu
 int tlpk_get_factor(tlpk_handle *h, double *lval, int64_t cap);
 
 /* ---------------------------------------------------------------------------------------------
+ * Block skip: leave diagonal blocks out of the following updates and solves (DESIGN.md section 4b'-s).  A handle whose matrix is block
+ * diagonal (tlpk_options.row_block, no linking rows) factorises and solves its blocks independently: no front of one block shares data
+ * with a front of another.  skip[k] != 0: block k (the ids of tlpk_options.row_block) is skipped; skip == NULL: no mask.  The mask
+ * stays in force until it is replaced.  It is a runtime predicate: the launch schedules, grids and task lists are what they are without
+ * it, the workgroups of a skipped block return at once, and nothing a skipped block owns is read or written.
+ *   Update.  The skipped blocks' panels, inverted diagonal blocks and update buffers keep every bit (they are not zeroed either); the
+ *   other blocks' factor equals an unmasked update's bit for bit.  A non-positive pivot in a skipped block cannot fail the update:
+ *   tlpk_stats.fail_col can only name a column of a block that ran.
+ *   Solve.  The other blocks' segments of dx / dy equal an unmasked solve's bit for bit (tlpk_solve_device and both right-hand sides of
+ *   tlpk_solve2_device; the host-pointer calls run the same kernels).  The segments of the skipped blocks are unspecified, but finite for
+ *   finite input and never uninitialised memory.  A block that is solved must have been factorised by the last update that touched it:
+ *   that is the caller's contract -- violating it gives unspecified values, never a wait.  After tlpk_block_skip(h, NULL, n_blocks) the
+ *   handle behaves as if no mask had ever been set.
+ *   Graph replay.  tlpk_set_values*, replayed schedules and tlpk_update_device_async keep working: the mask's content is read when the
+ *   kernels run, so a captured schedule stays valid when the mask changes.
+ * Checks, in this order (TLPK_BADARG with a sentence in tlpk_last_error unless a code is named): h NULL; not a single-device direct handle
+ * (multi-device, sharded, dense-matrix, Krylov and dense_cols handles); refine_steps > 0 (the refinement's norms run over all rows); a
+ * batch-loaded handle (the batch owns the mask: tlpk_ipm_batch_skip); no row_block, or linking rows; nblocks != tlpk_stats.n_blocks; a
+ * front that is not contained in one block (its pivot columns, its row indices, its parent); then TLPK_NO_DEVICE on an analyse-only
+ * handle.  A failed call leaves the previous mask in force.
+ * tlpk_symbolic_get keys: "front_unit" the block of every front, then of every isolated 1 x 1 front in the order of "singles" (-1 before
+ * the table exists: it is built by the first call that reaches that check); "front_skip" the bytes in force, per front and then per
+ * single (empty = no mask); "skip_bytes" one entry, the device memory of the tables (part of tlpk_stats.device_bytes once allocated).
+ * --------------------------------------------------------------------------------------------- */
+int tlpk_block_skip(tlpk_handle *h, const uint8_t *skip /*nblocks*/, int64_t nblocks);
+
+/* ---------------------------------------------------------------------------------------------
  * Device-resident HSD iterate: an OPTIONAL extension for callers that keep the
  * interior-point vectors in HBM.  The drop-in interface above moves 16 (m + n) bytes over PCIe per
  * solve and leaves every right-hand side to the host; here one call runs one routine of
@@ -447,7 +474,9 @@ int tlpk_ipm_get(tlpk_handle *h, int what, double *host, int64_t len);
  *   unbatched tlpk_mpc_* call on it returns TLPK_BADARG, as does every tlpk_ipm_batch_* / tlpk_mpc_batch_* call on a handle loaded with
  *   tlpk_ipm_load (or not loaded).
  *   tlpk_ipm_batch_factor: regP[k] / regD[k] are uniform within LP k.  An LP with active[k] = 0 is PARKED: theta_inv = 1, Rp = Rd = 1 on
- *   its block (the matrix the handle is analysed with), so a finished or failed LP cannot fail the update of the others.  On
+ *   its block (the matrix the handle is analysed with), so a finished or failed LP cannot fail the update of the others.  Whether the
+ *   parked block is then factorised and swept like every other block (the default) or left out of the update and the solves is
+ *   tlpk_ipm_batch_skip's choice, below; the vectors read with codes 33 - 35 of tlpk_ipm_get hold the parking values either way.  On
  *   TLPK_NOT_POSDEF *fail_lp is the LP that owns tlpk_stats.fail_col (through the permutation; K2: node j < n is a column, n + i a row),
  *   or -1 if that cannot be told; one failure is reported per update.  Otherwise *fail_lp = -1.
  * --------------------------------------------------------------------------------------------- */
@@ -463,6 +492,15 @@ int tlpk_ipm_batch_targets(tlpk_handle *h, const uint8_t *active, const double *
 /* the candidates of the LPs with active[k] != 0 become their accepted directions (a copy: the LPs accept independently) */
 int tlpk_ipm_batch_accept(tlpk_handle *h, const uint8_t *active);
 int tlpk_ipm_batch_advance(tlpk_handle *h, const uint8_t *active, const double *alpha /*nlp*/, double *out /*nlp*/);
+/* Batch-loaded handles: on != 0 -> every tlpk_ipm_batch_* / tlpk_mpc_batch_* call that takes `active` skips the blocks of the LPs with
+ * active[k] == 0 in its update / its solves (tlpk_block_skip's mechanism with the LPs as blocks; the flags travel with the call's scalars,
+ * there is no extra copy).  Default 0 = every block is factorised and swept.  With it on, tlpk_ipm_batch_factor still writes the parking
+ * values and leaves the parked LPs' panels as they are; tlpk_ipm_batch_hsolve_newton, tlpk_ipm_batch_newton and tlpk_mpc_batch_newton
+ * skip the parked LPs in their solves (an LP that is solved must be active in the last tlpk_ipm_batch_factor that followed its last change:
+ * the loops of hsd_batch.py / mpc_batch.py factorise every LP they solve).  tlpk_mpc_batch_start and tlpk_ipm_batch_refill run unmasked,
+ * and outside these calls no mask is in force.  The active LPs' results do not depend on the setting, bit for bit.
+ * TLPK_BADARG on a handle that is not batch-loaded, on one with refine_steps > 0, or when an LP's fronts are not its own. */
+int tlpk_ipm_batch_skip(tlpk_handle *h, int on);
 
 /* ---------------------------------------------------------------------------------------------
  * Refilling slots: a batch that keeps going.  A batch-loaded handle has nlp SLOTS; when the LP of a slot is decided, the next LP of the

@@ -10,7 +10,10 @@ per interior-point iteration (batched: per iteration of the batch, i.e. of its s
 iterations per LP, statuses, and the largest relative difference of the objectives between the two ways.
 Every batch size runs in a child process of its own under `timeout`; the driver stops at the first one that fails.
 
-    python tools/hsd_batch_bench.py [--sizes 1,8,64,512] [--reps 3] [--system K1]
+--skip-parked 0 runs the batch with every block factorised and swept (the default, and the behaviour before tlpk_ipm_batch_skip); 1 skips parked blocks.
+tools/batch_skip_bench.py measures both settings side by side in one process.
+
+    python tools/hsd_batch_bench.py [--sizes 1,8,64,512] [--reps 3] [--system K1] [--skip-parked 0]
 """
 import argparse
 import json
@@ -39,17 +42,17 @@ def costs(d, B, seed=20261018, rel=0.01):
     return out
 
 
-def worker(B, reps, system):
+def worker(B, reps, system, skip=0):
     from tulip_jl_amd.hsd_batch import BatchedDeviceHSD
     from tulip_jl_amd.hsd_device import DeviceHSD
     from tulip_jl_amd.problem import read_free_mps, standard_form
     d = standard_form(read_free_mps(os.path.join(ROOT, "tests", "golden", "stair25.mps")))
     cs = costs(d, B)
-    out = {"B": B, "system": system, "m": int(d.A.shape[0]), "n": int(d.A.shape[1]), "nnzA": int(d.A.nnz), "reps": reps}
+    out = {"B": B, "system": system, "m": int(d.A.shape[0]), "n": int(d.A.shape[1]), "nnzA": int(d.A.nnz), "reps": reps, "skip_parked": int(skip)}
     med = lambda v: float(np.median(np.asarray(v, dtype=float)))                         # noqa: E731
     # batched
     t0 = time.perf_counter()
-    opt = BatchedDeviceHSD([(d.A, d.b, c, d.l, d.u, d.c0, d.objsense) for c in cs], system=system, device=0)
+    opt = BatchedDeviceHSD([(d.A, d.b, c, d.l, d.u, d.c0, d.objsense) for c in cs], system=system, device=0, skip_parked=bool(skip))
     out["batched_setup_s"] = time.perf_counter() - t0
     wall = []
     for _ in range(reps):
@@ -95,15 +98,16 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--system", default="K1")
     ap.add_argument("--worker", type=int, default=0)
+    ap.add_argument("--skip-parked", type=int, choices=[0, 1], default=0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hsd_batch_bench.json"))
     a = ap.parse_args()
     if a.worker:
-        return worker(a.worker, a.reps, a.system)
+        return worker(a.worker, a.reps, a.system, a.skip_parked)
     res = []
     for B in (int(s) for s in a.sizes.split(",")):
         limit = LIMIT_S.get(B, 420)
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--worker", str(B), "--reps", str(a.reps),
-                            "--system", a.system], capture_output=True, text=True)
+                            "--system", a.system, "--skip-parked", str(a.skip_parked)], capture_output=True, text=True)
         line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not line:
             print(f"B = {B}: exit status {p.returncode}; nothing more is started on the GPU\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}", flush=True)

@@ -10,7 +10,10 @@ Median of three runs each.  Per B, written to profiles/hsd_stream_bench.json (al
 per LP, the time per refill call (the call returns when the device has finished), and whether every LP ends (a) with the status and the iteration
 count of (b).  Every B runs in a child process of its own under `timeout`; the driver stops at the first one that fails.
 
-    python tools/hsd_stream_bench.py [--slots 64,512] [--n 4096] [--reps 3] [--system K1]
+--skip-parked 0 runs stream and rounds with every block factorised and swept (the default, and the behaviour before tlpk_ipm_batch_skip); 1 skips
+parked blocks.  tools/batch_skip_bench.py measures both settings side by side in one process.
+
+    python tools/hsd_stream_bench.py [--slots 64,512] [--n 4096] [--reps 3] [--system K1] [--skip-parked 0]
 """
 import argparse
 import json
@@ -27,7 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 LIMIT_S = 540          # per child process
 
 
-def worker(B, N, reps, system):
+def worker(B, N, reps, system, skip=0):
     from hsd_batch_bench import costs
     from tulip_jl_amd.hsd_batch import BatchedDeviceHSD
     from tulip_jl_amd.problem import read_free_mps, standard_form
@@ -36,9 +39,9 @@ def worker(B, N, reps, system):
     cs = costs(d, N)
     lp = lambda c: (d.A, d.b, c, d.l, d.u, d.c0, d.objsense)                             # noqa: E731
     med = lambda v: float(np.median(np.asarray(v, dtype=float)))                         # noqa: E731
-    out = {"B": B, "N": N, "system": system, "m": int(d.A.shape[0]), "n": int(d.A.shape[1]), "nnzA": int(d.A.nnz), "reps": reps}
+    out = {"B": B, "N": N, "system": system, "m": int(d.A.shape[0]), "n": int(d.A.shape[1]), "nnzA": int(d.A.nnz), "reps": reps, "skip_parked": int(skip)}
     t0 = time.perf_counter()
-    opt = BatchedDeviceHSD([lp(c) for c in cs[:B]], system=system, device=0)
+    opt = BatchedDeviceHSD([lp(c) for c in cs[:B]], system=system, device=0, skip_parked=bool(skip))
     out["setup_s"] = time.perf_counter() - t0
     # (a) stream
     wall, passes, refills, refill_s = [], [], [], []
@@ -80,7 +83,7 @@ def worker(B, N, reps, system):
     for _ in range(reps):
         t0 = time.perf_counter()
         for r0 in range(0, N, B):
-            fresh = BatchedDeviceHSD([lp(c) for c in cs[r0:r0 + B]], system=system, device=0).optimize()
+            fresh = BatchedDeviceHSD([lp(c) for c in cs[r0:r0 + B]], system=system, device=0, skip_parked=bool(skip)).optimize()
             for what in (0, 3, 4, 5):
                 fresh._vec(what)
             fresh.kkt.close()
@@ -99,14 +102,15 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--system", default="K1")
     ap.add_argument("--worker", type=int, default=0)
+    ap.add_argument("--skip-parked", type=int, choices=[0, 1], default=0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hsd_stream_bench.json"))
     a = ap.parse_args()
     if a.worker:
-        return worker(a.worker, a.n, a.reps, a.system)
+        return worker(a.worker, a.n, a.reps, a.system, a.skip_parked)
     res = []
     for B in (int(s) for s in a.slots.split(",")):
         p = subprocess.run(["timeout", "-k", "10", str(LIMIT_S), sys.executable, os.path.abspath(__file__), "--worker", str(B), "--n", str(a.n),
-                            "--reps", str(a.reps), "--system", a.system], capture_output=True, text=True)
+                            "--reps", str(a.reps), "--system", a.system, "--skip-parked", str(a.skip_parked)], capture_output=True, text=True)
         line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not line:
             print(f"B = {B}: exit status {p.returncode}; nothing more is started on the GPU\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}", flush=True)

@@ -31,11 +31,11 @@ def note(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
-def run_batch(cls, lps, system, reps, tag):
+def run_batch(cls, lps, system, reps, tag, skip=0):
     med = lambda v: float(np.median(np.asarray(v, dtype=float)))                         # noqa: E731
     B = len(lps)
     t0 = time.perf_counter()
-    opt = cls(lps, system=system, device=0)
+    opt = cls(lps, system=system, device=0, skip_parked=bool(skip))
     out = {f"{tag}_setup_s": time.perf_counter() - t0}
     wall = []
     for r in range(reps):
@@ -52,7 +52,7 @@ def run_batch(cls, lps, system, reps, tag):
     return out, z
 
 
-def worker(B, reps, system):
+def worker(B, reps, system, skip=0):
     from hsd_batch_bench import costs
     from tulip_jl_amd.hsd_batch import BatchedDeviceHSD
     from tulip_jl_amd.mpc_batch import BatchedDeviceMPC
@@ -61,9 +61,9 @@ def worker(B, reps, system):
     d = standard_form(read_free_mps(os.path.join(ROOT, "tests", "golden", "stair25.mps")))
     cs = costs(d, B)
     lps = [(d.A, d.b, c, d.l, d.u, d.c0, d.objsense) for c in cs]
-    out = {"B": B, "system": system, "m": int(d.A.shape[0]), "n": int(d.A.shape[1]), "nnzA": int(d.A.nnz), "reps": reps}
+    out = {"B": B, "system": system, "m": int(d.A.shape[0]), "n": int(d.A.shape[1]), "nnzA": int(d.A.nnz), "reps": reps, "skip_parked": int(skip)}
     med = lambda v: float(np.median(np.asarray(v, dtype=float)))                         # noqa: E731
-    res, zb = run_batch(BatchedDeviceMPC, lps, system, reps, "mpc_batched")
+    res, zb = run_batch(BatchedDeviceMPC, lps, system, reps, "mpc_batched", skip)
     out.update(res)
     # sequential on one analysed handle
     t0 = time.perf_counter()
@@ -83,7 +83,7 @@ def worker(B, reps, system):
                sequential_iterations_mean=float(its.mean()), sequential_iterations_min=int(its.min()), sequential_iterations_max=int(its.max()),
                sequential_status={s: status.count(s) for s in set(status)})
     one.kkt.close()
-    res, zh = run_batch(BatchedDeviceHSD, lps, system, reps, "hsd_batched")
+    res, zh = run_batch(BatchedDeviceHSD, lps, system, reps, "hsd_batched", skip)
     out.update(res)
     out["speedup_over_sequential"] = out["mpc_batched_lps_per_s"] / out["sequential_lps_per_s"]
     out["mpc_over_hsd_batched"] = out["mpc_batched_lps_per_s"] / out["hsd_batched_lps_per_s"]
@@ -98,15 +98,16 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--system", default="K1")
     ap.add_argument("--worker", type=int, default=0)
+    ap.add_argument("--skip-parked", type=int, choices=[0, 1], default=0, help="0 (default): parked blocks are factorised and swept like the others; 1: skipped")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mpc_batch_bench.json"))
     a = ap.parse_args()
     if a.worker:
-        return worker(a.worker, a.reps, a.system)
+        return worker(a.worker, a.reps, a.system, a.skip_parked)
     res = []
     for B in (int(s) for s in a.sizes.split(",")):
         limit = LIMIT_S.get(B, 600)
         p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--worker", str(B), "--reps", str(a.reps),
-                            "--system", a.system], stdout=subprocess.PIPE, text=True)      # (the child's progress notes go straight to stderr)
+                            "--system", a.system, "--skip-parked", str(a.skip_parked)], stdout=subprocess.PIPE, text=True)     # (the child's progress notes go straight to stderr)
         line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not line:
             print(f"B = {B}: exit status {p.returncode}; nothing more is started on the GPU\n{p.stdout[-2000:]}", flush=True)

@@ -23,7 +23,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from . import _lib  # noqa: F401,E402
 from .kkt import (K1, K2, Backend, DenseBackend, DimensionMismatch, HIPDenseNormalEquations, HIPNormalEquations, KrylovBackend,  # noqa: F401,E402
                   OutOfMemoryError,
-                  PosDefException, arithmetic, backend, linear_system, run_ls_tests, setup,
+                  PosDefException, arithmetic, backend, block_skip, linear_system, run_ls_tests, setup,
                   set_values, set_values_device, solve, update)
 from .hsd_batch import BatchedDeviceHSD  # noqa: F401,E402
 from .mpc_batch import BatchedDeviceMPC  # noqa: F401,E402

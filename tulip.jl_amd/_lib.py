@@ -91,6 +91,7 @@ EXPORTS = [
     "tlpk_ipm_batch_targets", "tlpk_ipm_batch_accept", "tlpk_ipm_batch_advance",
     "tlpk_mpc_batch_start", "tlpk_mpc_batch_newton", "tlpk_mpc_batch_gap", "tlpk_mpc_batch_targets", "tlpk_mpc_batch_advance",
     "tlpk_ipm_batch_refill", "tlpk_ipm_get_lp",
+    "tlpk_block_skip", "tlpk_ipm_batch_skip",
 ]
 
 
@@ -213,7 +214,9 @@ def lib():
     L.tlpk_mpc_batch_advance.argtypes = [vp, pu8, pd, pd, pd]
     L.tlpk_ipm_batch_refill.argtypes = [vp, pu8, pd, C.c_int64, pd, pd, pd, pd]
     L.tlpk_ipm_get_lp.argtypes = [vp, C.c_int, C.c_int64, pd, C.c_int64]
-    for name in EXPORTS[-15:]:
+    L.tlpk_block_skip.argtypes = [vp, pu8, C.c_int64]
+    L.tlpk_ipm_batch_skip.argtypes = [vp, C.c_int]
+    for name in EXPORTS[-17:]:
         getattr(L, name).restype = C.c_int
     for name in ("tlpk_create", "tlpk_update", "tlpk_solve", "tlpk_update_device", "tlpk_solve_device",
                  "tlpk_sync", "tlpk_update_local", "tlpk_root_panel", "tlpk_update_finish",

@@ -55,6 +55,10 @@ __device__ __forceinline__ double *front_u(const DevCtx &c, const FrontDesc &fd)
 // columns of one slice are pld apart.
 __device__ __forceinline__ double *pcol(const DevCtx &c, const FrontDesc &fd, i32 col) { return c.Lval + fd.loff + pk_off(fd.lda, col); }
 __device__ __forceinline__ i32 pld(const FrontDesc &fd, i32 col) { return fd.lda - ((col >> 6) << 6); }
+// Block skip (DESIGN.md section 4b'-s): front_skip == nullptr is the unmasked path; else one byte per front (then one per isolated 1 x 1 front), set for the
+// fronts of the units that this update / solve leaves out.  Every per-front kernel asks right after it has read its task -- the front index is workgroup-uniform
+// (wave-uniform where a wave owns a front) -- and returns before it reads or writes anything the front owns.
+__device__ __forceinline__ bool front_skipped(const DevCtx &c, i32 front) { return c.front_skip != nullptr && c.front_skip[front] != 0; }
 
 // ------------------------------------------------------------------------------------------
 // elementwise / sparse kernels
@@ -94,10 +98,12 @@ __device__ __forceinline__ double asm_value(const i64 e, const i32 *__restrict__
 __global__ void k_assemble(i64 nent, const i64 *__restrict__ target, const i32 *__restrict__ diag_row,
                            const i64 *__restrict__ pptr, const double *__restrict__ pw,
                            const i32 *__restrict__ pj, const double *__restrict__ D,
-                           const double *__restrict__ regD, double *__restrict__ Lval, const unsigned char *__restrict__ upper, int part) {
+                           const double *__restrict__ regD, double *__restrict__ Lval, const unsigned char *__restrict__ upper, int part,
+                           const unsigned char *__restrict__ skip, const i32 *__restrict__ ent_front) {
     const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= nent) return;
     if (upper && (int)upper[e] != part) return;
+    if (skip && skip[ent_front[e]]) return;                        // block skip: ent_front[e] = the front whose panel holds entry e
     const i64 tg = target[e];
     if (tg < 0) return;
     Lval[tg] = asm_value(e, diag_row, pptr, pw, pj, D, regD);
@@ -109,9 +115,10 @@ __global__ void k_assemble(i64 nent, const i64 *__restrict__ target, const i32 *
 // the sign is applied with everybody else's between the sweeps (k_apply_signs).
 __global__ void k_single_factor(i64 n, const i64 *__restrict__ loff, const i64 *__restrict__ dinvoff,
                                 const i32 *__restrict__ col, double *__restrict__ Lval, double *__restrict__ dinv, int *info,
-                                const double *__restrict__ csign) {
+                                const double *__restrict__ csign, const unsigned char *__restrict__ skip) {
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (skip && skip[i]) return;                                  // block skip: the singles' bytes of front_skip
     double d = Lval[loff[i]];
     const double sj = csign ? csign[col[i]] : 1.0;
     if (!(sj * d > 0.0)) { atomicMin(info, col[i]); d = 1.0; }      // same convention as potrf_block
@@ -121,9 +128,10 @@ __global__ void k_single_factor(i64 n, const i64 *__restrict__ loff, const i64 *
     dinv[dinvoff[i]] = 1.0 / l;
 }
 __global__ void k_single_solve(i64 n, const i64 *__restrict__ dinvoff, const i32 *__restrict__ col,
-                               const double *__restrict__ dinv, double *__restrict__ xw, i64 xw2) {
+                               const double *__restrict__ dinv, double *__restrict__ xw, i64 xw2, const unsigned char *__restrict__ skip) {
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (skip && skip[i]) return;
     if (blockIdx.y) xw += xw2;                                    // (grid y = right-hand side of a pair)
     const double w = dinv[dinvoff[i]];
     xw[col[i]] = (xw[col[i]] * w) * w;                            // forward (x L^-1) then backward (x L^-1)
@@ -135,6 +143,7 @@ __global__ void k_single_solve(i64 n, const i64 *__restrict__ dinvoff, const i32
 // first row only -- and have no storage).
 __global__ __launch_bounds__(256) void k_zero_panels(const i32 *__restrict__ tasks, DevCtx c) {
     const i32 s = tasks[2 * blockIdx.x], c0 = tasks[2 * blockIdx.x + 1];
+    if (front_skipped(c, s)) return;
     const FrontDesc fd = c.fronts[s];
     const i32 lda = fd.lda, nc = min(NB_IN, fd.ns - c0), ld = pld(fd, c0);          // c0 = first column of a slice
     double *P = pcol(c, fd, c0);
@@ -149,6 +158,7 @@ __global__ __launch_bounds__(256) void k_zero_panels(const i32 *__restrict__ tas
 __global__ __launch_bounds__(256) void k_zero_small(const i32 *__restrict__ fronts, i64 n, DevCtx c) {      // one wave per small front
     const i64 idx = (i64)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (idx >= n) return;
+    if (front_skipped(c, fronts[idx])) return;                    // (wave-uniform)
     const FrontDesc fd = c.fronts[fronts[idx]];
     const i64 len = (i64)fd.lda * fd.ns;
     double *P = c.Lval + fd.loff;
@@ -173,6 +183,7 @@ __global__ __launch_bounds__(256) void k_extend_add(const EaTask *__restrict__ t
     __shared__ int s_ubuf[CB];
     __shared__ unsigned char s_tc[CB][EA_COLS];     // parent column - j0 of the child's columns [q0, q1)
     const EaTask t = tasks[blockIdx.x];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     const i32 f = fd.f, ns = fd.ns, rs = f - ns;
     double *Up = front_u(c, fd);
@@ -258,6 +269,7 @@ __global__ __launch_bounds__(256) void k_front_assemble(const FaTask *__restrict
     __shared__ int s_ubuf[CB];
     __shared__ unsigned char s_tc[CB][FA_CW];        // parent column - j0 of the child's columns [q0, q1)
     const FaTask t = tasks[blockIdx.x];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     const i32 ns = fd.ns;
     const i32 j0 = t.bc * FA_CW, j1 = min(j0 + FA_CW, ns);
@@ -1494,7 +1506,7 @@ __global__ __launch_bounds__(256) void k_potrf_small(const PotrfTask *__restrict
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform: task and front descriptor in scalar registers)
     const PotrfTask t = tasks[(i64)blockIdx.x * 4 + wave];
-    if (t.front < 0) return;
+    if (t.front < 0 || front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     const double *sg = SIGNED ? c.csign + fd.col0 : nullptr;
     const i32 ns = fd.ns;
@@ -1785,6 +1797,7 @@ template <bool SIGNED, int MODE>
 __global__ __launch_bounds__(256) void k_potrf(const PotrfTask *__restrict__ tasks, DevCtx c) {      // t.nb <= NB_IN
     __shared__ __attribute__((aligned(16))) double scratch[MODE == 3 ? POTRF_DPP_LDS : (MODE == 1 ? POTRF_WAVE_LDS : (MODE == 2 ? POTRF_PAIR_SCRATCH : POTRF_SCRATCH))];
     const PotrfTask t = tasks[blockIdx.x];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     potrf_block_any<SIGNED, MODE>(c, fd, t.k0, t.nb, t.k0, scratch);
 }
@@ -1850,6 +1863,7 @@ template <bool SIGNED, int MODE>
 __global__ __launch_bounds__(256, 2) void k_potrf_wide(const PotrfTask *__restrict__ tasks, DevCtx c) {
     __shared__ __attribute__((aligned(16))) double Ws[MODE == 3 ? POTRF_WIDE_DPP_LDS : (MODE == 1 ? POTRF_WAVE_LDS : NB_IN * LDW)];
     const PotrfTask t = tasks[blockIdx.x];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     potrf_wide_task<SIGNED, MODE>(t, fd, c, Ws);
 }
@@ -2235,6 +2249,7 @@ template <bool SIGNED>
 __global__ __launch_bounds__(256, 2) void k_trsm(const TrsmTask *__restrict__ tasks, DevCtx c) {
     __shared__ __attribute__((aligned(16))) double Wb[2][NB_IN * LDW];           // staged operand: Wb[.][k*LDW + c]; trsm_task_dma: two 64 x 64 images
     const TrsmTask t = tasks[blockIdx.x];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     if (t.nb == NB_OUT) {                                            // (workgroup-uniform)
         if constexpr (TRSM_DMA) trsm_task_dma<SIGNED, 2, false>(t, fd, c, &Wb[0][0], nullptr, TrsmProg{nullptr, nullptr, 0u});
@@ -2249,6 +2264,7 @@ template <bool SIGNED>
 __global__ __launch_bounds__(256) void k_trsm_thin(const TrsmTask *__restrict__ tasks, DevCtx c) {
     __shared__ double Wl[TRSM_THIN_W * TRSM_THIN_W];
     const TrsmTask t = tasks[blockIdx.x];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     const i32 w = t.nb;
     const i32 lda = pld(fd, t.k0);                  // leading dimension of the slice of the packed panel that holds the block column
@@ -2873,6 +2889,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void k_update(const Updat
     // memberwise: a 48-byte struct copy went through scratch memory (and every wave-uniform field of the task into vector registers)
     const UpdateTask *tp = tasks + b;
     const UpdateTask t{tp->front, tp->k0, tp->kw, tp->i0, tp->j0, tp->jlim, tp->beta0, tp->pad1, tp->seg, tp->nsl, 0, 0};
+    if (front_skipped(c, t.front)) return;              // (a split-K part leaves its scratch slot unwritten: the reduction of the same front is skipped too)
     const FrontDesc fd = c.fronts[t.front];
     const bool full = (t.i0 + TILE <= fd.f) && (t.j0 + TILE <= t.jlim) && (t.i0 >= t.j0 + TILE);
 #ifdef UPD_TRACE   /* tools/update_bench.hip: per-workgroup time stamps (100 MHz) and placement */
@@ -2897,6 +2914,7 @@ __global__ __launch_bounds__(256, 4) void k_update64(const UpdateTask *__restric
     __shared__ double lds[4 * UPD_KT * U64_LD];
     const UpdateTask *tp = tasks + blockIdx.x;
     const UpdateTask t{tp->front, tp->k0, tp->kw, tp->i0, tp->j0, tp->jlim, tp->beta0, tp->pad1, tp->seg, tp->nsl, tp->pad2, 0};
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     update_tile64<SIGNED>(t, fd, c, lds);
 }
@@ -2928,6 +2946,7 @@ __device__ __forceinline__ void reduce_part(const UpdateTask t, const int part, 
 }
 __global__ __launch_bounds__(256) void k_update_reduce(const UpdateTask *__restrict__ tasks, DevCtx c) {
     const UpdateTask t = tasks[blockIdx.x / RED_SPLIT];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     reduce_part(t, (int)(blockIdx.x % RED_SPLIT), fd, c);
 }
@@ -3093,6 +3112,16 @@ __global__ __launch_bounds__(256, 2) void k_chain(const ChainArgs a, DevCtx c) {
         if (slot >= (unsigned)a.nitems) return;
         const ChainItem *ip = a.items + slot;
         const ChainItem it{ip->role, ip->task, ip->sub, ip->w0, ip->n0, ip->need0, ip->w1, ip->n1, ip->need1, ip->w2, ip->need2, ip->sig};
+        // Block skip: an item of a skipped front is dropped where it is drawn -- it neither waits nor raises its counter.  Every counter an item waits for
+        // (wait 0 / 1 / 2, and the diagonal block's progress word of an early-entry strip) belongs to the item's OWN front, so the only items that could wait
+        // for the counter left at zero are items of the same front, and those are dropped here as well: a masked update never waits for a skipped item.
+        // (Raising the counter instead would publish "done" for work that was not done and cost a release fence per dropped item for nobody's benefit;
+        // the counters are zeroed at the start of every update, so nothing is left behind.)
+        if (c.front_skip != nullptr) {
+            const i32 fr = (it.role == CR_UPDATE) ? a.upd[it.task].front : (it.role == CR_POTRF) ? a.potrf[it.task].front :
+                           (it.role == CR_TRSM) ? a.trsm[it.task].front : a.red[it.task].front;
+            if (c.front_skip[fr]) continue;                    // (workgroup-uniform; the barrier at the top of the loop orders the next draw)
+        }
         unsigned long long *tr = a.trace ? a.trace + 4 * (size_t)slot : nullptr;
         if (tr && tid == 0) tr[0] = wall_clock64();
         if (tid < 64) {
@@ -3168,6 +3197,7 @@ __global__ __launch_bounds__(256) void k_rhs(i64 m, const i32 *__restrict__ perm
 __global__ __launch_bounds__(256) void k_fwd_gather(const SolveTask *__restrict__ tasks, DevCtx c) {
     if (blockIdx.y) { c.xw += c.xw2; c.uc += c.uc2; }      // second right-hand side of a pair: its copies of xw / uc (one launch for both)
     const SolveTask t = tasks[blockIdx.x];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     if (t.nb == SOLVE_ROWS / 8) {
         // wide fan-in (the root front of a block-angular LP: every linking row collects one entry per diagonal block): the
@@ -3377,6 +3407,7 @@ __device__ __forceinline__ void bwd_diag_solve(const DevCtx &c, const FrontDesc 
 __global__ __launch_bounds__(256) void k_fwd_diag(const SolveTask *__restrict__ tasks, DevCtx c) {
     __shared__ double scratch[FWD_DIAG_SCRATCH];
     const SolveTask t = tasks[blockIdx.x];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     if (threadIdx.x < SOLVE_NB) scratch[threadIdx.x] = (threadIdx.x < t.nb) ? c.xw[fd.col0 + t.k0 + threadIdx.x] : 0.0;
     __syncthreads();
@@ -3392,6 +3423,7 @@ __global__ __launch_bounds__(256) void k_fwd_update(const SolveTask *__restrict_
     __shared__ double ys[SOLVE_NB];
     __shared__ double scratch[FWD_DIAG_SCRATCH];
     const SolveTask t = tasks[blockIdx.x];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     const i32 f = fd.f, ns = fd.ns, nb = t.nb;
     const i32 lda = fd.lda;                         // leading dimension of the panel (>= f, multiple of 16 for large fronts)
@@ -3445,6 +3477,7 @@ __global__ __launch_bounds__(256, 4) void k_bwd_update(const SolveTask *__restri
     __shared__ double scratch[FWD_DIAG_SCRATCH];
     __shared__ double tacc[SOLVE_NB];       // running sums per column (a column belongs to one wave)
     const SolveTask t = tasks[blockIdx.x];
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     const i32 ns = fd.ns, nb = t.nb, nrows = t.slot;
     const i32 lda = fd.lda;                         // leading dimension of the panel (>= f, multiple of 16 for large fronts)
@@ -3725,7 +3758,7 @@ __global__ __launch_bounds__(256, WS ? (NR == 1 ? 3 : 2) : (NR == 1 ? 4 : 3)) vo
         const int lane = threadIdx.x & 63;
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         const SolveTask ts = a.small[(i64)t.k0 * 4 + wave];
-        if (ts.front < 0) return;
+        if (ts.front < 0 || front_skipped(c, ts.front)) return;
         const FrontDesc fs = c.fronts[ts.front];
         const bool few = fs.ns <= 4 && !c.small_full;
 #pragma unroll
@@ -3736,6 +3769,7 @@ __global__ __launch_bounds__(256, WS ? (NR == 1 ? 3 : 2) : (NR == 1 ? 4 : 3)) vo
         }
         return;
     }
+    if (front_skipped(c, t.front)) return;                       // its hand-over words stay at the sentinel: only items of the same tree poll them, all skipped
     const FrontDesc fd = c.fronts[t.front];
     if (t.slot) fwd_sweep_item<true, NR>(t, fd, c, a, scratch);         // workgroup-uniform
     else fwd_sweep_item<false, NR>(t, fd, c, a, scratch);
@@ -3759,7 +3793,7 @@ __global__ __launch_bounds__(256, NR == 1 ? 3 : 2) void k_bwd_sweep(const SolveT
     const SolveTask t = tasks[s_item];
     if (WS && t.nslot == -2) {                                   // (workgroup-uniform) four small fronts of the level, one per wave (see k_fwd_sweep)
         const SolveTask tsm = a.small[(i64)t.k0 * 4 + wave];
-        if (tsm.front < 0) return;
+        if (tsm.front < 0 || front_skipped(c, tsm.front)) return;
         const FrontDesc fs = c.fronts[tsm.front];
         const bool few = fs.ns <= 4 && !c.small_full;
 #pragma unroll
@@ -3770,6 +3804,7 @@ __global__ __launch_bounds__(256, NR == 1 ? 3 : 2) void k_bwd_sweep(const SolveT
         }
         return;
     }
+    if (front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     const i32 f = fd.f, ns = fd.ns, nb = t.nb;
     const i32 *rows = c.rowidx + fd.rowoff;
@@ -3950,7 +3985,7 @@ __global__ __launch_bounds__(256) void k_fwd_small(const SolveTask *__restrict__
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform, and the compiler must know: task, front descriptor and every column base stay in scalar registers)
     const SolveTask t = tasks[(i64)blockIdx.x * 4 + wave];
-    if (t.front < 0) return;
+    if (t.front < 0 || front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     const bool few = fd.ns <= 4 && !c.small_full;      // wave-uniform
     if (few) fwd_small_body<4>(fd, c, lane); else fwd_small_body<SMALL_NS>(fd, c, lane);
@@ -4011,7 +4046,7 @@ __global__ __launch_bounds__(256) void k_bwd_small(const SolveTask *__restrict__
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform, and the compiler must know: task, front descriptor and every column base stay in scalar registers)
     const SolveTask t = tasks[(i64)blockIdx.x * 4 + wave];
-    if (t.front < 0) return;
+    if (t.front < 0 || front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     const bool few = fd.ns <= 4 && !c.small_full;      // wave-uniform
     if (few) bwd_small_body<4>(fd, c, lane); else bwd_small_body<SMALL_NS>(fd, c, lane);
@@ -4259,19 +4294,19 @@ void launch_zero_panels(hipStream_t st, const DevArrays &a, int part) {
 void launch_assemble(hipStream_t st, const DevArrays &a, const double *D, const double *regD, int part) {
     if (a.n_asm > 0)
         hipLaunchKernelGGL(k_assemble, dim3(nblk(a.n_asm, 256)), dim3(256), 0, st, a.n_asm, a.asm_target_small, a.asm_diag,
-                           a.asm_ptr, a.pair_w, a.pair_j, D, regD, a.ctx.Lval, part < 0 ? nullptr : a.asm_upper, part);
+                           a.asm_ptr, a.pair_w, a.pair_j, D, regD, a.ctx.Lval, part < 0 ? nullptr : a.asm_upper, part, a.ctx.front_skip, a.asm_front);
 }
 void launch_single_factor(hipStream_t st, const DevArrays &a) {
     if (a.n_single > 0)
         hipLaunchKernelGGL(k_single_factor, dim3(nblk(a.n_single, 256)), dim3(256), 0, st, a.n_single, a.single_loff, a.single_dinvoff,
-                           a.single_col, a.ctx.Lval, a.ctx.dinv, a.ctx.info, a.ctx.csign);
+                           a.single_col, a.ctx.Lval, a.ctx.dinv, a.ctx.info, a.ctx.csign, a.ctx.front_skip ? a.ctx.front_skip + a.n_fronts : nullptr);
 }
 // The launchers of the per-right-hand-side solve kernels: `nrhs` right-hand sides (1, or the 2 of a pair) in slots 0 .. nrhs - 1 of xw; pointer arrays hold one entry
 // per right-hand side.  Kernels with a grid-y form take both in one launch (grid y = right-hand side), the K2 kernels are launched once each.
 void launch_single_solve(hipStream_t st, const DevArrays &a, int nrhs) {
     if (a.n_single > 0)
         hipLaunchKernelGGL(k_single_solve, dim3(nblk(a.n_single, 256), (unsigned)nrhs), dim3(256), 0, st, a.n_single, a.single_dinvoff, a.single_col,
-                           a.ctx.dinv, a.ctx.xw, a.ctx.xw2);
+                           a.ctx.dinv, a.ctx.xw, a.ctx.xw2, a.ctx.front_skip ? a.ctx.front_skip + a.n_fronts : nullptr);
 }
 // nrhs = 2 (solve schedules only): the two persistent sweep kernels run their two-right-hand-side instances (one pass over L for
 // both), every other solve kernel is launched once per right-hand side (the second on a context whose xw / uc point at the copies)
@@ -4412,6 +4447,19 @@ void launch_tasks(hipStream_t st, const DevArrays &a, const Launch &L, const Swe
     default: break;
     }
 #undef TLPK_LAUNCH_S
+}
+// Block skip: front_skip[s] for the n_fronts fronts and then the singles, from the byte (unit_skip) or the flag (unit_active: LP k's flag of the batch calls'
+// scalar block at unit_active[k * stride], 0 = parked) of the front's unit.  Runs on the stream of the update / solve it serves: the mask is data, not schedule.
+__global__ void k_expand_skip(i64 n, const i32 *__restrict__ front_unit, const unsigned char *__restrict__ unit_skip, const double *__restrict__ unit_active,
+                              int stride, unsigned char *__restrict__ front_skip) {
+    const i64 s = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const i32 u = front_unit[s];
+    front_skip[s] = unit_skip ? (unsigned char)(unit_skip[u] != 0) : (unsigned char)(unit_active[(i64)u * stride] == 0.0);
+}
+void launch_expand_skip(hipStream_t st, const DevArrays &a, const unsigned char *unit_skip, const double *unit_active, int stride) {
+    const i64 n = a.n_fronts + a.n_single;
+    if (n > 0) hipLaunchKernelGGL(k_expand_skip, dim3(nblk(n, 256)), dim3(256), 0, st, n, a.front_unit, unit_skip, unit_active, stride, a.skip_bytes);
 }
 void launch_k2_diag(hipStream_t st, i64 n, const double *theta, const double *regP, double *D2) {
     hipLaunchKernelGGL(k_k2_diag, dim3(nblk(n + 1, 256)), dim3(256), 0, st, n, theta, regP, D2);

@@ -439,7 +439,12 @@ void find_markers(tlpk_handle *h) {
 // turns it off, profile mode and the split-phase (sharded) calls never use it.  The sweep kernels need no per-launch host
 // state (their tickets are reset by the solve's own memset), every pointer in a captured node is either handle-owned or part
 // of the cache key.
-struct GraphKey { int kind; const void *p[8]; bool operator==(const GraphKey &o) const { return kind == o.kind && std::memcmp(p, o.p, sizeof(p)) == 0; } };
+// mask: DevCtx.front_skip as the captured kernels received it (block skip: a schedule captured without a mask must not serve a masked call, and the other way round;
+// the mask's CONTENT is device data the kernels read when they run, so one graph serves every mask)
+struct GraphKey {
+    int kind; const void *p[8]; const void *mask = nullptr;
+    bool operator==(const GraphKey &o) const { return kind == o.kind && mask == o.mask && std::memcmp(p, o.p, sizeof(p)) == 0; }
+};
 
 // Graphs are used for schedules with ONE stream group (general sparse LPs -- the small, launch-bound ones are of this kind; their
 // side-stream fork / join is captured).  Block-angular LPs run two concurrent stream groups + side streams: capturing those four
@@ -1291,12 +1296,126 @@ int tlpk_update_device(tlpk_handle *h, const double *d_theta, const double *d_re
         return update_finish_wait(h);
     }
     // the WHOLE factorisation as one replayed graph
-    const GraphKey key{1, {}};
+    const GraphKey key{1, {}, h->d.ctx.front_skip};
     rc = graph_or_direct(h, key, [&]() { const int q = enq_update_local(h); return q != TLPK_OK ? q : enq_update_finish(h); }, graph_usable(h));
     if (rc != TLPK_OK) return rc;
     h->local_done = true;
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     return update_finish_wait(h);
+}
+
+// ---- block skip (include/tlpk.h: tlpk_block_skip; DESIGN.md section 4b'-s) ----
+extern "C++" {
+int skip_build_units(tlpk_handle *h, const std::vector<i32> &row_unit, const std::vector<i32> &col_unit, i64 nunits, const char *what) {
+    const Symbolic &S = h->S;
+    const bool k2 = S.system == 1;
+    auto bad = [&](const std::string &msg) { h->last_error = std::string(what) + ": " + msg; return TLPK_BADARG; };
+    // unit of every node of the factored matrix (K1: node i = row i; K2: node j < n = column j, node n + i = row i, as batch_owner resolves them)
+    std::vector<i32> node_unit((size_t)S.m, -1);
+    for (i64 v = 0; v < S.m; ++v) {
+        i32 u = -1;
+        if (!k2) u = v < (i64)row_unit.size() ? row_unit[(size_t)v] : -1;
+        else if (v < S.k2_n) u = v < (i64)col_unit.size() ? col_unit[(size_t)v] : -1;
+        else u = v - S.k2_n < (i64)row_unit.size() ? row_unit[(size_t)(v - S.k2_n)] : -1;
+        if (u < 0 || u >= nunits) return bad("node " + std::to_string(v) + " of the factored matrix belongs to no block");
+        node_unit[(size_t)v] = u;
+    }
+    const size_t nf = S.fronts.size(), nsg = S.single_col.size();
+    std::vector<i32> fu(nf + nsg, -1);
+    for (size_t s = 0; s < nf; ++s) {
+        const FrontDesc &fd = S.fronts[s];
+        if (fd.ns <= 0) return bad("front " + std::to_string(s) + " has no pivot column");
+        const i32 u = node_unit[(size_t)S.perm[(size_t)fd.col0]];
+        for (i32 k = 0; k < fd.ns; ++k)
+            if (node_unit[(size_t)S.perm[(size_t)(fd.col0 + k)]] != u) return bad("the pivot columns of front " + std::to_string(s) + " lie in more than one block");
+        for (i32 r = 0; r < fd.f; ++r)
+            if (node_unit[(size_t)S.perm[(size_t)S.rowidx[(size_t)(fd.rowoff + r)]]] != u) return bad("the rows of front " + std::to_string(s) + " lie in more than one block");
+        fu[s] = u;
+    }
+    for (size_t s = 0; s < nf; ++s) {
+        const i32 p = S.fronts[s].parent;
+        if (p >= 0 && fu[(size_t)p] != fu[s]) return bad("front " + std::to_string(s) + " has its parent in another block");
+    }
+    for (size_t i = 0; i < nsg; ++i) fu[nf + i] = fu[(size_t)S.sn_of_col[(size_t)S.single_col[i]]];
+    h->front_unit.swap(fu);
+    h->skip_units = nunits;
+    return TLPK_OK;
+}
+int skip_device_tables(tlpk_handle *h) {
+    if (h->d.skip_bytes) return TLPK_OK;
+    const Symbolic &S = h->S;
+    DevArrays &d = h->d;
+    const i64 before = h->device_bytes;
+    // the front of every assembled entry: the entries of a permuted column are consecutive (one rank: the lists of the analyse phase are the device's).  A table per
+    // permuted column would be smaller, but k_assemble has no column: it would need the entry -> column map, which is this table's size again.
+    std::vector<i32> ef((size_t)d.n_asm);
+    for (i64 kk = 0; kk < S.m && d.n_asm > 0; ++kk) std::fill(ef.begin() + S.Sp[(size_t)kk], ef.begin() + S.Sp[(size_t)kk + 1], S.sn_of_col[(size_t)kk]);
+    i32 *fu = nullptr, *af = nullptr; unsigned char *sb = nullptr, *us = nullptr;
+    int rc;
+    if ((rc = dev_upload(h, &fu, h->front_unit)) != TLPK_OK) return rc;
+    if ((rc = dev_upload(h, &af, ef)) != TLPK_OK) return rc;
+    if ((rc = dev_alloc(h, &sb, (i64)h->front_unit.size())) != TLPK_OK) return rc;
+    if ((rc = dev_alloc(h, &us, h->skip_units)) != TLPK_OK) return rc;
+    HIPCHK(h, hipMemset(sb, 0, std::max<size_t>(h->front_unit.size(), 1)));
+    d.n_fronts = (i64)S.fronts.size();
+    d.front_unit = fu; d.asm_front = af; d.skip_bytes = sb; d.unit_skip = us;
+    h->skip_dev_bytes = h->device_bytes - before;
+    return TLPK_OK;
+}
+int skip_from_flags(tlpk_handle *h, const double *d_flag, int stride) {
+    if (int rc = skip_device_tables(h)) return rc;
+    launch_expand_skip(h->stream, h->d, nullptr, d_flag, stride);
+    h->d.ctx.front_skip = h->d.skip_bytes;
+    return TLPK_OK;
+}
+void skip_off(tlpk_handle *h) { h->d.ctx.front_skip = nullptr; }
+}  // extern "C++"
+
+int tlpk_block_skip(tlpk_handle *h, const uint8_t *skip, int64_t nblocks) {
+    if (!h) return TLPK_BADARG;
+    const Symbolic &S = h->S;
+    auto bad = [&](const char *msg) { h->last_error = std::string("tlpk_block_skip: ") + msg; return TLPK_BADARG; };
+    const char *why = nullptr;
+    if (!h->sub.empty()) why = "a multi-device handle";
+    else if (h->opt.nranks > 1) why = "a sharded handle";
+    else if (S.dense_matrix) why = "a dense-matrix handle";
+    else if (h->krylov) why = "a matrix-free (Krylov) handle";
+    else if (S.n_dense > 0) why = "a handle with dense columns (dense_cols)";
+    if (why) { h->last_error = std::string("tlpk_block_skip: ") + why + " cannot skip blocks (single-device direct handles, K1 or K2, only)"; return TLPK_BADARG; }
+    if (h->refine_steps > 0) return bad("refine_steps > 0: the norms of the refinement run over all rows");
+    if (ipm_is_batch(h)) return bad("the handle is batch-loaded: the batch owns the mask (tlpk_ipm_batch_skip)");
+    if (h->row_block_copy.empty()) return bad("the handle has no row_block: there are no blocks to skip");
+    for (i64 b : h->row_block_copy) if (b < 0) return bad("the handle has linking rows: the root front joins every block");
+    if (nblocks != (int64_t)S.nblocks) { h->last_error = "tlpk_block_skip: nblocks must be the handle's n_blocks = " + std::to_string(S.nblocks); return TLPK_BADARG; }
+    if (h->front_unit.empty()) {
+        std::vector<i32> ru(h->row_block_copy.begin(), h->row_block_copy.end()), cu;
+        if (S.system == 1) {
+            // K2: the columns of S.Ap are the entries of A as pairs (variable node j, constraint node n + i): a column takes the block of its rows
+            cu.assign((size_t)S.k2_n, -1);
+            for (i64 p = 0; p < S.n; ++p) {
+                i64 j = -1, i = -1;
+                for (i64 q = S.Ap[(size_t)p]; q < S.Ap[(size_t)p + 1]; ++q) { const i64 v = S.Ai[(size_t)q]; if (v < S.k2_n) j = v; else i = v - S.k2_n; }
+                if (j < 0 || i < 0 || i >= (i64)ru.size()) continue;
+                if (cu[(size_t)j] >= 0 && cu[(size_t)j] != ru[(size_t)i]) return bad("a column of A spans two blocks");
+                cu[(size_t)j] = ru[(size_t)i];
+            }
+        }
+        if (int rc = skip_build_units(h, ru, cu, S.nblocks, "tlpk_block_skip")) return rc;
+    }
+    if (!h->has_device) return TLPK_NO_DEVICE;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->root_pending) (void)update_async_wait(h);
+    if (!skip) { skip_off(h); h->skip_host.clear(); return TLPK_OK; }
+    if (int rc = skip_device_tables(h)) return rc;
+    // the earlier work of the handle has read the old mask before the new one lands: both travel on the handle's stream
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->d.unit_skip, skip, (size_t)nblocks, hipMemcpyHostToDevice));
+    launch_expand_skip(h->stream, h->d, h->d.unit_skip, nullptr, 0);
+    HIPCHK(h, hipGetLastError());
+    h->d.ctx.front_skip = h->d.skip_bytes;
+    h->skip_host.resize(h->front_unit.size());
+    for (size_t s = 0; s < h->front_unit.size(); ++s) h->skip_host[s] = skip[h->front_unit[s]] != 0;
+    return TLPK_OK;
 }
 
 // Host-pointer entry points: the caller's vectors are ordinary pageable memory (Julia arrays, KKT.jl:83,100).  They go through pinned
@@ -1558,7 +1677,7 @@ static int solve_finish(tlpk_handle *h, const SolveIo &io) {
 // one whole solve or pair (both halves) through the graph cache, keyed by its pointers (kind 2: a solve, 3: a pair)
 static int solve_whole(tlpk_handle *h, const SolveIo &io) {
     if (int rc = solve_begin(h)) return rc;
-    GraphKey key{io.nrhs == 2 ? 3 : 2, {io.dx[0], io.dy[0], io.xip[0], io.xid[0]}};
+    GraphKey key{io.nrhs == 2 ? 3 : 2, {io.dx[0], io.dy[0], io.xip[0], io.xid[0]}, h->d.ctx.front_skip};
     if (io.nrhs == 2) { key.p[4] = io.dx[1]; key.p[5] = io.dy[1]; key.p[6] = io.xip[1]; key.p[7] = io.xid[1]; }
     const int rc = graph_or_direct(h, key, [&]() { const int q = enq_solve_local(h, io); return q != TLPK_OK ? q : enq_solve_finish(h, io); }, graph_usable_solve(h));
     return rc != TLPK_OK ? rc : solve_end(h);
@@ -2727,6 +2846,9 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
     else if (w == "launch_meta") { for (auto *v : {&S.factor_launches, &S.fwd_launches, &S.bwd_launches}) for (auto &L : *v) { tmp.push_back(L.group); tmp.push_back(L.side); tmp.push_back(L.pad); } }
     else if (w == "zero_tasks") from32(S.zero_tasks);
     else if (w == "zero_small") from32(S.zero_small);
+    else if (w == "front_unit") { if (h->front_unit.empty()) tmp.assign(S.fronts.size() + S.single_col.size(), -1); else from32(h->front_unit); }
+    else if (w == "front_skip") tmp.assign(h->skip_host.begin(), h->skip_host.end());
+    else if (w == "skip_bytes") tmp.assign(1, h->skip_dev_bytes);
     else if (w == "singles") {
         tmp = S.single_loff; tmp.insert(tmp.end(), S.single_dinvoff.begin(), S.single_dinvoff.end()); tmp.insert(tmp.end(), S.single_col.begin(), S.single_col.end());
         tmp.push_back(S.n_zero_lower); tmp.push_back(S.spart_len);

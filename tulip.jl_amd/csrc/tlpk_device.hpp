@@ -26,6 +26,7 @@ struct DevCtx {
     const i32 *upd_seg;    // K-segment lists of the update tasks (UpdateTask.seg)
     int small_full;        // TLPK_SMALL_FULL=1 (debugging): the small-front solve kernels always take their (16 columns, 256 rows) body
     i64 xw2, uc2;          // two-right-hand-side solves: the second rhs / solution at xw + xw2, its contribution vectors at uc + uc2
+    const unsigned char *front_skip;   // block skip (tlpk_block_skip / tlpk_ipm_batch_skip): nullptr = no mask; else != 0 per front (then per single) that this update / solve leaves out
 };
 
 // per-launch arguments of the persistent sweep kernels
@@ -83,6 +84,11 @@ struct DevArrays {
     unsigned long long *sweep_tickets = nullptr;      // one counter per sweep launch of the schedules, stored right in front of ...
     double *sweep_xh = nullptr;                       // ... the hand-over words: [0, m) forward sweep, [m, 2m) backward sweep
     i64 sweep_reset_bytes = 0, sweep_reset_bytes2 = 0;   // tickets + hand-over words (of one / two right-hand sides): one hipMemsetAsync(0xFF) per solve
+    // block skip, allocated by the first mask (tlpk_api.cpp: skip_tables): unit of every front and then of every single; the front of every assembled entry
+    // (k_assemble works per entry); the storage ctx.front_skip points at while a mask is in force; the per-unit bytes of tlpk_block_skip
+    i64 n_fronts = 0;
+    i32 *front_unit = nullptr, *asm_front = nullptr;
+    unsigned char *skip_bytes = nullptr, *unit_skip = nullptr;
 };
 
 void launch_compute_d(hipStream_t st, i64 n, const double *theta, const double *regP, double *D);
@@ -91,6 +97,8 @@ void launch_assemble(hipStream_t st, const DevArrays &a, const double *D, const 
 void launch_zero_panels(hipStream_t st, const DevArrays &a, int part = -1);
 void launch_tasks(hipStream_t st, const DevArrays &a, const Launch &L, const SweepArgs *sw = nullptr, int nrhs = 1);
 void launch_single_factor(hipStream_t st, const DevArrays &a);
+// a.skip_bytes from the units' bytes (unit_skip, != 0 = skipped) or from the units' flags (unit_active[k * stride], 0.0 = skipped); one of the two is null
+void launch_expand_skip(hipStream_t st, const DevArrays &a, const unsigned char *unit_skip, const double *unit_active, int stride);
 // The per-right-hand-side kernels of a solve: nrhs = 1, or 2 for a pair (ONE launch each where the kernel has a grid-y form, grid y = right-hand side; slots
 // 0 .. nrhs - 1 of xw); the pointer arrays hold nrhs entries.  dy_shared / local_only: shards of a multi-device handle publishing into the lead's vectors (nrhs = 1)
 void launch_single_solve(hipStream_t st, const DevArrays &a, int nrhs = 1);

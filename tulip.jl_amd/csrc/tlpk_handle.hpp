@@ -110,10 +110,26 @@ struct tlpk_handle {
     i64 krylov_chunk0 = 4, krylov_chunk_max = 32;   // iterations enqueued before the first look at the outcome / at most between two looks (TLPK_CG_CHUNK=first,max)
     i64 krylov_iters = 0, krylov_iters_total = 0, krylov_converged = 0, krylov_launches = 0, krylov_unsolved = 0;
     double krylov_resid0 = 0, krylov_resid = 0;
+    // block skip (tlpk_block_skip / tlpk_ipm_batch_skip; tlpk_api.cpp: skip_*): units are the blocks of row_block, or the LPs of a batch-loaded handle
+    std::vector<i32> front_unit;        // unit of every front, then of every single (the order of S.single_col); empty = not built yet
+    i64 skip_units = 0;                 // number of units the table was built for
+    bool skip_units_batch = false;      // ... and whether they are the LPs of the batch (tlpk_ipm_batch_skip) or the blocks of row_block (tlpk_block_skip)
+    std::vector<unsigned char> skip_host;   // tlpk_block_skip: the bytes in force per front and then per single; empty = no mask
+    i64 skip_dev_bytes = 0;             // device memory of the tables (tlpk_symbolic_get "skip_bytes")
+    bool batch_skip = false;            // tlpk_ipm_batch_skip(h, 1)
     std::string last_error;
 };
+// tlpk_api.cpp, block skip.  skip_build_units: the front_unit table from the unit of every row and column of the caller's A (a column's unit is only read for
+// K2), verified -- TLPK_BADARG with a sentence and nothing changed if a front is not contained in one unit.  skip_device_tables: the device copies, once.
+// skip_from_flags: the mask of the NEXT update / solves from per-unit flags in device memory (flag[k * stride] == 0.0 -> unit k is skipped), enqueued on the
+// handle's stream; skip_off: no mask (the tables stay)
+int skip_build_units(tlpk_handle *h, const std::vector<i32> &row_unit, const std::vector<i32> &col_unit, i64 nunits, const char *what);
+int skip_device_tables(tlpk_handle *h);
+int skip_from_flags(tlpk_handle *h, const double *d_flag, int stride);
+void skip_off(tlpk_handle *h);
 
 void ipm_free(tlpk_handle *h);          // tlpk_ipm.cpp
+bool ipm_is_batch(const tlpk_handle *h);   // tlpk_ipm.cpp: the handle holds a stack of LPs (tlpk_ipm_load_batch)
 int sync_host_values(tlpk_handle *h);   // tlpk_api.cpp: S.Ax <- the device copy after a tlpk_set_values*_device
 // tlpk_api.cpp, for tlpk_ipm_batch_refill: the refresh of tlpk_set_values restricted to the LPs of a stack whose flag is set (d_flag[k * stride] != 0; d_lp_of: the LP of
 // every entry of nzval; ranges: (lo, hi) pairs, the entries of nzval that are read).  Enqueued on the handle's stream.

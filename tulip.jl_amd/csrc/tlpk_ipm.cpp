@@ -165,6 +165,7 @@ static void dense_products(tlpk_handle *c, bool cols, bool rows) {
     if (rows) { const double *x[1] = {v.x}, *none[1] = {nullptr}; double *o[1] = {const_cast<double *>(v.ax)}; launch_dense_gemv_n(c->stream, c->d, nullptr, x, none, o, 1); }
 }
 
+bool ipm_is_batch(const tlpk_handle *h) { return h && h->ipm && h->ipm->bat; }
 void ipm_free(tlpk_handle *h) {
     if (!h || !h->ipm) return;
     if (h->ipm->h_out) hipHostFree(h->ipm->h_out);
@@ -870,6 +871,13 @@ i64 batch_owner(const tlpk_handle *h, const IpmBatchState &bs, i64 col) {
     if (old < 0 || old >= off->back()) return -1;
     return (i64)(std::upper_bound(off->begin(), off->end(), old) - off->begin()) - 1;
 }
+// tlpk_ipm_batch_skip: the update / the solves enqueued while a MaskScope lives leave out the LPs whose flag in the call's scalar block is 0 -- the copy
+// batch_scalars has just enqueued, expanded per front on the same stream; no mask is in force once the scope ends
+struct MaskScope {
+    tlpk_handle *h; int rc = TLPK_OK;
+    MaskScope(tlpk_handle *h_, IpmBatchState &bs) : h(h_) { if (h->batch_skip) rc = skip_from_flags(h, bs.d_sc + (IPM_BSC - 1), IPM_BSC); }
+    ~MaskScope() { skip_off(h); }
+};
 // step.jl:232-246 for one LP, from the six sums of the pre / dots kernels
 inline void newton_scalars(const double *q, double tau, double kappa, double h0, double xi_g, double xi_tk, double &dtau, double &dkappa) {
     const double xi_g_ = xi_g + xi_tk / tau - q[0] + q[1] - q[2] - q[3];
@@ -996,6 +1004,7 @@ int tlpk_ipm_load_batch(tlpk_handle *h, int64_t nlp, const int64_t *row_off, con
         }();
     }
     if (rc != TLPK_OK) ipm_free(h);
+    else { skip_off(h); h->skip_host.clear(); }      // the batch owns the mask from here on: one that tlpk_block_skip set before the load is lifted
     return rc;
 }
 
@@ -1032,9 +1041,37 @@ int tlpk_ipm_batch_factor(tlpk_handle *h, const uint8_t *active, const double *r
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q == 0 ? regP[k] : (q == 1 ? regD[k] : 0.0); })) return rc;
     ipmb_launch_theta(h->stream, h->ipm->v, bs.B, h->d_theta, h->d_regP, h->d_regD);
+    MaskScope mask(h, bs);
+    if (mask.rc != TLPK_OK) return mask.rc;
     const int rc = tlpk_update_device(h, h->d_theta, h->d_regP, h->d_regD);
     if (rc == TLPK_NOT_POSDEF) *fail_lp = batch_owner(h, bs, h->fail_col);
     return rc;
+}
+
+int tlpk_ipm_batch_skip(tlpk_handle *h, int on) {
+    if (!h) return TLPK_BADARG;
+    if (!ipm_is_batch(h)) { h->last_error = "tlpk_ipm_batch_skip: the handle is not batch-loaded (tlpk_ipm_load_batch)"; return TLPK_BADARG; }
+    if (h->refine_steps > 0) { h->last_error = "tlpk_ipm_batch_skip: refine_steps > 0: the norms of the refinement run over all rows"; return TLPK_BADARG; }
+    if (!on) { h->batch_skip = false; return TLPK_OK; }
+    const IpmBatchState &bs = *h->ipm->bat;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->front_unit.empty() || !h->skip_units_batch) {
+        // (a table that tlpk_block_skip built before the load names the blocks of row_block, which need not be the LPs: rebuilt, and its device copy refreshed)
+        std::vector<i32> ru((size_t)bs.row_off.back()), cu((size_t)bs.col_off.back());
+        for (i64 k = 0; k < bs.nlp; ++k) {
+            std::fill(ru.begin() + bs.row_off[(size_t)k], ru.begin() + bs.row_off[(size_t)k + 1], (i32)k);
+            std::fill(cu.begin() + bs.col_off[(size_t)k], cu.begin() + bs.col_off[(size_t)k + 1], (i32)k);
+        }
+        if (int rc = skip_build_units(h, ru, cu, bs.nlp, "tlpk_ipm_batch_skip")) return rc;
+        h->skip_units_batch = true;
+        if (h->d.front_unit) {
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            HIPCHK(h, hipMemcpy(h->d.front_unit, h->front_unit.data(), h->front_unit.size() * sizeof(i32), hipMemcpyHostToDevice));
+        }
+    }
+    if (int rc = skip_device_tables(h)) return rc;
+    h->batch_skip = true;
+    return TLPK_OK;
 }
 
 /* tlpk_ipm_hsolve_newton per LP: sc[8 k ..] and out[4 k ..] in its layouts; inactive LPs: out = 0 */
@@ -1048,7 +1085,11 @@ int tlpk_ipm_batch_hsolve_newton(tlpk_handle *h, const uint8_t *active, const do
     if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q < 3 ? sc[8 * k + 5 + q] : 0.0; })) return rc;      // eta, gamma mu, delta
     ipmb_launch_hrhs(h->stream, s.v, bs.B);
     ipmb_launch_newton_pre(h->stream, s.v, dst, bs.B, 0, bs.partials[0]);
-    int rc = tlpk_solve2_device(h, bs.sx[0], bs.sy[0], s.v.b, s.v.hxid, bs.sx[1], bs.sy[1], s.v.xip, s.v.xid);
+    int rc;
+    {
+        MaskScope mask(h, bs);
+        rc = mask.rc != TLPK_OK ? mask.rc : tlpk_solve2_device(h, bs.sx[0], bs.sy[0], s.v.b, s.v.hxid, bs.sx[1], bs.sy[1], s.v.xip, s.v.xid);
+    }
     if (rc != TLPK_OK) return rc;
     ipmb_launch_take(h->stream, s.v.hx, s.v.hy, bs.sx[0], bs.sy[0], bs.B);      // an inactive LP keeps its h-system and direction
     ipmb_launch_take(h->stream, dst.x, dst.y, bs.sx[1], bs.sy[1], bs.B);
@@ -1086,7 +1127,11 @@ int tlpk_ipm_batch_newton(tlpk_handle *h, int mode, const uint8_t *active, const
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q < 3 ? sc[8 * k + 5 + q] : 0.0; })) return rc;
     ipmb_launch_newton_pre(h->stream, s.v, acc, bs.B, mode, bs.partials[0]);
-    int rc = tlpk_solve_device(h, bs.sx[0], bs.sy[0], s.v.xip, s.v.xid);
+    int rc;
+    {
+        MaskScope mask(h, bs);
+        rc = mask.rc != TLPK_OK ? mask.rc : tlpk_solve_device(h, bs.sx[0], bs.sy[0], s.v.xip, s.v.xid);
+    }
     if (rc != TLPK_OK) return rc;
     ipmb_launch_take(h->stream, dst.x, dst.y, bs.sx[0], bs.sy[0], bs.B);        // an inactive LP keeps its direction
     ipmb_launch_newton_dots(h->stream, s.v, dst, bs.B, bs.partials[0]);
@@ -1342,7 +1387,11 @@ int tlpk_mpc_batch_newton(tlpk_handle *h, int mode, const uint8_t *active, const
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = batch_scalars(h, bs, active, [&](i64 k, int q) { return q == 0 ? 1.0 : (q == 1 ? gmu[k] : 0.0); })) return rc;      // eta = 1, gamma mu, delta = 0
     ipmb_launch_newton_pre(h->stream, s.v, acc, bs.B, mode, bs.partials[0]);
-    int rc = tlpk_solve_device(h, bs.sx[0], bs.sy[0], s.v.xip, s.v.xid);
+    int rc;
+    {
+        MaskScope mask(h, bs);
+        rc = mask.rc != TLPK_OK ? mask.rc : tlpk_solve_device(h, bs.sx[0], bs.sy[0], s.v.xip, s.v.xid);
+    }
     if (rc != TLPK_OK) return rc;
     ipmb_launch_take(h->stream, dst.x, dst.y, bs.sx[0], bs.sy[0], bs.B);        // an inactive LP keeps its direction
     if ((rc = tlpk_sync(h)) != TLPK_OK) return rc;                              // the kernels above have read this call's first scalars

@@ -72,8 +72,13 @@ def stream_assign(free_slots, slot_keys, queue_keys):
 
 
 class BatchedDeviceHSD:
-    def __init__(self, lps, system="K1", options=None, load=True, **backend_kw):
+    def __init__(self, lps, system="K1", options=None, load=True, skip_parked=False, **backend_kw):
         # options: one Options for every LP, or a sequence with one per LP
+        # skip_parked=True: the blocks of the LPs a call's mask leaves out are skipped inside the factorisation and the sweeps (tlpk_ipm_batch_skip); the results
+        # of optimize() / optimize_stream() do not depend on it, bit for bit.  Silently off on handles with refine > 0 (the refinement's norms run over all rows).
+        # Off by default: with it on, an LP that a tlpk_ipm_batch_factor call left out has NO factor of the parking values -- a caller that drives the
+        # tlpk_ipm_batch_* calls itself and solves such an LP gets unspecified values where it used to get the solve against the parked block (the loops here
+        # never do that; tests/test_ipm_kernels.py's call-by-call sequences do)
         # load=False: stop after the analysis (the stacking can be inspected on a machine without a GPU: device=-1)
         # backend_kw: tlpk.Backend's (device, refine, ordering, ...); row_block defaults to the LP index of every row
         import scipy.sparse as sp
@@ -125,6 +130,17 @@ class BatchedDeviceHSD:
             self._call(self.L.tlpk_ipm_load_batch(self.kkt._h, B, _lib.as_p64(self.row_off), _lib.as_p64(self.col_off),
                                                   _lib.as_pd(self._b), _lib.as_pd(self._c), _lib.as_pd(self._l), _lib.as_pd(self._u)))
             self.loaded = True
+        self._can_skip = self.loaded and int(backend_kw.get("refine", 0)) == 0
+        self.skip_parked = False
+        self.set_skip_parked(skip_parked)
+
+    def set_skip_parked(self, on):
+        """Switch the skipping of parked blocks (tlpk_ipm_batch_skip) on or off between runs; stays off on a handle with refine > 0."""
+        on = bool(on) and self._can_skip
+        if on != self.skip_parked:
+            self._call(self.L.tlpk_ipm_batch_skip(self.kkt._h, int(on)))
+            self.skip_parked = on
+        return self
 
     @staticmethod
     def _stack(vs, lens, what):

@@ -218,6 +218,14 @@ end
 ipm_get!(h::Ptr{Cvoid}, what::Integer, host::Vector{Float64}) =
     GC.@preserve host ccall((:tlpk_ipm_get, libtlpk[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64), h, what, host, length(host))
 
+# Block skip (include/tlpk.h): skip[k] != 0 leaves block k of `row_block` out of the following update! / solve! calls; `nothing` lifts the mask.
+block_skip!(h::Ptr{Cvoid}, skip::Vector{UInt8}) =
+    GC.@preserve skip ccall((:tlpk_block_skip, libtlpk[]), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int64), h, skip, length(skip))
+block_skip!(h::Ptr{Cvoid}, ::Nothing, nblocks::Integer) =
+    ccall((:tlpk_block_skip, libtlpk[]), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int64), h, C_NULL, nblocks)
+# batch-loaded handles: the tlpk_ipm_batch_* / tlpk_mpc_batch_* calls leave the parked LPs' blocks out of their update and solves
+ipm_batch_skip!(h::Ptr{Cvoid}, on::Bool) = ccall((:tlpk_ipm_batch_skip, libtlpk[]), Cint, (Ptr{Cvoid}, Cint), h, on ? 1 : 0)
+
 update(h::Ptr{Cvoid}, θinv::Vector{Float64}, regP::Vector{Float64}, regD::Vector{Float64}) =
     GC.@preserve θinv regP regD ccall((:tlpk_update, libtlpk[]), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, θinv, regP, regD)

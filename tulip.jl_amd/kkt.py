@@ -494,6 +494,25 @@ def set_values(kkt, A_or_data):
     return None
 
 
+def block_skip(kkt, mask):
+    """tlpk_block_skip: leave diagonal blocks out of the following `update` / `solve` calls.  mask: one entry per block of the handle's
+    `row_block` (non-zero = skipped), or None = no mask.  The skipped blocks' panels keep every bit, the other blocks' factor and their
+    segments of dx / dy are those of an unmasked call bit for bit; the skipped segments of dx / dy are unspecified (finite).  A block
+    that is solved must have been factorised by the last update that touched it.  Handles with linking rows, without row_block, with
+    refine > 0, batch-loaded, multi-device, sharded, dense, Krylov or dense_cols handles raise (TLPK_BADARG)."""
+    L = _lib.lib()
+    nb = int(kkt.stats()["n_blocks"])
+    if mask is None:
+        rc = L.tlpk_block_skip(kkt._h, None, nb)
+    else:
+        m8 = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m8.ndim != 1:
+            raise DimensionMismatch("block_skip: the mask is a vector with one entry per block")
+        rc = L.tlpk_block_skip(kkt._h, _lib.as_pu8(m8), m8.shape[0])
+    _raise_for(rc, kkt._h, "block_skip: ")
+    return None
+
+
 def set_values_device(kkt, d_nzval, length):
     """tlpk_set_values_device: the values are in device memory (integer address), the refresh is enqueued on the handle's stream.
     `kkt.A` is NOT updated (the values never reach the host)."""

@@ -118,17 +118,18 @@ class Model:
         return self
 
     @classmethod
-    def optimize_batch(cls, models, slots=None, **kw):
+    def optimize_batch(cls, models, slots=None, skip_parked=False, **kw):
         """`optimize()` of many models in one set of launches (hsd_batch.BatchedDeviceHSD, or mpc_batch.BatchedDeviceMPC where every model
         has algorithm="mpc"): each model is presolved and brought to standard form on its own, ONE batched interior-point run solves the LPs
         presolve did not already finish, each is postsolved, and every model ends as after its own `optimize()`.
         kw: the backend's keywords (system=, device=, ...; default: those of the first model).
+        skip_parked=True: the batch leaves the blocks of finished LPs out of its factorisations and sweeps (the results do not depend on it).
         slots=B: the LPs STREAM through handles of at most B slots (BatchedDeviceHSD.optimize_stream) -- the models that reach the interior-point
         method are grouped by the pattern of their standard form, each group runs through one handle of min(B, group size) slots, and a slot whose
         LP is decided takes the group's next one.  The homogeneous self-dual loop only: algorithm="mpc" with slots raises ValueError."""
         models = list(models)
         if slots is not None:
-            return cls._optimize_stream(models, int(slots), kw)
+            return cls._optimize_stream(models, int(slots), kw, skip_parked)
         algorithms = {mdl.algorithm for mdl in models}
         if len(algorithms) > 1:
             raise ValueError(f"optimize_batch runs ONE interior-point loop for the whole batch: the models mix the algorithms {sorted(algorithms)}")
@@ -151,7 +152,7 @@ class Model:
                 lp_inner = ps.reduced_problem()
             pending.append((mdl, lp_inner))
         if pending:
-            opt = Batched([standard_form(lp) for _, lp in pending], **(kw or models[0].backend_kw)).optimize()
+            opt = Batched([standard_form(lp) for _, lp in pending], skip_parked=skip_parked, **(kw or models[0].backend_kw)).optimize()
             for k, (mdl, lp_inner) in enumerate(pending):
                 res = mdl.inner = InnerResult(str(opt.status[k]), str(opt.primal_status[k]), str(opt.dual_status[k]), opt._get(k, 0), opt._get(k, 5),
                                               opt._get(k, 3), opt._get(k, 4), float(opt.tau[k]), float(opt.primal_objective[k]),
@@ -163,7 +164,7 @@ class Model:
         return models
 
     @classmethod
-    def _optimize_stream(cls, models, slots, kw):
+    def _optimize_stream(cls, models, slots, kw, skip_parked=False):
         from .hsd_batch import BatchedDeviceHSD, pattern_key
         if slots < 1:
             raise ValueError("optimize_batch: slots must be at least 1")
@@ -185,7 +186,7 @@ class Model:
             groups.setdefault(pattern_key(d.A), []).append((mdl, lp_inner, d))
         for group in groups.values():
             nslots = min(slots, len(group))
-            opt = BatchedDeviceHSD([d for _, _, d in group[:nslots]], **(kw or models[0].backend_kw))
+            opt = BatchedDeviceHSD([d for _, _, d in group[:nslots]], skip_parked=skip_parked, **(kw or models[0].backend_kw))
             records = opt.optimize_stream([d for _, _, d in group[nslots:]])
             for (mdl, lp_inner, _), r in zip(group, records):
                 res = mdl.inner = InnerResult(r["status"], r["primal_status"], r["dual_status"], r["xh"], r["yh"], r["zl"], r["zu"], r["tau"],
