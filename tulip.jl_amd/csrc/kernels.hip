@@ -33,6 +33,7 @@
 // subtract / store, without the wave waiting for the old value.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <mutex>
 
@@ -170,6 +171,9 @@ __global__ __launch_bounds__(256) void k_zero_small(const i32 *__restrict__ fron
 // update-matrix columns that land in its range (panel columns before the front is factorised, U
 // columns after its U has been written by k_update).
 // ------------------------------------------------------------------------------------------
+// the task is k_ea_gather's: its front is on the per-column index (workgroup-uniform; row-band tasks, TLPK_EA_BANDS, stay on k_extend_add)
+__device__ __forceinline__ bool ea_task_gathered(const DevCtx &c, const EaTask &t) { return c.eg_front != nullptr && c.eg_front[t.front] != 0 && t.br1 == 0; }
+
 __global__ __launch_bounds__(256) void k_extend_add(const EaTask *__restrict__ tasks, DevCtx c) {
     // Parent column tc of the range is owned by wave (tc - j0) & 3 for the whole kernel: every
     // contribution to a column is applied by the same wave in child order (deterministic) and the
@@ -183,7 +187,7 @@ __global__ __launch_bounds__(256) void k_extend_add(const EaTask *__restrict__ t
     __shared__ int s_ubuf[CB];
     __shared__ unsigned char s_tc[CB][EA_COLS];     // parent column - j0 of the child's columns [q0, q1)
     const EaTask t = tasks[blockIdx.x];
-    if (front_skipped(c, t.front)) return;
+    if (front_skipped(c, t.front) || ea_task_gathered(c, t)) return;
     const FrontDesc fd = c.fronts[t.front];
     const i32 f = fd.f, ns = fd.ns, rs = f - ns;
     double *Up = front_u(c, fd);
@@ -239,6 +243,117 @@ __global__ __launch_bounds__(256) void k_extend_add(const EaTask *__restrict__ t
                     for (int u = 0; u < 4; ++u) if (r + 64 * u < rhi) dst[tg[u]] = d[u] + v[u];
                 }
             }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// extend-add by parent column (TLPK_EA_GATHER), over the same task list as k_extend_add.  The wave that owns parent column tc
+// -- the (tc - j0) & 3 rule -- takes the column's segments of c.eg_cap rows in turn: it brings the stored rows of the segment into its LDS slice,
+// adds the segment's contributors from the per-column index (symbolic.cpp step 13a': child order) and writes the slice back once.  An entry's sum
+// is formed in the order of k_extend_add -- the stored value, then child after child --, so the factor is bit-identical; a parent line is read once
+// and written once instead of once per 8-byte read-modify-write.  The contributors of a segment are known before its first load: the stored rows
+// and the rel / U loads of EG_EB contributors (of at most EG_CH x 64 rows each) are in flight together.  LDS operations of one wave execute in
+// order and nothing crosses waves: no barrier, no flag, no atomic.  A slice is at most 8 KB: LDS leaves room for five workgroups per CU, the
+// launch bounds ask for four (with whole columns of up to 4 569 rows in LDS, one workgroup per CU, the kernel was latency-bound: DESIGN.md section 5c).
+// ------------------------------------------------------------------------------------------
+constexpr int EG_LD = EG_CAP_MAX / 64, EG_EB = 8, EG_CH = 2;
+struct EgBatch { const i32 *rl[EG_EB]; const double *sr[EG_EB]; i32 n[EG_EB]; };
+__device__ __forceinline__ EgBatch eg_entries(const DevCtx &c, const i64 e, const i64 e1) {      // entries [e, e + EG_EB) of a list that ends at e1 > e: n = 0 past the end
+    EgBatch b;
+#pragma unroll
+    for (int u = 0; u < EG_EB; ++u) {
+        const EaGatherEnt g = c.eg_ent[min(e + u, e1 - 1)];
+        b.rl[u] = c.rel + g.rel;
+        b.sr[u] = (((g.src >> EG_UBUF_BIT) & 1) ? c.U1 : c.U0) + (g.src & (((i64)1 << EG_UBUF_BIT) - 1));
+        b.n[u] = (e + u < e1) ? g.n : 0;
+    }
+    return b;
+}
+__device__ __forceinline__ i32 eg_nmax(const EgBatch &b) {
+    i32 m = 0;
+#pragma unroll
+    for (int u = 0; u < EG_EB; ++u) m = max(m, b.n[u]);
+    return m;
+}
+__global__ __launch_bounds__(256, 4) void k_ea_gather(const EaTask *__restrict__ tasks, DevCtx c, int slice_rows) {
+    extern __shared__ double eg_slices[];           // [4 waves][slice_rows], slice_rows = min(c.eg_cap, longest column of the launch)
+    const EaTask t = tasks[blockIdx.x];
+    if (!ea_task_gathered(c, t) || front_skipped(c, t.front)) return;
+    const FrontDesc fd = c.fronts[t.front];
+    const i32 f = fd.f, ns = fd.ns, rs = f - ns, cap = c.eg_cap;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double *slice = eg_slices + (size_t)wave * slice_rows;
+    const i64 *colseg = c.eg_col + c.eg_base[t.front];
+    double *Up = front_u(c, fd);
+    for (i32 tc = t.j0 + wave; tc < t.j1; tc += 4) {
+        double *__restrict__ col0 = (tc < ns) ? pcol(c, fd, tc) : (Up + (i64)(tc - ns) * rs - ns);      // virtual row 0 of the stored column
+        const i64 g0 = colseg[tc], g1 = colseg[tc + 1];
+        for (i64 g = g0; g < g1; ++g) {
+            const i64 e0 = c.eg_ptr[g], e1 = c.eg_ptr[g + 1];
+            if (e0 == e1) continue;                 // nothing lands in this segment
+            const i32 r0 = tc + (i32)(g - g0) * cap, n = min(cap, f - r0);      // rows [r0, r0 + n) of the front
+            if (n > slice_rows) continue;           // (never: the launch's slice is sized by the same rule)
+            double *__restrict__ col = col0 + r0;
+            EgBatch b = eg_entries(c, e0, e1);
+            double cv[EG_LD];
+#pragma unroll
+            for (int u = 0; u < EG_LD; ++u) cv[u] = col[min(lane + 64 * u, n - 1)];
+            bool seeded = false;
+            for (i64 e = e0; e < e1; e += EG_EB) {
+                // rel and U of the whole batch, clamped (a guarded load would wait for its guard): row r of contributor u goes to front row rl[u][r]
+                const bool thin = eg_nmax(b) <= 64 * EG_CH;
+                i32 tg[EG_EB][EG_CH]; double v[EG_EB][EG_CH];
+                if (thin) {
+#pragma unroll
+                    for (int u = 0; u < EG_EB; ++u)
+#pragma unroll
+                        for (int k = 0; k < EG_CH; ++k) {
+                            const i32 ru = max(min(lane + 64 * k, b.n[u] - 1), 0);
+                            tg[u][k] = b.rl[u][ru] - r0; v[u][k] = b.sr[u][ru];
+                        }
+                }
+                if (!seeded) {                      // the stored rows into the slice, behind the first batch's loads
+#pragma unroll
+                    for (int u = 0; u < EG_LD; ++u) if (lane + 64 * u < n) slice[lane + 64 * u] = cv[u];
+                    seeded = true;
+                }
+                EgBatch nb = b;
+                if (e + EG_EB < e1) nb = eg_entries(c, e + EG_EB, e1);      // the next batch's entries come while this one is added
+                __builtin_amdgcn_wave_barrier();
+                if (thin) {
+                    // contributor after contributor (list order); the rows of one contributor are distinct front rows: read all, then write all
+#pragma unroll
+                    for (int u = 0; u < EG_EB; ++u) {
+                        double d[EG_CH];
+#pragma unroll
+                        for (int k = 0; k < EG_CH; ++k) d[k] = slice[tg[u][k]];
+#pragma unroll
+                        for (int k = 0; k < EG_CH; ++k) if (lane + 64 * k < b.n[u]) slice[tg[u][k]] = d[k] + v[u][k];
+                        __builtin_amdgcn_wave_barrier();
+                    }
+                } else {
+                    // a contributor of more than EG_CH x 64 rows in the batch: each in turn, 4 x 64 rows per trip
+                    for (int u = 0; u < EG_EB; ++u) {
+                        const i32 nu = b.n[u];
+                        for (i32 r = lane; r - lane < nu; r += 256) {
+                            i32 tq[4]; double w[4], d[4];
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) { const i32 ru = min(r + 64 * k, nu - 1); tq[k] = b.rl[u][ru] - r0; w[k] = b.sr[u][ru]; }
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) d[k] = slice[tq[k]];
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) if (r + 64 * k < nu) slice[tq[k]] = d[k] + w[k];
+                            __builtin_amdgcn_wave_barrier();
+                        }
+                    }
+                }
+                b = nb;
+            }
+            __builtin_amdgcn_wave_barrier();
+            for (i32 r = lane; r < n; r += 64) col[r] = slice[r];
+            __builtin_amdgcn_wave_barrier();
         }
     }
 }
@@ -4348,7 +4463,19 @@ void launch_tasks(hipStream_t st, const DevArrays &a, const Launch &L, const Swe
         // TLPK_EA_LDS (tuning knob): extra dynamic LDS per workgroup = fewer resident workgroups = a smaller working set of parent
         // columns (the kernel's fabric traffic is parent lines evicted between two children's contributions)
         static const unsigned ea_lds = [] { const char *e = std::getenv("TLPK_EA_LDS"); return e ? (unsigned)std::atoi(e) : 0u; }();
-        hipLaunchKernelGGL(k_extend_add, g, dim3(256), ea_lds, st, a.ea_tasks + L.first, a.ctx); break;
+        // fronts on the per-column index (TLPK_EA_GATHER): both kernels over the same task range, each leaves the other's tasks alone; a kernel
+        // without a task in the launch (counted at create) is not launched
+        bool plain = true;
+        if (a.eg_launch) {
+            const EaGatherLaunch *e = std::lower_bound(a.eg_launch, a.eg_launch + a.n_eg_launch, L.first, [](const EaGatherLaunch &x, i64 first) { return x.first < first; });
+            if (e != a.eg_launch + a.n_eg_launch && e->first == L.first) {
+                if (e->n_gather > 0)
+                    hipLaunchKernelGGL(k_ea_gather, g, dim3(256), (unsigned)(4 * 8 * e->rows), st, a.ea_tasks + L.first, a.ctx, (int)e->rows);
+                plain = e->n_plain > 0;
+            }
+        }
+        if (plain) hipLaunchKernelGGL(k_extend_add, g, dim3(256), ea_lds, st, a.ea_tasks + L.first, a.ctx);
+        break;
     }
     case LK_FRONT_ASSEMBLE:
         hipLaunchKernelGGL(k_front_assemble, g, dim3(256), 0, st, a.fa_tasks + L.first, a.ctx, a.asm_colptr, a.asm_target, a.asm_diag, a.asm_ptr,

@@ -1109,6 +1109,85 @@ int analyse_rank(Symbolic &S, const Options &opt) {
             }
         }, 64);
     }
+    // ---- 13a'. per-column extend-add index (k_ea_gather): the inverse of rel.  A column tc of a selected parent is cut into SEGMENTS of at most
+    // ea_gather_cap rows from its diagonal down (rows [tc + p cap, tc + (p + 1) cap) of the front: what one wave holds in LDS); for every segment the
+    // (child, child column q) pairs with rel[q] == tc that have rows in it, with those rows, children in the order of the child list -- the summation
+    // order of k_extend_add --, so that the wave knows a segment's contributors before its first load.  A segment nothing lands in has no entries and
+    // is neither read nor written.  TLPK_EA_GATHER = 0 | 1 | unset (auto), read per analysis: 1 selects every local parent with at least
+    // TLPK_EA_GATHER_MIN_CHILD children, auto only those of at least EG_AUTO_MIN_F rows that their children fill densely enough (below).
+    // TLPK_EA_GATHER_CAP: rows of a segment.
+    {
+        constexpr i32 EG_AUTO_MIN_F = 2048; constexpr double EG_AUTO_COLS = 4.0, EG_AUTO_FILL = 4.0;
+        int mode = -1; i32 min_child = 16, cap = EG_CAP_MAX;
+        if (const char *e = std::getenv("TLPK_EA_GATHER")) mode = std::atoi(e) != 0;
+        if (const char *e = std::getenv("TLPK_EA_GATHER_MIN_CHILD")) min_child = (i32)std::max(1, std::atoi(e));
+        if (const char *e = std::getenv("TLPK_EA_GATHER_CAP")) cap = (i32)std::max(1, std::min(std::atoi(e), EG_CAP_MAX));
+        S.ea_gather_base.assign((size_t)ns_total, -1);
+        S.ea_gather_col.clear(); S.ea_gather_ptr.clear(); S.ea_gather_ent.clear();
+        S.ea_gather_cap = cap;
+        std::vector<i32> sel;
+        i64 ncol = 0;
+        for (i32 s = 0; s < ns_total && mode != 0; ++s) {
+            const FrontDesc &w = S.fronts[s];
+            if (!S.front_local[s] || S.front_fa[(size_t)s] || w.nchild < min_child) continue;
+            if (mode < 0) {
+                // auto: big parents that many thin children hit all over -- on average at least EG_AUTO_COLS child columns per parent column and one child
+                // entry per EG_AUTO_FILL entries of the parent's lower triangle.  Below that most of a column that is read and written whole receives
+                // nothing, and the scattered adds of k_extend_add move less (measured: DESIGN.md section 5c)
+                double cols = 0, ents = 0;
+                for (i32 t = 0; t < w.nchild; ++t) { const FrontDesc &cd = S.fronts[S.children[w.child_ptr + t]]; const double r = cd.f - cd.ns; cols += r; ents += 0.5 * r * (r + 1); }
+                if (w.f < EG_AUTO_MIN_F || cols < EG_AUTO_COLS * (double)w.f || EG_AUTO_FILL * ents < 0.5 * (double)w.f * (w.f + 1)) continue;
+            }
+            S.ea_gather_base[(size_t)s] = ncol; ncol += w.f + 1;
+            sel.push_back(s);
+        }
+        // per selected front, on the host threads: the first segment of every column (front-relative), entries per segment, the entries
+        struct Part { std::vector<i64> col, ptr; std::vector<EaGatherEnt> ent; };
+        std::vector<Part> parts(sel.size());
+        parallel_for_throw((i64)sel.size(), host_threads((i64)sel.size()), [&](unsigned, i64 k) {
+            const FrontDesc &w = S.fronts[sel[(size_t)k]];
+            Part &P = parts[(size_t)k];
+            P.col.assign((size_t)w.f + 1, 0);
+            for (i32 tc = 0; tc < w.f; ++tc) P.col[(size_t)tc + 1] = P.col[(size_t)tc] + (w.f - tc + cap - 1) / cap;
+            const i64 nseg = P.col[(size_t)w.f];
+            std::vector<std::pair<i64, EaGatherEnt>> tmp;
+            P.ptr.assign((size_t)nseg + 1, 0);
+            for (i32 t = 0; t < w.nchild; ++t) {
+                const i32 c = S.children[w.child_ptr + t];
+                const FrontDesc &cd = S.fronts[c];
+                const i32 rsc = cd.f - cd.ns;
+                const i32 *rel = S.rel.data() + cd.reloff;
+                for (i32 q = 0; q < rsc; ++q) {
+                    const i32 tc = rel[q];
+                    for (i32 ra = q; ra < rsc;) {              // the child's rows [ra, rb) land in segment pc of column tc
+                        const i32 pc = (rel[ra] - tc) / cap;
+                        const i32 rb = (i32)(std::lower_bound(rel + ra, rel + rsc, tc + (pc + 1) * cap) - rel);
+                        const i64 seg = P.col[(size_t)tc] + pc;
+                        tmp.push_back({seg, EaGatherEnt{(cd.uoff + (i64)q * rsc + ra) | ((i64)cd.ubuf << EG_UBUF_BIT), cd.reloff + ra, rb - ra, c}});
+                        P.ptr[(size_t)seg + 1]++;
+                        ra = rb;
+                    }
+                }
+            }
+            for (i64 g = 0; g < nseg; ++g) P.ptr[(size_t)g + 1] += P.ptr[(size_t)g];
+            std::vector<i64> fill(P.ptr.begin(), P.ptr.end() - 1);
+            P.ent.resize(tmp.size());
+            for (const auto &te : tmp) P.ent[(size_t)fill[(size_t)te.first]++] = te.second;      // (stable: child order inside a segment)
+        });
+        i64 nseg = 0, nent = 0;
+        for (const Part &P : parts) { nseg += (i64)P.ptr.size() - 1; nent += (i64)P.ent.size(); }
+        if (!sel.empty()) {
+            S.ea_gather_col.reserve((size_t)ncol); S.ea_gather_ptr.reserve((size_t)nseg + 1); S.ea_gather_ent.reserve((size_t)nent);
+            i64 seg0 = 0, ent0 = 0;
+            for (const Part &P : parts) {
+                for (const i64 v : P.col) S.ea_gather_col.push_back(seg0 + v);
+                for (size_t g = 0; g + 1 < P.ptr.size(); ++g) S.ea_gather_ptr.push_back(ent0 + P.ptr[g]);
+                S.ea_gather_ent.insert(S.ea_gather_ent.end(), P.ent.begin(), P.ent.end());
+                seg0 += (i64)P.ptr.size() - 1; ent0 += (i64)P.ent.size();
+            }
+            S.ea_gather_ptr.push_back(ent0);
+        }
+    }
 
     pt.mark("structural zeros");
     // ---- 13c. structural zeros of the amalgamated fronts.  A merged supernode is stored and factorised as a dense trapezoid, but

@@ -240,6 +240,24 @@ void run_launches(tlpk_handle *h, const std::vector<Launch> &L, size_t from, siz
     join_groups(h);
 }
 
+// The LK_EXTEND_ADD launches that have a task for k_ea_gather (ascending `first`): the tasks of gathered fronts, the tasks that stay on k_extend_add, and the
+// longest segment of the gathered ones = rows of a wave's LDS slice.  The kernels decide by the same rule (kernels.hip: ea_task_gathered).
+std::vector<EaGatherLaunch> eg_count_launches(const Symbolic &S) {
+    std::vector<EaGatherLaunch> out;
+    if (S.ea_gather_ent.empty()) return out;
+    for (const Launch &L : S.factor_launches) {
+        if (L.kind != LK_EXTEND_ADD || L.count <= 0) continue;
+        EaGatherLaunch g{L.first, 0, 0, 1};
+        for (i64 k = L.first; k < L.first + L.count; ++k) {
+            const EaTask &t = S.ea_tasks[(size_t)k];
+            if (S.ea_gather_base[(size_t)t.front] >= 0 && t.br1 == 0) { g.n_gather++; g.rows = std::max(g.rows, std::min(S.fronts[(size_t)t.front].f - t.j0, S.ea_gather_cap)); }
+            else g.n_plain++;
+        }
+        if (g.n_gather > 0) out.push_back(g);
+    }
+    return out;
+}
+
 int upload_all(tlpk_handle *h) {
     Symbolic &S = h->S;
     DevArrays &d = h->d;
@@ -365,6 +383,21 @@ int upload_all(tlpk_handle *h) {
     { i64 *p; UP(p, S.gth_src); d.ctx.gth_src = p; }
     UP(d.fa_tasks, S.fa_tasks);
     UP(d.ea_tasks, S.ea_tasks); UP(d.potrf_tasks, S.potrf_tasks); UP(d.trsm_tasks, S.trsm_tasks);
+    if (!S.ea_gather_ent.empty()) {
+        // per-column extend-add index: the tables, the per-front byte that splits the task list between k_ea_gather and k_extend_add, and per launch how
+        // many tasks each kernel has and the longest segment k_ea_gather holds (its LDS slice)
+        std::vector<unsigned char> gf(S.fronts.size(), 0);
+        for (size_t s = 0; s < gf.size(); ++s) gf[s] = S.ea_gather_base[s] >= 0;
+        { unsigned char *p; UP(p, gf); d.ctx.eg_front = p; }
+        { i64 *p; UP(p, S.ea_gather_base); d.ctx.eg_base = p; }
+        { i64 *p; UP(p, S.ea_gather_col); d.ctx.eg_col = p; }
+        { i64 *p; UP(p, S.ea_gather_ptr); d.ctx.eg_ptr = p; }
+        { EaGatherEnt *p; UP(p, S.ea_gather_ent); d.ctx.eg_ent = p; }
+        d.ctx.eg_cap = S.ea_gather_cap;
+        h->eg_launches = eg_count_launches(S);
+        if (!h->eg_launches.empty()) { d.eg_launch = h->eg_launches.data(); d.n_eg_launch = (i64)h->eg_launches.size(); }
+        else d.ctx.eg_front = nullptr;              // (no launch has a task for it: k_extend_add does everything)
+    }
     UP(d.update_tasks, S.update_tasks); UP(d.reduce_tasks, S.reduce_tasks);
     UP(d.chain_items, S.chain_items); d.n_chain_cnt = S.chain_counters;
     if (S.chain_counters > 0 && (rc = dev_alloc(h, &d.chain_cnt, S.chain_counters)) != TLPK_OK) return rc;
@@ -2780,6 +2813,14 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
     else if (w == "rowidx") from32(S.rowidx);
     else if (w == "rel") from32(S.rel);
     else if (w == "ea_tab") from32(S.ea_tab);
+    // per-column extend-add index: per front the offset of its f + 1 entries of ea_gather_col (-1: not gathered); per column its first segment; per segment its
+    // first entry; (src, rel, n, child) per entry; rows of a segment; (first, tasks of k_ea_gather, tasks of k_extend_add, slice rows) per launch with a gathered task
+    else if (w == "ea_gather_base") tmp = S.ea_gather_base;
+    else if (w == "ea_gather_col") tmp = S.ea_gather_col;
+    else if (w == "ea_gather_ptr") tmp = S.ea_gather_ptr;
+    else if (w == "ea_gather_ent") { for (auto &g : S.ea_gather_ent) { tmp.push_back(g.src); tmp.push_back(g.rel); tmp.push_back(g.n); tmp.push_back(g.child); } }
+    else if (w == "ea_gather_cap") tmp.assign(1, S.ea_gather_cap);
+    else if (w == "ea_gather_launches") { for (auto &g : eg_count_launches(S)) { tmp.push_back(g.first); tmp.push_back(g.n_gather); tmp.push_back(g.n_plain); tmp.push_back(g.rows); } }
     else if (w == "front_eatab") field([](const FrontDesc &f) { return f.eatab; });
     else if (w == "children") from32(S.children);
     else if (w == "depth") from32(S.depth);

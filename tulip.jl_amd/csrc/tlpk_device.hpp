@@ -26,6 +26,9 @@ struct DevCtx {
     const i32 *upd_seg;    // K-segment lists of the update tasks (UpdateTask.seg)
     int small_full;        // TLPK_SMALL_FULL=1 (debugging): the small-front solve kernels always take their (16 columns, 256 rows) body
     i64 xw2, uc2;          // two-right-hand-side solves: the second rhs / solution at xw + xw2, its contribution vectors at uc + uc2
+    // per-column extend-add index (k_ea_gather): eg_front == nullptr: none; else != 0 per front whose extend-add k_ea_gather does (k_extend_add leaves its
+    // tasks alone); eg_col + eg_base[front] = per column of the front its first segment (eg_cap rows each), eg_ptr[segment] = its first entry of eg_ent
+    const unsigned char *eg_front; const i64 *eg_base, *eg_col, *eg_ptr; const EaGatherEnt *eg_ent; i32 eg_cap;
     const unsigned char *front_skip;   // block skip (tlpk_block_skip / tlpk_ipm_batch_skip): nullptr = no mask; else != 0 per front (then per single) that this update / solve leaves out
 };
 
@@ -40,8 +43,13 @@ struct SweepArgs {
     const SolveTask *small = nullptr;       // round 6: the small-front tasks of this direction (items with slot == 2 of a merged launch name groups of four of them)
 };
 
+// an LK_EXTEND_ADD launch as its two kernels see it, counted at create (tlpk_api.cpp: eg_count_launches): tasks of k_ea_gather / of k_extend_add,
+// rows of a wave's LDS slice = the longest segment k_ea_gather holds in the launch
+struct EaGatherLaunch { i64 first; i32 n_gather, n_plain, rows; };
+
 struct DevArrays {
     DevCtx ctx{};
+    const EaGatherLaunch *eg_launch = nullptr; i64 n_eg_launch = 0;   // host memory of the handle, ascending `first`; nullptr: no front is gathered
     i64 m = 0, n = 0;                         // m: order of the factored matrix (K2: n + m; dense columns: m + k), n: columns of the stored matrix
     i64 mu = 0;                               // rows of A as the caller sees them (= m for plain K1): the residual kernels of the refinement
     // K1 with dense columns (tlpk_options.dense_cols): sparse_col[j] = 1 for a column formed into A_s D_s A_s', 0 for a dense one;

@@ -44,6 +44,7 @@ struct tlpk_handle {
     std::vector<std::array<long long, 3>> ev_launch;   // (kind, first, count) of the launch behind each pair (-1: not a schedule launch): TLPK_PROF_DUMP
     size_t ev_used = 0;
     DevArrays d;
+    std::vector<EaGatherLaunch> eg_launches;      // the LK_EXTEND_ADD launches with a gathered front (d.eg_launch points here)
     std::vector<void *> allocs;
     i64 device_bytes = 0;
     double *d_theta = nullptr, *d_regP = nullptr, *d_regD = nullptr, *d_D = nullptr;

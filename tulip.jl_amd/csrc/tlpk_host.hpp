@@ -82,6 +82,13 @@ struct FaTask    { i32 front, bc, br0, br1; };
 constexpr int FA_CW = 4;       // parent columns per tile = the extend-add column range of the large fronts (round 5: 4 x 2304 tall tiles; round 4: 16 x 256)
 constexpr int FA_RB = 576;     // row boundaries per tile: <= FA_RB * FA_CW = 2304 rows (73.7 KB of LDS per tile: two workgroups per CU)
 struct EaTask    { i32 front, j0, j1, bidx, br0, br1, pad0, pad1; };   // rows of the boundaries [br0, br1) only (br1 = 0: all rows): row bands shrink a workgroup's working set of parent lines (TLPK_EA_BANDS)                       // parent columns [j0, j1) = boundaries bidx, bidx + 1 of the front's extend-add ranges
+// per-column extend-add index (k_ea_gather): one contributor of a segment of a parent column tc = the rows of child column q, rel[q] == tc, that land in
+// the segment.  src = offset of the first of them in the child's U (column q) in its ping-pong buffer, bit EG_UBUF_BIT set for U1; rel = offset of their
+// relative indices; n = how many; child = the child front (host side: the export and the tests)
+struct EaGatherEnt { i64 src, rel; i32 n, child; };
+static_assert(sizeof(EaGatherEnt) == 24, "EaGatherEnt layout");
+constexpr int EG_UBUF_BIT = 62;
+constexpr int EG_CAP_MAX = 1024;   // rows of a segment at most = a wave's LDS slice: 4 waves x 1024 doubles = 32 KB per workgroup, four workgroups per CU
 struct SolveTask { i32 front, k0, nb, row0, slot, nslot, pad0, pad1; };
 // sweep items (LK_FWD_SWEEP): k0/nb = first row / rows of the chunk (<= SWEEP_NB pivot rows or <= SOLVE_NB rows below),
 //   slot = 1 pivot block (solve + publish) | 0 rows below, nslot = SWEEP_NB-wide solved blocks to consume (0 .. nslot-1);
@@ -183,6 +190,11 @@ struct Symbolic {
     std::vector<i32> rowidx;               // concatenated front row lists (permuted indices)
     std::vector<i32> rel;                  // concatenated relative indices
     std::vector<i32> ea_tab;               // per child front: lower bounds of its rel list at the parent's extend-add range boundaries
+    // per-column extend-add index (step 13a', TLPK_EA_GATHER): ea_gather_base[s] = -1, or the offset in ea_gather_col of the f + 1 entries of front s, whose
+    // extend-add k_ea_gather does; column tc has the segments [col[tc], col[tc + 1]) of ea_gather_cap rows each (the last one shorter), segment g the
+    // contributors ea_gather_ent[ptr[g] .. ptr[g + 1]) in child order
+    std::vector<i64> ea_gather_base, ea_gather_col, ea_gather_ptr; std::vector<EaGatherEnt> ea_gather_ent;
+    i32 ea_gather_cap = 0;
     std::vector<i64> gth_ptr, gth_src;     // forward gather lists: front row (rowoff + t) -> children's uc entries, in child order
     std::vector<i32> children;             // concatenated child lists
     std::vector<i32> depth;                // depth of each front (roots = 0)
