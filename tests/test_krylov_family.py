@@ -4,7 +4,8 @@ The three methods share one sparse gather (tulip.jl_amd/csrc/krylov_spmv.hpp) an
 five handles -- CG without and with Jacobi, MINRES without and with Jacobi, TriCG -- and the SHA-256 of the bytes of dx and of dy, the iteration count, the
 outcome, the two residual norms (as hex floats) and the launch count of the solve are compared FOR EQUALITY with tests/golden/krylov_family_digests.json.
 There is no tolerance: the digests pin the summation order documented in krylov_reduce.hpp (a fixed shuffle tree per row, column and workgroup, the partial
-sums added in slot order), which is what makes two solves of the same data bit-identical.
+sums added in slot order), which is what makes two solves of the same data bit-identical.  Whether the branches these cases reach compute the RIGHT sums
+is checked in tests/test_krylov_steps.py, against long double after one, two and three iterations.
 
 The fixture is re-recorded only by a change that MEANS to alter arithmetic, or by a compiler change; it names the `hipcc --version` it was recorded with.
 A change that must keep the arithmetic (a refactoring) records it from a build of its PARENT commit -- a copy of the parent tree with this one file added,
