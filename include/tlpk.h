@@ -518,13 +518,21 @@ int tlpk_ipm_batch_skip(tlpk_handle *h, int on);
  *   Checks, in this order (TLPK_BADARG): h NULL; not batch-loaded (the "load first" sentence of the tlpk_ipm_batch_* calls); slots NULL;
  *   nzval given with len != nnzA; the handle is stale after a whole-handle tlpk_set_values* without tlpk_ipm_reload.  A failed check leaves
  *   the handle as it was; no slot selected: TLPK_OK and nothing happens.  K1 and K2; refine_steps and row_block are fine, as at load.
- *   The Mehrotra batch has no refill (its starting point needs a factorisation and two solves per LP).
+ *   The Mehrotra batch refills with the same call; the starting point of the new LPs (a factorisation and two solves per LP) then rides in the
+ *   update and the solves of the running LPs: "Entering LPs" below.
  *   tlpk_ipm_get_lp is tlpk_ipm_get for ONE LP of a batch-loaded handle: LP k's segment of vector `what` (the codes of tlpk_ipm_get), len =
  *   that segment's length.  Refusals as tlpk_ipm_get, plus TLPK_BADARG on a handle that is not batch-loaded, k out of range, a wrong len.
+ *   tlpk_ipm_get_lps reads the records of the LPs that leave in one go: the segments of the nwhat codes what[] (any order, row and column
+ *   vectors mixed) for the nk LPs lp[] (any order, each at most once), LP-major with the codes in the given order, len = the sum of the
+ *   segments' lengths.  One kernel gathers the segments into a device staging buffer (allocated by the first call, grown by a larger one; the
+ *   segment table travels with the launch), one copy brings them to `host`: the bytes are those of the tlpk_ipm_get_lp calls it replaces.
+ *   Refusals as tlpk_ipm_get_lp (NULL pointers and a code outside 0 .. 35 included), plus TLPK_BADARG with a sentence on an LP out of range, an
+ *   LP listed twice, a wrong len.  nk = 0 or nwhat = 0 with len = 0: TLPK_OK, nothing is written.
  * --------------------------------------------------------------------------------------------- */
 int tlpk_ipm_batch_refill(tlpk_handle *h, const uint8_t *slots /*nlp*/, const double *nzval, int64_t len,
                           const double *b, const double *c, const double *l, const double *u);
 int tlpk_ipm_get_lp(tlpk_handle *h, int what, int64_t k, double *host, int64_t len);
+int tlpk_ipm_get_lps(tlpk_handle *h, const int32_t *what, int64_t nwhat, const int64_t *lp, int64_t nk, double *host, int64_t len);
 
 /* ---- Mehrotra predictor-corrector with the iterate in HBM (/root/reference/src/IPM/MPC/MPC.jl:218-410,
  * MPC/step.jl:10-358).  Same vectors as above: tlpk_ipm_load once, tlpk_ipm_residuals with tau = 1 (MPC.jl:101-141),
@@ -554,6 +562,37 @@ int tlpk_mpc_batch_newton(tlpk_handle *h, int mode, const uint8_t *active, const
 int tlpk_mpc_batch_gap(tlpk_handle *h, const uint8_t *active, const double *ap /*nlp*/, const double *ad /*nlp*/, double *out /*2 nlp*/);
 int tlpk_mpc_batch_targets(tlpk_handle *h, const uint8_t *active, const double *par /*4 nlp: ap_, ad_, tmin, tmax*/);
 int tlpk_mpc_batch_advance(tlpk_handle *h, const uint8_t *active, const double *ap /*nlp*/, const double *ad /*nlp*/, double *out /*nlp*/);
+
+/* ---------------------------------------------------------------------------------------------
+ * Entering LPs: the Mehrotra batch as a stream (tulip.jl_amd/mpc_batch.py: BatchedDeviceMPC.refill / optimize_stream; DESIGN.md 4b''-s).
+ * The starting point of tlpk_mpc_batch_start costs one factorisation and two solves.  For an LP that tlpk_ipm_batch_refill has just put into
+ * a slot none of them needs launches of its own: a stacked update factorises every block with that block's own values and a stacked solve
+ * takes a right-hand side per block, so the LP ENTERS through the update, the predictor solve and the corrector solve of the LPs that are
+ * running.  The three calls carry an `enter` mask beside `active`; both are arguments of every call, nothing is remembered on the handle.
+ *   tlpk_mpc_batch_factor_enter  = tlpk_ipm_batch_factor for the active and the parked LPs (neither flag: parked).  An entering LP gets what
+ *     tlpk_mpc_batch_start writes before its update: theta_inv = 0, Rp = 1, xid = hx = 0 on its columns, Rd = 1e-6, xip = hy = 0 on its rows.
+ *     With tlpk_ipm_batch_skip on, the update leaves out the LPs that are neither active nor entering.  *fail_lp may name an entering LP.
+ *   tlpk_mpc_batch_newton_enter  = tlpk_mpc_batch_newton(mode 0 | 1) for the active LPs.  For an entering LP the segment of the right-hand
+ *     side of the call's one stacked solve is (xip, xid) = (0, c) with mode 0, its solution goes to (the accepted direction's x, y); with mode 1
+ *     it is (b, 0) and goes to (x, the accepted direction's y) -- the two solves of tlpk_mpc_batch_start, in its order.  The half of the
+ *     right-hand side that was used is 0 again afterwards.  out of an entering LP is 0.  The solve leaves out the LPs that are neither active
+ *     nor entering (tlpk_ipm_batch_skip).  mode 2: TLPK_BADARG (the centrality correctors keep using tlpk_mpc_batch_newton, which does not
+ *     touch an entering LP).
+ *   tlpk_mpc_batch_enter_finish  runs the rest of the starting point (shifts to positive coordinates, balanced products) on the entering LPs
+ *     alone; out[k] = xl'zl + xu'zu of LP k's starting point, 0 for every other LP.  From the next call on the LP is an active one.
+ * Contracts, bit for bit: with enter all zero each call is its counterpart (outputs and every vector tlpk_ipm_get reads); with every LP
+ * entering and none active, factor_enter, newton_enter(0), newton_enter(1), enter_finish is tlpk_mpc_batch_start (out and the codes 0 - 32);
+ * an entering LP's results do not depend on what the other LPs of the call are or do, nor theirs on it; an LP that is neither active nor
+ * entering keeps every bit of the codes 0 - 32.
+ * Refusals, in this order: TLPK_BADARG with a sentence on a handle that is not loaded or loaded with tlpk_ipm_load, on NULL pointers, after
+ * tlpk_set_values without tlpk_ipm_reload; TLPK_BADARG with a sentence when an LP is both active and entering (and on mode 2); then
+ * TLPK_NO_DEVICE.
+ * --------------------------------------------------------------------------------------------- */
+int tlpk_mpc_batch_factor_enter(tlpk_handle *h, const uint8_t *active, const uint8_t *enter, const double *regP /*nlp*/, const double *regD /*nlp*/,
+                                int64_t *fail_lp);
+int tlpk_mpc_batch_newton_enter(tlpk_handle *h, int mode /*0 | 1*/, const uint8_t *active, const uint8_t *enter, const double *gmu /*nlp*/,
+                                double *out /*2 nlp*/);
+int tlpk_mpc_batch_enter_finish(tlpk_handle *h, const uint8_t *enter, double *out /*nlp: xl'zl + xu'zu*/);
 
 const char *tlpk_strerror(int code);
 const char *tlpk_last_error(const tlpk_handle *h);

@@ -92,6 +92,7 @@ EXPORTS = [
     "tlpk_mpc_batch_start", "tlpk_mpc_batch_newton", "tlpk_mpc_batch_gap", "tlpk_mpc_batch_targets", "tlpk_mpc_batch_advance",
     "tlpk_ipm_batch_refill", "tlpk_ipm_get_lp",
     "tlpk_block_skip", "tlpk_ipm_batch_skip",
+    "tlpk_mpc_batch_factor_enter", "tlpk_mpc_batch_newton_enter", "tlpk_mpc_batch_enter_finish", "tlpk_ipm_get_lps",
 ]
 
 
@@ -216,7 +217,11 @@ def lib():
     L.tlpk_ipm_get_lp.argtypes = [vp, C.c_int, C.c_int64, pd, C.c_int64]
     L.tlpk_block_skip.argtypes = [vp, pu8, C.c_int64]
     L.tlpk_ipm_batch_skip.argtypes = [vp, C.c_int]
-    for name in EXPORTS[-17:]:
+    L.tlpk_mpc_batch_factor_enter.argtypes = [vp, pu8, pu8, pd, pd, p64]
+    L.tlpk_mpc_batch_newton_enter.argtypes = [vp, C.c_int, pu8, pu8, pd, pd]
+    L.tlpk_mpc_batch_enter_finish.argtypes = [vp, pu8, pd]
+    L.tlpk_ipm_get_lps.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64, p64, C.c_int64, pd, C.c_int64]
+    for name in EXPORTS[-21:]:
         getattr(L, name).restype = C.c_int
     for name in ("tlpk_create", "tlpk_update", "tlpk_solve", "tlpk_update_device", "tlpk_solve_device",
                  "tlpk_sync", "tlpk_update_local", "tlpk_root_panel", "tlpk_update_finish",

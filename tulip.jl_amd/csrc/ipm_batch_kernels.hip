@@ -320,6 +320,57 @@ __global__ __launch_bounds__(IPM_T) void k_mpcb_gap(IpmVecs v, IpmDir D, IpmBatc
 }
 
 // ---------------------------------------------------------------------------------------------
+// The Mehrotra stream (tlpk_mpc_batch_factor_enter / _newton_enter): an LP that ENTERS a slot rides in the update and the two solves of the
+// running LPs.  sc[IPM_ROLE] is the LP's role in the call; its `active` flag is 0, so every kernel above skips an entering LP.
+// ---------------------------------------------------------------------------------------------
+// k_ipmb_theta for the active and the parked LPs (sc[0] = regP, sc[1] = regD), k_mpcb_fill for the entering ones
+__global__ void k_mpcb_theta_enter(IpmVecs v, IpmBatch B, double *__restrict__ theta, double *__restrict__ regP, double *__restrict__ regD) {
+    const Seg g = seg_of(B, B.tb);
+    const i64 stride = (i64)g.nbk * blockDim.x, t0 = (i64)g.lb * blockDim.x + threadIdx.x;
+    if (g.sc[IPM_ROLE] == IPM_ENTERING) {                                    // (block-uniform)
+        for (i64 jj = t0; jj < g.nk; jj += stride) { const i64 j = g.c0 + jj; theta[j] = 0.0; regP[j] = 1.0; v.xid[j] = 0.0; v.hx[j] = 0.0; }
+        for (i64 ii = t0; ii < g.mk; ii += stride) { const i64 i = g.r0 + ii; regD[i] = 1e-6; v.xip[i] = 0.0; v.hy[i] = 0.0; }
+        return;
+    }
+    const double rP = g.active ? g.sc[0] : 1.0, rD = g.active ? g.sc[1] : 1.0;
+    for (i64 jj = t0; jj < g.nk; jj += stride) {
+        const i64 j = g.c0 + jj;
+        if (g.active) ipm_theta_col(v, j, theta);
+        else theta[j] = 1.0;
+        regP[j] = rP;
+    }
+    for (i64 ii = t0; ii < g.mk; ii += stride) regD[g.r0 + ii] = rD;
+}
+// the right-hand side of an entering LP's starting solve: mode 0 (0, c) for y, mode 1 (b, 0) for x (MPC.jl:371-377)
+__global__ void k_mpcb_enter_rhs(IpmVecs v, IpmBatch B, int mode) {
+    const Seg g = seg_of(B, B.tb);
+    if (g.sc[IPM_ROLE] != IPM_ENTERING) return;
+    const i64 stride = (i64)g.nbk * blockDim.x, t0 = (i64)g.lb * blockDim.x + threadIdx.x;
+    for (i64 jj = t0; jj < g.nk; jj += stride) { const i64 j = g.c0 + jj; v.xid[j] = mode == 0 ? v.c[j] : 0.0; }
+    for (i64 ii = t0; ii < g.mk; ii += stride) { const i64 i = g.r0 + ii; v.xip[i] = mode == 0 ? 0.0 : v.b[i]; }
+}
+// ... and its solution from the scratch vectors of the call's one solve: mode 0 -> (D0.x, y), mode 1 -> (x, D0.y); the half of the right-hand side that
+// the solve used goes back to 0
+__global__ void k_mpcb_enter_take(IpmVecs v, IpmDir D0, const double *__restrict__ sx, const double *__restrict__ sy, IpmBatch B, int mode) {
+    const Seg g = seg_of(B, B.tb);
+    if (g.sc[IPM_ROLE] != IPM_ENTERING) return;
+    const i64 stride = (i64)g.nbk * blockDim.x, t0 = (i64)g.lb * blockDim.x + threadIdx.x;
+    if (mode == 0) {
+        for (i64 jj = t0; jj < g.nk; jj += stride) { const i64 j = g.c0 + jj; D0.x[j] = sx[j]; v.xid[j] = 0.0; }
+        for (i64 ii = t0; ii < g.mk; ii += stride) { const i64 i = g.r0 + ii; v.y[i] = sy[i]; }
+    } else {
+        for (i64 jj = t0; jj < g.nk; jj += stride) { const i64 j = g.c0 + jj; v.x[j] = sx[j]; }
+        for (i64 ii = t0; ii < g.mk; ii += stride) { const i64 i = g.r0 + ii; D0.y[i] = sy[i]; v.xip[i] = 0.0; }
+    }
+}
+// tlpk_ipm_get_lps: the records of the LPs that leave, gathered for one copy.  blockIdx.x = segment of the table, the blocks of a column of the grid stride over it
+__global__ void k_ipmb_gather_segs(const IpmGatherSeg *__restrict__ tab, double *__restrict__ out) {
+    const IpmGatherSeg s = tab[blockIdx.x];
+    const i64 stride = (i64)gridDim.y * blockDim.x;
+    for (i64 q = (i64)blockIdx.y * blockDim.x + threadIdx.x; q < s.len; q += stride) out[s.dst + q] = s.src[q];
+}
+
+// ---------------------------------------------------------------------------------------------
 void ipmb_launch_finalize(hipStream_t st, const IpmBatch &B, const IpmBlockTab &t, int nsum, int nmax, int nmin, const double *partials, double *out) {
     hipLaunchKernelGGL(k_ipmb_finalize, dim3((unsigned)B.nlp), dim3(64 * (nsum + nmax + nmin)), 0, st, B, t, nsum, nmax, nmin, partials, out);
 }
@@ -368,6 +419,20 @@ void mpcb_launch_targets(hipStream_t st, const IpmVecs &v, const IpmDir &D, cons
 }
 void mpcb_launch_advance(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials) {
     hipLaunchKernelGGL(k_ipmb_advance<true>, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, D, B, partials);
+}
+void mpcb_launch_theta_enter(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD) {
+    hipLaunchKernelGGL(k_mpcb_theta_enter, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, B, theta, regP, regD);
+}
+void mpcb_launch_enter_rhs(hipStream_t st, const IpmVecs &v, const IpmBatch &B, int mode) {
+    hipLaunchKernelGGL(k_mpcb_enter_rhs, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, B, mode);
+}
+void mpcb_launch_enter_take(hipStream_t st, const IpmVecs &v, const IpmDir &D0, const double *sx, const double *sy, const IpmBatch &B, int mode) {
+    hipLaunchKernelGGL(k_mpcb_enter_take, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, D0, sx, sy, B, mode);
+}
+void ipmb_launch_gather_segs(hipStream_t st, const IpmGatherSeg *tab, i64 nseg, i64 maxlen, double *out) {
+    if (nseg < 1) return;
+    const unsigned ny = (unsigned)std::max<i64>(1, std::min<i64>(64, (maxlen + 4 * IPM_T - 1) / (4 * IPM_T)));
+    hipLaunchKernelGGL(k_ipmb_gather_segs, dim3((unsigned)nseg, ny), dim3(IPM_T), 0, st, tab, out);
 }
 
 }  // namespace tlpk

@@ -47,6 +47,9 @@ struct IpmBatchState {
     bool refill_maps = false;
     std::vector<i64> nz_off;
     i32 *d_lp_of = nullptr, *d_ktx_src = nullptr;
+    // tlpk_ipm_get_lps, allocated by its first call and grown by a later, larger one: the device staging of the gathered segments and the segment table (device / pinned)
+    double *d_stage = nullptr; i64 stage_cap = 0;
+    IpmGatherSeg *d_tab = nullptr, *h_tab = nullptr; i64 tab_cap = 0;
 };
 
 // ---- one device or several ---------------------------------------------------------------------------------------------------
@@ -173,6 +176,9 @@ void ipm_free(tlpk_handle *h) {
     if (IpmBatchState *bs = h->ipm->bat) {
         if (bs->h_out) hipHostFree(bs->h_out);
         if (bs->h_sc) hipHostFree(bs->h_sc);
+        if (bs->h_tab) hipHostFree(bs->h_tab);
+        if (bs->d_tab) hipFree(bs->d_tab);
+        if (bs->d_stage) hipFree(bs->d_stage);
         delete bs;
     }
     delete h->ipm;                  // device vectors are in h->allocs
@@ -875,7 +881,7 @@ i64 batch_owner(const tlpk_handle *h, const IpmBatchState &bs, i64 col) {
 // batch_scalars has just enqueued, expanded per front on the same stream; no mask is in force once the scope ends
 struct MaskScope {
     tlpk_handle *h; int rc = TLPK_OK;
-    MaskScope(tlpk_handle *h_, IpmBatchState &bs) : h(h_) { if (h->batch_skip) rc = skip_from_flags(h, bs.d_sc + (IPM_BSC - 1), IPM_BSC); }
+    MaskScope(tlpk_handle *h_, IpmBatchState &bs, int slot = IPM_BSC - 1) : h(h_) { if (h->batch_skip) rc = skip_from_flags(h, bs.d_sc + slot, IPM_BSC); }
     ~MaskScope() { skip_off(h); }
 };
 // step.jl:232-246 for one LP, from the six sums of the pre / dots kernels
@@ -1444,6 +1450,188 @@ int tlpk_mpc_batch_advance(tlpk_handle *h, const uint8_t *active, const double *
     ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 1, 0, 0, bs.partials[0], bs.d_out);
     if (int rc = batch_gather(h, bs, 1)) return rc;
     for (i64 k = 0; k < bs.nlp; ++k) out[k] = bs.h_out[(size_t)k * IPM_SLOTS];
+    return TLPK_OK;
+}
+
+/* ---- the Mehrotra stream (include/tlpk.h, "Entering LPs"; DESIGN.md section 4b''-s) ---------------------------------------------------------
+ * An LP that enters a slot needs the starting point of tlpk_mpc_batch_start: one factorisation and two solves.  A stacked update factorises every
+ * block with that block's own values and a stacked solve takes a right-hand side per block, so the entering LP rides in the update and in the
+ * predictor and corrector solves of the running LPs: the calls below are tlpk_ipm_batch_factor / tlpk_mpc_batch_newton with an `enter` mask beside
+ * `active`.  Only the column kernels of the starting point (tlpk_mpc_batch_enter_finish) are launches of the entering LPs' own. */
+}  // extern "C"
+
+namespace {
+
+// the refusals of the three calls in their order: not loaded / not batch-loaded, NULL pointers, the stale handle, an LP with two roles, no device
+int enter_state(tlpk_handle *h, IpmBatchState *&bs, const char *name, bool null_ptr, const uint8_t *active, const uint8_t *enter) {
+    if (!h) return TLPK_BADARG;
+    if (!h->ipm) { h->last_error = "tlpk_ipm_load_batch has not been called (load first)"; return TLPK_BADARG; }
+    if (!h->ipm->bat) { h->last_error = "the handle holds one LP (tlpk_ipm_load): the tlpk_ipm_batch_* calls need tlpk_ipm_load_batch"; return TLPK_BADARG; }
+    if (null_ptr) { h->last_error = std::string(name) + ": a NULL pointer"; return TLPK_BADARG; }
+    if (h->ipm_stale) {
+        h->last_error = "the matrix values changed (tlpk_set_values) after the LPs were loaded: call tlpk_ipm_reload before the device-resident loops";
+        return TLPK_BADARG;
+    }
+    bs = h->ipm->bat;
+    if (active)
+        for (i64 k = 0; k < bs->nlp; ++k)
+            if (active[k] && enter[k]) { h->last_error = std::string(name) + ": LP " + std::to_string(k) + " is both active and entering"; return TLPK_BADARG; }
+    if (!h->has_device) return TLPK_NO_DEVICE;
+    return TLPK_OK;
+}
+// batch_scalars with the roles: sc(k, q) for q < IPM_ROLE, the role, the `active` flag (0 for an entering LP: the kernels of the running LPs skip it)
+template <class F>
+int role_scalars(tlpk_handle *h, IpmBatchState &bs, const uint8_t *active, const uint8_t *enter, F &&sc) {
+    for (i64 k = 0; k < bs.nlp; ++k) {
+        double *row = bs.h_sc + (size_t)k * IPM_BSC;
+        for (int q = 0; q < IPM_ROLE; ++q) row[q] = sc(k, q);
+        row[IPM_ROLE] = active[k] ? IPM_ACTIVE : (enter[k] ? IPM_ENTERING : IPM_PARKED);
+        row[IPM_BSC - 1] = active[k] ? 1.0 : 0.0;
+    }
+    HIPCHK(h, hipMemcpyAsync(bs.d_sc, bs.h_sc, (size_t)bs.nlp * IPM_BSC * 8, hipMemcpyHostToDevice, h->stream));
+    return TLPK_OK;
+}
+bool any_of(const uint8_t *mask, i64 n) { for (i64 k = 0; k < n; ++k) if (mask[k]) return true; return false; }
+
+}  // namespace
+
+extern "C" {
+
+/* tlpk_ipm_batch_factor with three roles: active (regP[k], regD[k]), entering (the starting matrix: theta_inv = 0, Rp = 1, Rd = 1e-6), parked */
+int tlpk_mpc_batch_factor_enter(tlpk_handle *h, const uint8_t *active, const uint8_t *enter, const double *regP, const double *regD, int64_t *fail_lp) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = enter_state(h, bp, "tlpk_mpc_batch_factor_enter", !active || !enter || !regP || !regD || !fail_lp, active, enter)) return rc;
+    IpmBatchState &bs = *bp;
+    *fail_lp = -1;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = role_scalars(h, bs, active, enter, [&](i64 k, int q) { return q == 0 ? regP[k] : (q == 1 ? regD[k] : 0.0); })) return rc;
+    mpcb_launch_theta_enter(h->stream, h->ipm->v, bs.B, h->d_theta, h->d_regP, h->d_regD);
+    MaskScope mask(h, bs, IPM_ROLE);                                  // parked = neither active nor entering
+    if (mask.rc != TLPK_OK) return mask.rc;
+    const int rc = tlpk_update_device(h, h->d_theta, h->d_regP, h->d_regD);
+    if (rc == TLPK_NOT_POSDEF) *fail_lp = batch_owner(h, bs, h->fail_col);
+    return rc;
+}
+
+/* tlpk_mpc_batch_newton(mode 0 | 1) for the active LPs; the entering LPs take one of the two solves of their starting point from the same stacked solve */
+int tlpk_mpc_batch_newton_enter(tlpk_handle *h, int mode, const uint8_t *active, const uint8_t *enter, const double *gmu, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = enter_state(h, bp, "tlpk_mpc_batch_newton_enter", !active || !enter || !gmu || !out, active, enter)) return rc;
+    if (mode < 0 || mode > 1) { h->last_error = "tlpk_mpc_batch_newton_enter: mode must be 0 or 1 (the centrality correctors go through tlpk_mpc_batch_newton)"; return TLPK_BADARG; }
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm; const i64 nlp = bs.nlp;
+    const IpmDir &acc = s.D[s.cur];
+    const bool entering = any_of(enter, nlp);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = role_scalars(h, bs, active, enter, [&](i64 k, int q) { return q == 0 ? 1.0 : (q == 1 ? gmu[k] : 0.0); })) return rc;      // eta = 1, gamma mu, delta = 0
+    ipmb_launch_newton_pre(h->stream, s.v, acc, bs.B, mode, bs.partials[0]);
+    if (entering) mpcb_launch_enter_rhs(h->stream, s.v, bs.B, mode);
+    int rc;
+    {
+        MaskScope mask(h, bs, IPM_ROLE);
+        rc = mask.rc != TLPK_OK ? mask.rc : tlpk_solve_device(h, bs.sx[0], bs.sy[0], s.v.xip, s.v.xid);
+    }
+    if (rc != TLPK_OK) return rc;
+    ipmb_launch_take(h->stream, acc.x, acc.y, bs.sx[0], bs.sy[0], bs.B);
+    if (entering) mpcb_launch_enter_take(h->stream, s.v, s.D[0], bs.sx[0], bs.sy[0], bs.B, mode);      // D[0]: where tlpk_mpc_batch_start keeps its two halves
+    if ((rc = tlpk_sync(h)) != TLPK_OK) return rc;                              // the kernels above have read this call's first scalars
+    if ((rc = batch_scalars(h, bs, active, [](i64, int) { return 0.0; })) != TLPK_OK) return rc;      // dtau = 0
+    ipmb_launch_newton_post(h->stream, s.v, acc, acc, bs.B, 0, bs.partials[1]);
+    ipmb_launch_finalize(h->stream, bs.B, bs.B.tb, 0, 0, 2, bs.partials[1], bs.d_out);
+    if ((rc = batch_gather(h, bs, 1)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) { const double *q = bs.h_out + (size_t)k * IPM_SLOTS; out[2 * k] = q[0]; out[2 * k + 1] = q[1]; }
+    return TLPK_OK;
+}
+
+/* stages 1 - 4 of tlpk_mpc_batch_start for the entering LPs, whose x, y and the halves in D[0] the two newton_enter calls have written */
+int tlpk_mpc_batch_enter_finish(tlpk_handle *h, const uint8_t *enter, double *out) {
+    IpmBatchState *bp = nullptr;
+    if (int rc = enter_state(h, bp, "tlpk_mpc_batch_enter_finish", !enter || !out, nullptr, enter)) return rc;
+    IpmBatchState &bs = *bp; IpmState &s = *h->ipm; const i64 nlp = bs.nlp;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    const double *q = bs.h_out;
+    // one stage: the kernels select by the flag, which here is `enter`
+    auto stage = [&](int st, auto &&sc, int nsum, int nmin) -> int {
+        if (int r = batch_scalars(h, bs, enter, sc)) return r;
+        mpcb_launch_start(h->stream, s.v, bs.B, st, bs.partials[0]);
+        ipmb_launch_finalize(h->stream, bs.B, bs.B.tc, nsum, 0, nmin, bs.partials[0], bs.d_out);
+        return batch_gather(h, bs, 1);
+    };
+    std::vector<double> a((size_t)nlp), b((size_t)nlp);
+    if ((rc = stage(1, [](i64, int) { return 0.0; }, 0, 2)) != TLPK_OK) return rc;
+    if ((rc = tlpk_sync(h)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) { const double *r = q + (size_t)k * IPM_SLOTS; a[(size_t)k] = 1.0 + std::fmax(0.0, std::fmax(-1.5 * r[0], -1.5 * r[1])); }      // dxs
+    if ((rc = stage(2, [&](i64 k, int slot) { return slot == 0 ? a[(size_t)k] : 0.0; }, 0, 2)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) { const double *r = q + (size_t)k * IPM_SLOTS; a[(size_t)k] = 1.0 + std::fmax(0.0, std::fmax(-1.5 * r[0], -1.5 * r[1])); }      // dzs
+    if ((rc = stage(3, [&](i64 k, int slot) { return slot == 0 ? a[(size_t)k] : 0.0; }, 3, 0)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) {
+        const double *r = q + (size_t)k * IPM_SLOTS;
+        const double mu = r[0];
+        a[(size_t)k] = mu / (2.0 * r[1]); b[(size_t)k] = mu / (2.0 * r[2]);      // ddx, ddz
+    }
+    if ((rc = stage(4, [&](i64 k, int slot) { return slot == 0 ? a[(size_t)k] : (slot == 1 ? b[(size_t)k] : 0.0); }, 1, 0)) != TLPK_OK) return rc;
+    for (i64 k = 0; k < nlp; ++k) out[k] = enter[k] ? q[(size_t)k * IPM_SLOTS] : 0.0;
+    return TLPK_OK;
+}
+
+/* tlpk_ipm_get_lp for several codes and several LPs: one gather kernel into a staging buffer, one copy out.  host: LP-major, the codes in the given order */
+int tlpk_ipm_get_lps(tlpk_handle *h, const int32_t *what, int64_t nwhat, const int64_t *lp, int64_t nk, double *host, int64_t len) {
+    Shards sh;
+    if (int rc = ipm_shards(h, sh, true, true, true)) return rc;
+    if (!host || !what || !lp || nwhat < 0 || nk < 0) return TLPK_BADARG;
+    for (i64 w = 0; w < nwhat; ++w) if (what[w] < 0 || what[w] > 35) return TLPK_BADARG;
+    IpmBatchState *bs = h->ipm->bat;
+    if (!bs) { h->last_error = "tlpk_ipm_get_lps: the handle holds one LP (tlpk_ipm_load): it needs tlpk_ipm_load_batch"; return TLPK_BADARG; }
+    std::vector<char> seen((size_t)bs->nlp, 0);
+    i64 need = 0, maxlen = 0;
+    for (i64 q = 0; q < nk; ++q) {
+        const i64 k = lp[q];
+        if (k < 0 || k >= bs->nlp) { h->last_error = "tlpk_ipm_get_lps: LP " + std::to_string(k) + " of " + std::to_string(bs->nlp); return TLPK_BADARG; }
+        if (seen[(size_t)k]) { h->last_error = "tlpk_ipm_get_lps: LP " + std::to_string(k) + " is listed twice"; return TLPK_BADARG; }
+        seen[(size_t)k] = 1;
+        for (i64 w = 0; w < nwhat; ++w) {
+            const std::vector<i64> &off = ipm_get_is_row(what[w]) ? bs->row_off : bs->col_off;
+            const i64 seg = off[(size_t)k + 1] - off[(size_t)k];
+            need += seg; maxlen = std::max(maxlen, seg);
+        }
+    }
+    if (len != need) { h->last_error = "tlpk_ipm_get_lps: wrong length (the listed segments hold " + std::to_string(need) + " entries)"; return TLPK_BADARG; }
+    const double *src[36];
+    ipm_get_sources(h, src);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (i64 w = 0; w < nwhat; ++w) if (!src[what[w]]) { h->last_error = "tlpk_ipm_get_lps: the handle does not hold that vector"; return TLPK_BADARG; }
+    const i64 nseg = nk * nwhat;
+    if (nseg == 0 || need == 0) return TLPK_OK;
+    if (nseg > ((i64)1 << 30)) { h->last_error = "tlpk_ipm_get_lps: too many segments"; return TLPK_TOO_LARGE; }
+    if (nseg > bs->tab_cap) {
+        if (bs->h_tab) { hipHostFree(bs->h_tab); bs->h_tab = nullptr; }
+        if (bs->d_tab) { hipFree(bs->d_tab); bs->d_tab = nullptr; }
+        bs->tab_cap = 0;
+        const i64 cap = std::max<i64>(nseg, std::min<i64>(bs->nlp * 4, (i64)1 << 20));
+        HIPCHK(h, hipHostMalloc((void **)&bs->h_tab, (size_t)cap * sizeof(IpmGatherSeg), hipHostMallocDefault));
+        HIPCHK(h, hipMalloc((void **)&bs->d_tab, (size_t)cap * sizeof(IpmGatherSeg)));
+        bs->tab_cap = cap;
+    }
+    if (need > bs->stage_cap) {
+        if (bs->d_stage) { hipFree(bs->d_stage); bs->d_stage = nullptr; }
+        bs->stage_cap = 0;
+        HIPCHK(h, hipMalloc((void **)&bs->d_stage, (size_t)need * 8));
+        bs->stage_cap = need;
+    }
+    i64 dst = 0, t = 0;
+    for (i64 q = 0; q < nk; ++q)
+        for (i64 w = 0; w < nwhat; ++w) {
+            const std::vector<i64> &off = ipm_get_is_row(what[w]) ? bs->row_off : bs->col_off;
+            const i64 k = lp[q], seg = off[(size_t)k + 1] - off[(size_t)k];
+            bs->h_tab[t++] = IpmGatherSeg{src[what[w]] + off[(size_t)k], seg, dst};
+            dst += seg;
+        }
+    HIPCHK(h, hipMemcpyAsync(bs->d_tab, bs->h_tab, (size_t)nseg * sizeof(IpmGatherSeg), hipMemcpyHostToDevice, h->stream));
+    ipmb_launch_gather_segs(h->stream, bs->d_tab, nseg, maxlen, bs->d_stage);
+    HIPCHK(h, hipMemcpyAsync(host, bs->d_stage, (size_t)need * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
     return TLPK_OK;
 }
 

@@ -85,5 +85,18 @@ void mpcb_launch_start(hipStream_t st, const IpmVecs &v, const IpmBatch &B, int 
 void mpcb_launch_gap(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
 void mpcb_launch_targets(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
 void mpcb_launch_advance(hipStream_t st, const IpmVecs &v, const IpmDir &D, const IpmBatch &B, double *partials);
+// Mehrotra stream (tlpk_mpc_batch_*_enter): an LP that ENTERS a slot gets its starting point from the update and the two solves the running LPs need anyway.
+// The role of LP k in the call travels in B.sc[k][IPM_ROLE]; an entering LP's `active` flag is 0, so every kernel above skips it.
+constexpr int IPM_ROLE = IPM_BSC - 2;
+constexpr double IPM_PARKED = 0.0, IPM_ACTIVE = 1.0, IPM_ENTERING = 2.0;
+// theta / regP / regD by role: active as ipmb_launch_theta (sc[0] = regP, sc[1] = regD), parked as it parks, entering as mpcb_launch_fill
+void mpcb_launch_theta_enter(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD);
+// entering LPs only.  mode 0: (xip, xid) = (0, c), the solution goes to (D0.x, y); mode 1: (xip, xid) = (b, 0), the solution goes to (x, D0.y).
+// The take puts the half of the right-hand side it used back to 0, as tlpk_mpc_batch_start leaves it.
+void mpcb_launch_enter_rhs(hipStream_t st, const IpmVecs &v, const IpmBatch &B, int mode);
+void mpcb_launch_enter_take(hipStream_t st, const IpmVecs &v, const IpmDir &D0, const double *sx, const double *sy, const IpmBatch &B, int mode);
+// tlpk_ipm_get_lps: segment s of the table is copied to out + dst; blockIdx.x = segment, blockIdx.y strides within it
+struct IpmGatherSeg { const double *src; i64 len, dst; };
+void ipmb_launch_gather_segs(hipStream_t st, const IpmGatherSeg *tab, i64 nseg, i64 maxlen, double *out);
 
 }  // namespace tlpk

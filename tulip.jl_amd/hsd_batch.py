@@ -125,6 +125,7 @@ class BatchedDeviceHSD:
         self.passes = self.refills = 0                                           # optimize_stream: trips round the loop; refill calls, the time inside them and in reading records
         self.refill_seconds = self.record_seconds = 0.0
         self.corrector_rounds = 0
+        self._replaced = {}                                                      # slot -> the matrix values of the LP its present one replaced (`_apply`)
         self.loaded = False
         if load:
             self._call(self.L.tlpk_ipm_load_batch(self.kkt._h, B, _lib.as_p64(self.row_off), _lib.as_p64(self.col_off),
@@ -221,7 +222,9 @@ class BatchedDeviceHSD:
         return (shape, indptr.tobytes(), indices.tobytes())
 
     def _hsd_only(self, what):
-        if type(self).optimize is not BatchedDeviceHSD.optimize:             # (BatchedDeviceMPC: its starting point needs a factorisation and two solves per LP)
+        # a subclass that brings its own loop brings its own stream (BatchedDeviceMPC does: the starting point of an LP that enters a slot, a factorisation
+        # and two solves, rides in the update and the solves of the running LPs); one that does not cannot borrow this one
+        if type(self).optimize is not BatchedDeviceHSD.optimize and type(self).optimize_stream is BatchedDeviceHSD.optimize_stream:
             raise NotImplementedError(f"{what} serves the homogeneous self-dual loop only: {type(self).__name__} has no refill")
 
     def _per_lp(self, options, count, what):
@@ -289,6 +292,8 @@ class BatchedDeviceHSD:
                                    ("l", self._l[cs], vecs[2]), ("u", self._u[cs], vecs[3])):
                 if not same(dst, src):
                     new[name] = True
+                    if name == "A":
+                        self._replaced[k] = dst.copy()
                     dst[:] = src
             self.c0[k] = c0; self.objsense[k] = sense
             sel[k] = 1
@@ -539,7 +544,7 @@ class BatchedDeviceHSD:
     # ---- a batch that keeps going (DESIGN.md section 4b'-r) ----
     def optimize_stream(self, lps, options=None):
         """N LPs through the B slots of this handle: the LPs of the constructor are the first occupants, `lps` is the queue.  When an LP leaves
-        (decided, iteration limit, numerical problem) its record is read through tlpk_ipm_get_lp and, at the top of the next pass, its slot takes
+        (decided, iteration limit, numerical problem) its record is read through tlpk_ipm_get_lps and, at the top of the next pass, its slot takes
         the first LP of the queue whose pattern is the slot's (`stream_assign`; `refill`) while every other slot continues untouched.  The
         schedule is deterministic.  options: for the LPs of the queue (one `Options`, or one per LP; default `Options()`) -- options travel
         with the LP, not with the slot.  IterationsLimit counts per LP, TimeLimit is global.  One pass is one trip round the loop of
@@ -548,18 +553,8 @@ class BatchedDeviceHSD:
         passes (1-based) in which it entered and left.  A queue LP that matches no slot raises ValueError before anything runs."""
         self._hsd_only("optimize_stream")
         B = self.nlp
-        memo = {}
-        queue = [self._stage(lp, f"optimize_stream, LP {q} of the queue", memo) for q, lp in enumerate(lps)]
+        queue, qopts, slot_keys, qkeys = self._stream_queue(lps, options)
         N = len(queue)
-        qopts = self._per_lp(options, N, "optimize_stream options")
-        number = {}                                                          # pattern key -> a small integer: the schedule compares those
-        slot_keys = [number.setdefault(self.slot_key(k), len(number)) for k in range(B)]
-        qkeys = [number.get(st[0], -1) for st in queue]
-        for q, key in enumerate(qkeys):
-            if key < 0:
-                raise ValueError(f"optimize_stream: LP {q} of the queue has the pattern (shape, column pointers, row indices) of no slot")
-        if not self.loaded:
-            raise RuntimeError("BatchedDeviceHSD(load=False): nothing is loaded on the device")
         tstart = time.perf_counter()
         time_limit = min([self.time_limit] + [float(o.TimeLimit) for o in qopts])
         self._call(self.L.tlpk_ipm_reset(self.kkt._h))
@@ -574,11 +569,7 @@ class BatchedDeviceHSD:
         stopped = None
 
         def leave(mask):
-            t0 = time.perf_counter()
-            for k in np.flatnonzero(mask):
-                records[lp_of_slot[k]] = self._record(int(k), entered[k], self.passes)
-                free.add(int(k))
-            self.record_seconds += time.perf_counter() - t0
+            self._leave(mask, records, lp_of_slot, entered, free)
 
         with np.errstate(all="ignore"):
             while True:
@@ -616,14 +607,64 @@ class BatchedDeviceHSD:
                 leave(failed)
                 self.niter[act] += 1
         for q in waiting:                                                    # (only after a global stop: these LPs never ran)
-            zn, zm = np.zeros(len(queue[q][2][1])), np.zeros(len(queue[q][2][0]))
-            records[B + q] = {"status": stopped, "niter": 0, "x": zn, "y": zm, "s": zn, "z_primal": 0.0, "z_dual": 0.0, "primal_status": "Sln_Unknown",
-                              "dual_status": "Sln_Unknown", "rho": (0.0, 0.0, 0.0), "zl": zn, "zu": zn, "xh": zn, "yh": zm, "tau": 1.0, "timers": {},
-                              "slot": None, "entered": None, "left": None, "primal_objective": 0.0, "dual_objective": 0.0}
+            records[B + q] = self._never_ran(queue[q], stopped)
         self._cache = {}
         self.seconds = time.perf_counter() - tstart
         self.records = records
         return records
+
+    def _stream_queue(self, lps, options):
+        """What `optimize_stream` checks before anything runs: the queue staged (`_stage`), its options, and the pattern of every slot and every waiting LP
+        as small integers (the schedule compares those)."""
+        memo = {}
+        queue = [self._stage(lp, f"optimize_stream, LP {q} of the queue", memo) for q, lp in enumerate(lps)]
+        qopts = self._per_lp(options, len(queue), "optimize_stream options")
+        number = {}
+        slot_keys = [number.setdefault(self.slot_key(k), len(number)) for k in range(self.nlp)]
+        qkeys = [number.get(st[0], -1) for st in queue]
+        for q, key in enumerate(qkeys):
+            if key < 0:
+                raise ValueError(f"optimize_stream: LP {q} of the queue has the pattern (shape, column pointers, row indices) of no slot")
+        if not self.loaded:
+            raise RuntimeError(f"{type(self).__name__}(load=False): nothing is loaded on the device")
+        return queue, qopts, slot_keys, qkeys
+
+    @staticmethod
+    def _never_ran(staged, stopped):
+        zn, zm = np.zeros(len(staged[2][1])), np.zeros(len(staged[2][0]))
+        return {"status": stopped, "niter": 0, "x": zn, "y": zm, "s": zn, "z_primal": 0.0, "z_dual": 0.0, "primal_status": "Sln_Unknown",
+                "dual_status": "Sln_Unknown", "rho": (0.0, 0.0, 0.0), "zl": zn, "zu": zn, "xh": zn, "yh": zm, "tau": 1.0, "timers": {},
+                "slot": None, "entered": None, "left": None, "primal_objective": 0.0, "dual_objective": 0.0}
+
+    gather_records = True                                                    # the records of the LPs that leave in one pass: one tlpk_ipm_get_lps (False: four tlpk_ipm_get_lp per LP)
+
+    def _leave(self, mask, records, lp_of_slot, entered, free):
+        """The LPs of `mask` leave in this pass: their records are read, their slots are free."""
+        ks = [int(k) for k in np.flatnonzero(mask)]
+        if not ks:
+            return
+        t0 = time.perf_counter()
+        vecs = self._get_lps(ks, (0, 3, 4, 5)) if self.gather_records else [None] * len(ks)
+        for k, vec in zip(ks, vecs):
+            records[lp_of_slot[k]] = self._record(k, entered[k], self.passes, vec)
+            free.add(k)
+        self.record_seconds += time.perf_counter() - t0
+
+    def _get_lps(self, ks, codes):
+        """[{code: segment}] for the LPs `ks` through ONE tlpk_ipm_get_lps: one gather kernel, one copy."""
+        lens = [[int((self.row_off if what in _lib.IPM_GET_ROWS else self.col_off)[k + 1] - (self.row_off if what in _lib.IPM_GET_ROWS else self.col_off)[k])
+                 for what in codes] for k in ks]
+        buf = np.empty(sum(sum(row) for row in lens))
+        what, lp = np.array(codes, dtype=np.int32), np.array(ks, dtype=np.int64)
+        self._call(self.L.tlpk_ipm_get_lps(self.kkt._h, what.ctypes.data_as(C.POINTER(C.c_int32)), what.shape[0], _lib.as_p64(lp), lp.shape[0],
+                                           _lib.as_pd(buf), buf.shape[0]))
+        out, pos = [], 0
+        for row in lens:
+            vec = {}
+            for what_, length in zip(codes, row):
+                vec[what_] = buf[pos:pos + length].copy(); pos += length
+            out.append(vec)
+        return out
 
     def _get_lp(self, k, what):
         """`_get` through tlpk_ipm_get_lp: LP k's segment alone crosses the bus."""
@@ -632,8 +673,8 @@ class BatchedDeviceHSD:
         self._call(self.L.tlpk_ipm_get_lp(self.kkt._h, what, k, _lib.as_pd(v), v.shape[0]))
         return v
 
-    def _record(self, k, entered, left):
-        vec = {what: self._get_lp(k, what) for what in (0, 3, 4, 5)}
+    def _record(self, k, entered, left, vec=None):
+        vec = vec or {what: self._get_lp(k, what) for what in (0, 3, 4, 5)}
         rec = self._solution(k, None, lambda _k, what: vec[what])
         rec.update(zl=vec[3], zu=vec[4], xh=vec[0], yh=vec[5], tau=float(self.tau[k]), timers=self.timers_of(k), slot=k, entered=entered, left=left,
                    primal_objective=float(self.primal_objective[k]), dual_objective=float(self.dual_objective[k]))

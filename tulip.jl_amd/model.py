@@ -126,10 +126,14 @@ class Model:
         skip_parked=True: the batch leaves the blocks of finished LPs out of its factorisations and sweeps (the results do not depend on it).
         slots=B: the LPs STREAM through handles of at most B slots (BatchedDeviceHSD.optimize_stream) -- the models that reach the interior-point
         method are grouped by the pattern of their standard form, each group runs through one handle of min(B, group size) slots, and a slot whose
-        LP is decided takes the group's next one.  The homogeneous self-dual loop only: algorithm="mpc" with slots raises ValueError."""
+        LP is decided takes the group's next one.  The homogeneous self-dual loop only: algorithm="mpc" with slots raises ValueError
+        (`Model.optimize_stream` streams both loops)."""
         models = list(models)
         if slots is not None:
-            return cls._optimize_stream(models, int(slots), kw, skip_parked)
+            if any(mdl.algorithm != "hsd" for mdl in models):
+                raise ValueError("optimize_batch(slots=...) streams through the homogeneous self-dual loop: every model must have algorithm='hsd' "
+                                 "(algorithm='mpc': use Model.optimize_stream, which streams Mehrotra's loop too)")
+            return cls._optimize_stream(models, int(slots), kw, skip_parked, "optimize_batch")
         algorithms = {mdl.algorithm for mdl in models}
         if len(algorithms) > 1:
             raise ValueError(f"optimize_batch runs ONE interior-point loop for the whole batch: the models mix the algorithms {sorted(algorithms)}")
@@ -164,14 +168,28 @@ class Model:
         return models
 
     @classmethod
-    def _optimize_stream(cls, models, slots, kw, skip_parked=False):
+    def optimize_stream(cls, models, slots, skip_parked=False, **kw):
+        """`optimize()` of many models through handles of at most `slots` slots, whatever their algorithms: the models that reach the interior-point
+        method are grouped by algorithm ("hsd" | "mpc") and by the pattern of their standard form, each group streams through one handle of
+        min(slots, group size) slots (BatchedDeviceHSD.optimize_stream / BatchedDeviceMPC.optimize_stream), and every model ends as after its own
+        `optimize()`.  kw: the backend's keywords (default: those of the first model); skip_parked as in `optimize_batch`."""
+        models = list(models)
+        if isinstance(slots, bool) or not isinstance(slots, (int, np.integer)):
+            raise TypeError("optimize_stream: slots is the number of slots of a handle (an integer)")
+        for mdl in models:
+            if not isinstance(mdl, Model):
+                raise TypeError("optimize_stream: models is a sequence of Model objects")
+        return cls._optimize_stream(models, int(slots), kw, skip_parked, "optimize_stream")
+
+    @classmethod
+    def _optimize_stream(cls, models, slots, kw, skip_parked=False, who="optimize_batch"):
         from .hsd_batch import BatchedDeviceHSD, pattern_key
+        from .mpc_batch import BatchedDeviceMPC
         if slots < 1:
-            raise ValueError("optimize_batch: slots must be at least 1")
-        if any(mdl.algorithm != "hsd" for mdl in models):
-            raise ValueError("optimize_batch(slots=...) streams through the homogeneous self-dual loop: every model must have algorithm='hsd' "
-                             "(algorithm='mpc': the Mehrotra batch has no refill)")
-        groups = {}                                                          # pattern -> [(model, reduced LP, standard form)], in the order of `models`
+            raise ValueError(f"{who}: slots must be at least 1")
+        if any(mdl.algorithm not in ("hsd", "mpc") for mdl in models):
+            raise ValueError(f"{who} streams through the homogeneous self-dual loop or Mehrotra's: every model must have algorithm='hsd' or 'mpc'")
+        groups = {}                                                          # (algorithm, pattern) -> [(model, reduced LP, standard form)], in the order of `models`
         for mdl in models:
             lp_inner = mdl.lp
             if mdl.presolve_options.Level > 0:
@@ -183,10 +201,11 @@ class Model:
                     continue
                 lp_inner = ps.reduced_problem()
             d = standard_form(lp_inner)
-            groups.setdefault(pattern_key(d.A), []).append((mdl, lp_inner, d))
-        for group in groups.values():
+            groups.setdefault((mdl.algorithm, pattern_key(d.A)), []).append((mdl, lp_inner, d))
+        for (algorithm, _), group in groups.items():
             nslots = min(slots, len(group))
-            opt = BatchedDeviceHSD([d for _, _, d in group[:nslots]], skip_parked=skip_parked, **(kw or models[0].backend_kw))
+            Batched = BatchedDeviceMPC if algorithm == "mpc" else BatchedDeviceHSD
+            opt = Batched([d for _, _, d in group[:nslots]], skip_parked=skip_parked, **(kw or models[0].backend_kw))
             records = opt.optimize_stream([d for _, _, d in group[nslots:]])
             for (mdl, lp_inner, _), r in zip(group, records):
                 res = mdl.inner = InnerResult(r["status"], r["primal_status"], r["dual_status"], r["xh"], r["yh"], r["zl"], r["zu"], r["tau"],

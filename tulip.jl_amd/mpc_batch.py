@@ -8,13 +8,26 @@ the `tlpk_mpc_batch_*` calls (include/tlpk.h) and the shared `tlpk_ipm_batch_*` 
 
     opt = BatchedDeviceMPC([standard_form(lp) for lp in lps], device=0).optimize()
     opt.status[k], opt.niter[k], opt.primal_objective[k], opt.solution(k)
+
+More LPs than slots (DESIGN.md section 4b''-s): `optimize_stream(queue)` as the HSD batch has it.  Mehrotra's starting point costs a factorisation and two
+solves per LP; an LP that takes a slot pays for none of them: it is ENTERING for the rest of the pass in which its predecessor left -- the update of that
+pass factorises its starting matrix beside the running LPs' iterates, the predictor solve and the corrector solve carry its two right-hand sides
+(`tlpk_mpc_batch_factor_enter`, `tlpk_mpc_batch_newton_enter`) -- and `tlpk_mpc_batch_enter_finish` runs the column kernels of the starting point.
+
+    pass p, after the leaves and the refill     active LPs                      entering LPs
+      tlpk_mpc_batch_factor_enter               theta of the iterate, regP/regD   theta_inv = 0, Rp = 1, Rd = 1e-6
+      tlpk_mpc_batch_newton_enter(0)            predictor                         (0, c) -> y
+      tlpk_mpc_batch_newton_enter(1)            corrector                         (b, 0) -> x
+      gap / targets / newton(2) / advance       as in optimize()                  skipped (their `active` flag is 0)
+      tlpk_mpc_batch_enter_finish               --                                shifts, balanced products; active from pass p + 1
 """
+import ctypes as C
 import time
 
 import numpy as np
 
 from . import _lib
-from .hsd_batch import _DECIDED, BatchedDeviceHSD
+from .hsd_batch import _DECIDED, BatchedDeviceHSD, stream_assign
 from .hsd_device import SQRT_EPS
 from .kkt import OutOfMemoryError
 
@@ -80,11 +93,17 @@ class BatchedDeviceMPC(BatchedDeviceHSD):
         self.timers["n_solve"] += 2
         self.mu = self._per_p(out)
 
-    def _newton(self, mode, m, gmu=0.0):
-        """MPC/step.jl:164-217 for the LPs of `m`; returns the primal and dual step lengths (at most 1) as arrays."""
+    def _newton(self, mode, m, gmu=0.0, enter=None):
+        """MPC/step.jl:164-217 for the LPs of `m`; returns the primal and dual step lengths (at most 1) as arrays.
+        enter (modes 0, 1): the LPs that take a solve of their starting point from the same stacked solve."""
         g = np.ascontiguousarray(np.broadcast_to(np.asarray(gmu, dtype=np.float64), (self.nlp,)))
         out = np.zeros((self.nlp, 2))
-        self._call(self.L.tlpk_mpc_batch_newton(self.kkt._h, mode, self._mask(m), _lib.as_pd(g), _lib.as_pd(out)))
+        if enter is not None and enter.any():
+            e8 = np.ascontiguousarray(enter, dtype=np.uint8)
+            self._call(self.L.tlpk_mpc_batch_newton_enter(self.kkt._h, mode, self._mask(m), _lib.as_pu8(e8), _lib.as_pd(g), _lib.as_pd(out)))
+            self.timers["n_solve"][enter] += 1
+        else:
+            self._call(self.L.tlpk_mpc_batch_newton(self.kkt._h, mode, self._mask(m), _lib.as_pd(g), _lib.as_pd(out)))
         self.timers["n_solve"][m] += 1
         return np.minimum(1.0, out[:, 0]), np.minimum(1.0, out[:, 1])
 
@@ -105,15 +124,20 @@ class BatchedDeviceMPC(BatchedDeviceHSD):
         with np.errstate(all="ignore"):
             return self._direction_and_move(step)
 
-    def _direction_and_move(self, step):
+    def _direction_and_move(self, step, enter=None):
         o = self._o
         # predictor (affine scaling), step.jl:225-241
-        ap, ad = self._newton(0, step)
+        ap, ad = self._newton(0, step, enter=enter)
         # corrector, step.jl:246-274
-        ga, _ = self._gap(step, ap, ad)
-        ratio = (ga / self.p) / self.mu
-        sigma = np.minimum(np.maximum(np.array([_cube(r) for r in ratio.tolist()]), SQRT_EPS), 1.0 - SQRT_EPS)
-        ap, ad = self._newton(1, step, sigma * self.mu)
+        if step.any():
+            ga, _ = self._gap(step, ap, ad)
+            ratio = (ga / self.p) / self.mu
+            sigma = np.minimum(np.maximum(np.array([_cube(r) for r in ratio.tolist()]), SQRT_EPS), 1.0 - SQRT_EPS)
+        else:
+            sigma = np.zeros(self.nlp)                                       # (a pass in which only entering LPs are left: their second solve)
+        ap, ad = self._newton(1, step, sigma * self.mu, enter=enter)
+        if not step.any():
+            return step
         # extra centrality corrections, step.jl:71-109, 279-322 (delta = 0.3, gamma = 0.1): while ANY LP still corrects
         ncor = np.zeros(self.nlp, dtype=np.int64)
         cor = step & (ncor < o["CorrectionLimit"])
@@ -130,6 +154,7 @@ class BatchedDeviceMPC(BatchedDeviceHSD):
                 ap, ad = np.where(take, apc, ap), np.where(take, adc, ad)
                 ncor[take] += 1
             cor = take & (ncor < o["CorrectionLimit"])                       # a refused candidate or the limit: masked for the rest of the step
+            self.corrector_rounds += 1                                       # (a statistic: rounds of the centrality corrector, summed over the steps)
         ap, ad = ap * o["StepDampFactor"], ad * o["StepDampFactor"]
         self._set(self.alpha_p, step, ap); self._set(self.alpha_d, step, ad)
         xz = np.zeros(self.nlp)
@@ -168,6 +193,175 @@ class BatchedDeviceMPC(BatchedDeviceHSD):
         self._cache = {}
         self.seconds = time.perf_counter() - tstart
         return self
+
+    # ---- a batch that keeps going (DESIGN.md section 4b''-s) ----
+    def _init_slot(self, k):
+        super()._init_slot(k)
+        self.kappa[k] = 0.0
+        self.alpha_p[k] = self.alpha_d[k] = 0.0
+
+    def _factor_enter(self, step, enter):
+        """`_factor` with entering LPs in the update: returns (the LPs of `step` that hold a factor, the LPs of `enter` whose starting matrix was factorised).
+        An entering LP that the update names as its failure is out with Trm_NumericalProblem: its regularisations are the starting point's constants, there is
+        nothing to bump.  The others retry as in `_factor`."""
+        if not enter.any():
+            return self._factor(step), enter.copy()
+        B = self.nlp
+        step, enter, entering = step.copy(), enter.copy(), enter.copy()
+        nbump = np.zeros(B, dtype=np.int64)
+        fail = C.c_int64(-1)
+        while step.any() or enter.any():
+            s8, e8 = np.ascontiguousarray(step, dtype=np.uint8), np.ascontiguousarray(enter, dtype=np.uint8)
+            rc = self.L.tlpk_mpc_batch_factor_enter(self.kkt._h, _lib.as_pu8(s8), _lib.as_pu8(e8), _lib.as_pd(self.regP), _lib.as_pd(self.regD), C.byref(fail))
+            self.last_update_rc = rc
+            if rc == _lib.OK:
+                self.timers["n_update"][step | enter] += 1
+                break
+            if rc != _lib.NOT_POSDEF:
+                self._call(rc)
+            k = int(fail.value)
+            if 0 <= k < B and enter[k]:
+                self.status[k] = "Trm_NumericalProblem"
+                enter[k] = False
+                self._evict(k)
+                continue
+            bad = np.zeros(B, dtype=bool)
+            if 0 <= k < B and step[k]:
+                bad[k] = True
+            else:
+                bad[:] = step | enter                                        # the pivot cannot be attributed: every LP of the update counts a failure
+            for name in self._bumped:
+                getattr(self, name)[bad & step] *= 100
+            nbump[bad] += 1
+            self.timers["n_bump"][bad & step] += 1
+            gone = bad & ~(nbump < 3)
+            self.status[gone] = "Trm_NumericalProblem"
+            step &= ~gone; enter &= ~gone
+        self.timers["max_bumps_in_a_step"] = np.maximum(self.timers["max_bumps_in_a_step"], np.where(entering, 0, nbump))
+        return step, enter
+
+    def _evict(self, k):
+        """The starting matrix of the LP in slot k was refused.  From here on the slot is parked, and a parked block is factorised with every update unless
+        `skip_parked` leaves it out: values that broke the starting matrix (an entry that is not a number, say) would break the parked one as well and fail
+        the updates of every other LP.  So the slot takes back the matrix values of the LP it replaced, which this slot has factorised before; its vectors
+        and the record of the refused LP stay (its iterate is the one `_apply` left: the update failed before anything was written)."""
+        old = self._replaced.pop(k, None)
+        if old is None:
+            return
+        p0, p1 = self._slot_range(k)
+        self.A.data[p0:p1] = old
+        sel = np.zeros(self.nlp, dtype=np.uint8); sel[k] = 1
+        nz = self.A.data
+        t0 = time.perf_counter()
+        self._call(self.L.tlpk_ipm_batch_refill(self.kkt._h, _lib.as_pu8(sel), _lib.as_pd(nz), nz.shape[0], None, None, None, None))
+        self.refill_seconds += time.perf_counter() - t0
+
+    def _enter_finish(self, enter):
+        out = np.zeros(self.nlp)
+        t0 = time.perf_counter()
+        e8 = np.ascontiguousarray(enter, dtype=np.uint8)
+        self._call(self.L.tlpk_mpc_batch_enter_finish(self.kkt._h, _lib.as_pu8(e8), _lib.as_pd(out)))
+        self.enter_finish_seconds += time.perf_counter() - t0
+        self._set(self.mu, enter, self._per_p(out))
+
+    enter_finish_seconds = 0.0
+
+    def _step_stream(self, act, enter):
+        """`compute_step` for the LPs of `act` with the LPs of `enter` riding along; returns (the active LPs that moved, the entering LPs that now stand at
+        their starting point)."""
+        step = act.copy()
+        self._set(self.regP, step, np.minimum(np.maximum(self.regP / 10, SQRT_EPS), 1.0))
+        self._set(self.regD, step, np.minimum(np.maximum(self.regD / 10, SQRT_EPS), 1.0))
+        step, enter = self._factor_enter(step, enter)
+        if step.any() or enter.any():                                        # the two entering solves happen also when no active LP holds a factor
+            self._direction_and_move(step, enter)
+        if enter.any():
+            self._enter_finish(enter)
+        return step, enter
+
+    def refill(self, slots, lps, options=None):
+        """`BatchedDeviceHSD.refill`, then Mehrotra's starting point for those slots alone (no LP is active in the four calls, the new ones enter).  An LP
+        whose starting matrix cannot be factorised ends Trm_NumericalProblem."""
+        super().refill(slots, lps, options)
+        enter = np.zeros(self.nlp, dtype=bool)
+        enter[[int(k) for k in slots]] = True
+        with np.errstate(all="ignore"):
+            self._step_stream(np.zeros(self.nlp, dtype=bool), enter)
+        return self
+
+    def optimize_stream(self, lps, options=None):
+        """`BatchedDeviceHSD.optimize_stream` for Mehrotra's loop: the same records, the same FIFO schedule (`stream_assign`), options that travel with the LP,
+        `passes`, `refills`, `refill_seconds`, `record_seconds` (and `enter_finish_seconds`).  An LP found decided in pass p leaves in pass p; its slot is
+        refilled straight after the leaves of that pass and the new LP is ENTERING for the rest of it (module docstring), active from pass p + 1 -- the pass its
+        record names as `entered`.  A slot so holds an LP for niter + 1 passes.  An entering LP whose starting matrix fails the update gets
+        Trm_NumericalProblem with niter 0 (entered = left = p) and frees its slot."""
+        B = self.nlp
+        queue, qopts, slot_keys, qkeys = self._stream_queue(lps, options)
+        N = len(queue)
+        tstart = time.perf_counter()
+        time_limit = min([self.time_limit] + [float(o.TimeLimit) for o in qopts])
+        self._init_state()
+        act = self.active
+        act[:] = True
+        enter = np.zeros(B, dtype=bool)
+        records = [None] * (B + N)
+        lp_of_slot, entered, free, waiting = list(range(B)), [1] * B, set(), list(range(N))
+        self.passes = self.refills = 0
+        self.refill_seconds = self.record_seconds = self.enter_finish_seconds = 0.0
+        self.corrector_rounds = 0
+        stopped = None
+
+        def leave(mask):
+            self._leave(mask, records, lp_of_slot, entered, free)
+
+        def assign():
+            return stream_assign(free, slot_keys, [qkeys[q] for q in waiting]) if free and waiting else []
+
+        with np.errstate(all="ignore"):
+            self.compute_starting_point()
+            while act.any() or assign():
+                self.passes += 1
+                before = act.copy()
+                if act.any():
+                    self.compute_residuals(act)
+                    self.update_solver_status(act)
+                    act &= ~np.isin(self.status, _DECIDED)
+                    lim = act & (self.niter >= self._o["IterationsLimit"])
+                    self.status[lim] = "Trm_IterationLimit"
+                    act &= ~lim
+                    leave(before & ~act)
+                pairs = assign()                                             # straight after the leaves: the new LPs enter in this pass
+                if pairs:
+                    qs = [waiting[pos] for _, pos in pairs]
+                    self._apply([(k,) + queue[q][1:] for (k, _), q in zip(pairs, qs)], [qopts[q] for q in qs])
+                    for (k, _), q in zip(pairs, qs):
+                        lp_of_slot[k], entered[k] = B + q, self.passes + 1
+                        free.discard(k); enter[k] = True
+                    gone = set(qs)
+                    waiting = [q for q in waiting if q not in gone]
+                if not (act.any() or enter.any()):
+                    break
+                if time.perf_counter() - tstart >= time_limit:
+                    self.status[act | enter] = stopped = "Trm_TimeLimit"; leave(act | enter); act[:] = False; break
+                try:
+                    moved, entered_now = self._step_stream(act, enter)
+                except OutOfMemoryError:
+                    self.status[act | enter] = stopped = "Trm_MemoryLimit"; leave(act | enter); act[:] = False; break
+                failed = act & ~moved                                        # (Trm_NumericalProblem: the slot is free like any other)
+                failed_entering = enter & ~entered_now
+                for k in np.flatnonzero(failed_entering):
+                    entered[k] = self.passes                                 # (it never became active)
+                act &= moved
+                leave(failed | failed_entering)
+                self.niter[act] += 1
+                act |= entered_now                                           # active from the next pass
+                enter[:] = False
+        for q in waiting:                                                    # (only after a global stop: these LPs never ran)
+            records[B + q] = self._never_ran(queue[q], stopped)
+        self._cache = {}
+        self.seconds = time.perf_counter() - tstart
+        self.records = records
+        return records
 
 
 __all__ = ["BatchedDeviceMPC"]
