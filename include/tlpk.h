@@ -501,6 +501,26 @@ int tlpk_ipm_batch_advance(tlpk_handle *h, const uint8_t *active, const double *
  * and outside these calls no mask is in force.  The active LPs' results do not depend on the setting, bit for bit.
  * TLPK_BADARG on a handle that is not batch-loaded, on one with refine_steps > 0, or when an LP's fronts are not its own. */
 int tlpk_ipm_batch_skip(tlpk_handle *h, int on);
+/* One update of the stack with a ROLE per LP and a VERDICT per LP: every LP whose block meets a non-positive pivot is reported by the
+ * one call, and an LP that already holds a good factor can keep it while the others are factorised again.  role[k]:
+ *   0  parked    the parking values, as active[k] = 0 of tlpk_ipm_batch_factor; whether the parked block is factorised stays
+ *                tlpk_ipm_batch_skip's choice
+ *   1  active    theta_inv from the iterate, regP[k] / regD[k], factorised: tlpk_ipm_batch_factor's active LP
+ *   2  hold      nothing of the LP is written, assembled, zeroed or factorised: its segments of the vectors behind codes 33 - 35 of
+ *                tlpk_ipm_get, its panels and its inverted diagonal blocks keep every bit, regP[k] / regD[k] are not read, and the factor
+ *                of an earlier call stays the one the next solves use (tlpk_block_skip's mechanism, whatever tlpk_ipm_batch_skip says)
+ *   3  entering  what tlpk_mpc_batch_factor_enter does for enter[k]
+ * fail_col[k] = the permuted column of LP k's first non-positive pivot in this update, or -1; *nfail = the number of LPs with one.  A held
+ * or parked-and-skipped LP never has one.  TLPK_OK: no LP failed, the handle is factored.  TLPK_NOT_POSDEF: at least one did, the handle
+ * is not factored (as after tlpk_ipm_batch_factor), tlpk_stats.fail_col is the smallest of them; the blocks of the other LPs hold valid
+ * factors -- a failing pivot is replaced by 1 inside its own block -- which a following call can hold.  After the call no mask is in force.
+ * An update without a failure costs no extra copy and no extra wait.
+ * TLPK_BADARG, in this order: h NULL; a handle that is not batch-loaded; a NULL pointer; a role above 3; a stale handle after
+ * tlpk_set_values*; ("... hold refused: ...") a hold on a handle with refine_steps > 0 or on one where an LP's fronts are not its own (tlpk_ipm_batch_skip's
+ * conditions, but for one case: a front that LPs share and that stands alone -- no rows below its pivot block, no children; K2 gathers the
+ * columns of A without entries in such a root front -- is accepted and factorised by every call, holds or not).  Then TLPK_NO_DEVICE. */
+int tlpk_ipm_batch_factor_each(tlpk_handle *h, const uint8_t *role /*nlp*/, const double *regP /*nlp*/, const double *regD /*nlp*/,
+                               int64_t *fail_col /*nlp*/, int64_t *nfail);
 
 /* ---------------------------------------------------------------------------------------------
  * Refilling slots: a batch that keeps going.  A batch-loaded handle has nlp SLOTS; when the LP of a slot is decided, the next LP of the

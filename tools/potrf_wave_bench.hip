@@ -27,7 +27,7 @@ static double run(int nf, int n, const std::vector<double> &A0, std::vector<doub
     FrontDesc *dfr; PotrfTask *dt; double *L, *dinv, *sp; int *info;
     hipMalloc(&dfr, sizeof(FrontDesc) * nf); hipMemcpy(dfr, fr.data(), sizeof(FrontDesc) * nf, hipMemcpyHostToDevice);
     hipMalloc(&dt, sizeof(PotrfTask) * nf); hipMemcpy(dt, tasks.data(), sizeof(PotrfTask) * nf, hipMemcpyHostToDevice);
-    hipMalloc(&L, 8 * loff); hipMalloc(&dinv, 8 * doff); hipMemset(dinv, 0, 8 * doff); hipMalloc(&sp, 8 * 32 * nf + 64); hipMalloc(&info, 16);
+    hipMalloc(&L, 8 * loff); hipMalloc(&dinv, 8 * doff); hipMemset(dinv, 0, 8 * doff); hipMalloc(&sp, 8 * 32 * nf + 64); hipMalloc(&info, 4 * (INFO_WORDS + n));      // (status words, then a mark word per column: record_fail)
     hipMemset(sp, 0, 8 * 32 * nf + 64);
     { int big = 0x7fffffff; hipMemcpy(info, &big, 4, hipMemcpyHostToDevice); }
     c.fronts = dfr; c.Lval = L; c.dinv = dinv; c.info = info; c.spart = sp;

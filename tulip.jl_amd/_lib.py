@@ -93,6 +93,7 @@ EXPORTS = [
     "tlpk_ipm_batch_refill", "tlpk_ipm_get_lp",
     "tlpk_block_skip", "tlpk_ipm_batch_skip",
     "tlpk_mpc_batch_factor_enter", "tlpk_mpc_batch_newton_enter", "tlpk_mpc_batch_enter_finish", "tlpk_ipm_get_lps",
+    "tlpk_ipm_batch_factor_each",
 ]
 
 
@@ -218,6 +219,7 @@ def lib():
     L.tlpk_block_skip.argtypes = [vp, pu8, C.c_int64]
     L.tlpk_ipm_batch_skip.argtypes = [vp, C.c_int]
     L.tlpk_mpc_batch_factor_enter.argtypes = [vp, pu8, pu8, pd, pd, p64]
+    L.tlpk_ipm_batch_factor_each.argtypes = [vp, pu8, pd, pd, p64, p64]
     L.tlpk_mpc_batch_newton_enter.argtypes = [vp, C.c_int, pu8, pu8, pd, pd]
     L.tlpk_mpc_batch_enter_finish.argtypes = [vp, pu8, pd]
     L.tlpk_ipm_get_lps.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64, p64, C.c_int64, pd, C.c_int64]

@@ -324,8 +324,11 @@ __global__ __launch_bounds__(IPM_T) void k_mpcb_gap(IpmVecs v, IpmDir D, IpmBatc
 // running LPs.  sc[IPM_ROLE] is the LP's role in the call; its `active` flag is 0, so every kernel above skips an entering LP.
 // ---------------------------------------------------------------------------------------------
 // k_ipmb_theta for the active and the parked LPs (sc[0] = regP, sc[1] = regD), k_mpcb_fill for the entering ones
+// HOLD (tlpk_ipm_batch_factor_each): an LP with the role IPM_HOLD keeps every bit of its three segments
+template <bool HOLD>
 __global__ void k_mpcb_theta_enter(IpmVecs v, IpmBatch B, double *__restrict__ theta, double *__restrict__ regP, double *__restrict__ regD) {
     const Seg g = seg_of(B, B.tb);
+    if (HOLD && g.sc[IPM_ROLE] == IPM_HOLD) return;                          // (block-uniform)
     const i64 stride = (i64)g.nbk * blockDim.x, t0 = (i64)g.lb * blockDim.x + threadIdx.x;
     if (g.sc[IPM_ROLE] == IPM_ENTERING) {                                    // (block-uniform)
         for (i64 jj = t0; jj < g.nk; jj += stride) { const i64 j = g.c0 + jj; theta[j] = 0.0; regP[j] = 1.0; v.xid[j] = 0.0; v.hx[j] = 0.0; }
@@ -421,7 +424,10 @@ void mpcb_launch_advance(hipStream_t st, const IpmVecs &v, const IpmDir &D, cons
     hipLaunchKernelGGL(k_ipmb_advance<true>, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, D, B, partials);
 }
 void mpcb_launch_theta_enter(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD) {
-    hipLaunchKernelGGL(k_mpcb_theta_enter, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, B, theta, regP, regD);
+    hipLaunchKernelGGL(k_mpcb_theta_enter<false>, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, B, theta, regP, regD);
+}
+void ipmb_launch_theta_roles(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD) {
+    hipLaunchKernelGGL(k_mpcb_theta_enter<true>, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, B, theta, regP, regD);
 }
 void mpcb_launch_enter_rhs(hipStream_t st, const IpmVecs &v, const IpmBatch &B, int mode) {
     hipLaunchKernelGGL(k_mpcb_enter_rhs, dim3(B.tb.nblocks), dim3(IPM_T), 0, st, v, B, mode);

@@ -60,6 +60,20 @@ __device__ __forceinline__ i32 pld(const FrontDesc &fd, i32 col) { return fd.lda
 // fronts of the units that this update / solve leaves out.  Every per-front kernel asks right after it has read its task -- the front index is workgroup-uniform
 // (wave-uniform where a wave owns a front) -- and returns before it reads or writes anything the front owns.
 __device__ __forceinline__ bool front_skipped(const DevCtx &c, i32 front) { return c.front_skip != nullptr && c.front_skip[front] != 0; }
+// A non-positive pivot in permuted column `col`, by ONE lane of the front's workgroup (wave), in the cold branch: info[0] keeps the smallest column of the
+// update, and the column's own mark word behind the status words takes `col` (DESIGN.md section 4b'-v) -- a plain store through the pointer and of the value the
+// atomic has in registers anyway (an unmarked word holds FAIL_NONE): a second pointer in DevCtx with a test for null cost the pivot kernels registers and scratch
+// (profiles/batch_retry_resources.txt).  Only tlpk_ipm_batch_factor_each reads the marks: it resets them before its update and k_fold_fail turns them into one
+// verdict per LP after an update that failed; every other update leaves stale marks behind, which nobody reads.
+__device__ __forceinline__ void record_fail(const DevCtx &c, i32 col) {
+    atomicMin(c.info, col);
+    c.info[INFO_WORDS + col] = col;
+}
+// ... for the kernels whose register peak lies in this branch (k_potrf_small, potrf_block): TWO lanes (who = 0, 1) of the wave call, and the one atomic
+// instruction the parent had serves both words -- lane 0 the status word, lane 1 the column's mark (an unmarked word holds FAIL_NONE, above every column)
+__device__ __forceinline__ void record_fail_pair(const DevCtx &c, i32 col, int who) {
+    atomicMin(c.info + (who ? INFO_WORDS + col : 0), col);              // (a select: the product who * (INFO_WORDS + col) cost k_potrf_wide<true, 0> 48 bytes of scratch)
+}
 
 // ------------------------------------------------------------------------------------------
 // elementwise / sparse kernels
@@ -122,7 +136,7 @@ __global__ void k_single_factor(i64 n, const i64 *__restrict__ loff, const i64 *
     if (skip && skip[i]) return;                                  // block skip: the singles' bytes of front_skip
     double d = Lval[loff[i]];
     const double sj = csign ? csign[col[i]] : 1.0;
-    if (!(sj * d > 0.0)) { atomicMin(info, col[i]); d = 1.0; }      // same convention as potrf_block
+    if (!(sj * d > 0.0)) { atomicMin(info, col[i]); info[INFO_WORDS + col[i]] = col[i]; d = 1.0; }      // same convention as potrf_block (record_fail)
     d = fabs(d);
     const double l = sqrt(d);
     Lval[loff[i]] = l;
@@ -572,7 +586,7 @@ __device__ __forceinline__ void potrf_block(const DevCtx &c, const FrontDesc &fd
             for (int q = 0; q <= jq; ++q) rv[q] = rowbuf[pb][cg + 4 * q];
             const double sj = SIGNED ? sg[bk0 + j] : 1.0;
             if (!(sj * d > 0.0)) {
-                if (tid == 0) atomicMin(c.info, fd.col0 + bk0 + j);
+                if (tid < 2) record_fail_pair(c, fd.col0 + bk0 + j, tid);
                 d = sj;
             }
             if (SIGNED) d = fabs(d);
@@ -694,7 +708,7 @@ __device__ __forceinline__ void potrf_block_pair(const DevCtx &c, const FrontDes
     // pivot of one column from its diagonal entry d (sign s): 1 / (signed pivot), column scale, sqrt|d| -- potrf_block's arithmetic
     auto pivot = [&](double d, const double sj, const i32 j, double &inv2, double &isq, double &sq) {
         if (!(sj * d > 0.0)) {
-            if (tid == 0) atomicMin(c.info, fd.col0 + bk0 + j);
+            if (tid == 0) record_fail(c, fd.col0 + bk0 + j);
             d = sj;
         }
         if (SIGNED) d = fabs(d);
@@ -973,7 +987,7 @@ __device__ __forceinline__ void potrf_block_wave(const DevCtx &c, const FrontDes
         }
         TLPK_LDS_FENCE();
     }
-    if (failcol < NB_IN && r == 0) atomicMin(c.info, fd.col0 + bk0 + failcol);
+    if (failcol < NB_IN && r == 0) record_fail(c, fd.col0 + bk0 + failcol);
     }
     PT_STAMP();
     // off-diagonal blocks of the inverse, by block distance: W_ij = -W_ii (sum_{k=j}^{i-1} L_ik W_kj); the blocks of one distance are independent:
@@ -1586,7 +1600,7 @@ __device__ __forceinline__ void potrf_block_dpp(const DevCtx &c, const FrontDesc
     // stores panel 3; after one more barrier W_3j = -W_33 G_3j
     if (wave == 1) inv_diag(3);
     else if (wave == 0) {
-        if (failcol < NB_IN && lane == 0) atomicMin(c.info, fd.col0 + bk0 + failcol);
+        if (failcol < NB_IN && lane == 0) record_fail(c, fd.col0 + bk0 + failcol);
         gb = inv_gpart(zero4, 3, 2, 2, 3);
         store_panel(3, 0, PW_W);
     } else {
@@ -1641,7 +1655,7 @@ __global__ __launch_bounds__(256) void k_potrf_small(const PotrfTask *__restrict
             double d = __shfl(a[k], k);
             const double sk = SIGNED ? sg[k] : 1.0;
             if (!(sk * d > 0.0)) {
-                if (lane == 0) atomicMin(c.info, fd.col0 + k);
+                if (lane < 2) record_fail_pair(c, fd.col0 + k, lane);
                 d = sk;
             }
             if (SIGNED) d = fabs(d);
@@ -4587,6 +4601,17 @@ __global__ void k_expand_skip(i64 n, const i32 *__restrict__ front_unit, const u
 void launch_expand_skip(hipStream_t st, const DevArrays &a, const unsigned char *unit_skip, const double *unit_active, int stride) {
     const i64 n = a.n_fronts + a.n_single;
     if (n > 0) hipLaunchKernelGGL(k_expand_skip, dim3(nblk(n, 256)), dim3(256), 0, st, n, a.front_unit, unit_skip, unit_active, stride, a.skip_bytes);
+}
+// Per-LP pivot verdicts: the smallest marked column of every unit.  Runs only after an update whose status word says "failed"; the marks are few, so the
+// atomics are too.
+__global__ void k_fold_fail(i64 m, const int *__restrict__ marks, const i32 *__restrict__ col_unit, int *__restrict__ unit_fail) {
+    const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m || marks[j] == FAIL_NONE) return;
+    const i32 u = col_unit[j];
+    if (u >= 0) atomicMin(unit_fail + u, (int)j);
+}
+void launch_fold_fail(hipStream_t st, const DevArrays &a) {
+    if (a.m > 0) hipLaunchKernelGGL(k_fold_fail, dim3(nblk(a.m, 256)), dim3(256), 0, st, a.m, a.ctx.info + INFO_WORDS, a.col_unit, a.unit_fail);
 }
 void launch_k2_diag(hipStream_t st, i64 n, const double *theta, const double *regP, double *D2) {
     hipLaunchKernelGGL(k_k2_diag, dim3(nblk(n + 1, 256)), dim3(256), 0, st, n, theta, regP, D2);

@@ -416,7 +416,7 @@ int upload_all(tlpk_handle *h) {
     AL(d.ctx.Lval, S.lval_len); AL(d.ctx.U0, S.ubuf_len[0]); AL(d.ctx.U1, S.ubuf_len[1]);
     // debugging aid: start from NaNs everywhere, so that a read of storage the factorisation never writes would show
     if (std::getenv("TLPK_POISON") && S.lval_len > 0) { HIPCHK(h, hipMemset(d.ctx.Lval, 0xFF, (size_t)S.lval_len * 8)); HIPCHK(h, hipDeviceSynchronize()); }
-    AL(d.ctx.uc, 2 * S.uc_len); AL(d.ctx.xw, 2 * S.m); AL(d.ctx.info, 16);      // two copies: the second right-hand side of tlpk_solve2_device
+    AL(d.ctx.uc, 2 * S.uc_len); AL(d.ctx.xw, 2 * S.m); AL(d.ctx.info, INFO_WORDS + S.m);      // (xw: two copies, the second right-hand side of tlpk_solve2_device; info: the status words, then one mark word per column)
     d.ctx.xw2 = S.m; d.ctx.uc2 = S.uc_len; AL(d.ctx.dinv, S.dinv_len); AL(d.ctx.spart, S.spart_len);
     const i64 nn = std::max<i64>(S.n + (S.n_dense > 0 ? 1 : 0), S.k2_n + 1);   // K2: user vectors have k2_n entries, D2 one more; dense columns: D one more
     AL(h->d_theta, nn); AL(h->d_regP, nn); AL(h->d_regD, S.m); AL(h->d_D, nn);
@@ -446,7 +446,7 @@ int upload_all(tlpk_handle *h) {
         if ((rc = dev_alloc(h, &blk, nt + 4 * S.m)) != TLPK_OK) return rc;       // [forward | backward] x two right-hand sides
         d.sweep_tickets = blk; d.sweep_xh = reinterpret_cast<double *>(blk + nt);
         d.sweep_reset_bytes = (nt + 2 * S.m) * 8; d.sweep_reset_bytes2 = (nt + 4 * S.m) * 8;
-        HIPCHK(h, hipMemset(d.ctx.info, 0, 16 * sizeof(int)));
+        HIPCHK(h, hipMemset(d.ctx.info, 0, INFO_WORDS * sizeof(int)));
     }
     HIPCHK(h, hipHostMalloc((void **)&h->h_info, 4 * sizeof(int), hipHostMallocDefault));
     h->h_info[0] = h->h_info[1] = h->h_info[2] = h->h_info[3] = 0;
@@ -1339,7 +1339,7 @@ int tlpk_update_device(tlpk_handle *h, const double *d_theta, const double *d_re
 
 // ---- block skip (include/tlpk.h: tlpk_block_skip; DESIGN.md section 4b'-s) ----
 extern "C++" {
-int skip_build_units(tlpk_handle *h, const std::vector<i32> &row_unit, const std::vector<i32> &col_unit, i64 nunits, const char *what) {
+int skip_build_units(tlpk_handle *h, const std::vector<i32> &row_unit, const std::vector<i32> &col_unit, i64 nunits, const char *what, bool allow_shared) {
     const Symbolic &S = h->S;
     const bool k2 = S.system == 1;
     auto bad = [&](const std::string &msg) { h->last_error = std::string(what) + ": " + msg; return TLPK_BADARG; };
@@ -1355,12 +1355,17 @@ int skip_build_units(tlpk_handle *h, const std::vector<i32> &row_unit, const std
     }
     const size_t nf = S.fronts.size(), nsg = S.single_col.size();
     std::vector<i32> fu(nf + nsg, -1);
+    std::vector<char> has_child(nf, 0);
+    for (size_t s = 0; s < nf; ++s) if (S.fronts[s].parent >= 0) has_child[(size_t)S.fronts[s].parent] = 1;
+    bool shared = false;
     for (size_t s = 0; s < nf; ++s) {
         const FrontDesc &fd = S.fronts[s];
         if (fd.ns <= 0) return bad("front " + std::to_string(s) + " has no pivot column");
         const i32 u = node_unit[(size_t)S.perm[(size_t)fd.col0]];
-        for (i32 k = 0; k < fd.ns; ++k)
-            if (node_unit[(size_t)S.perm[(size_t)(fd.col0 + k)]] != u) return bad("the pivot columns of front " + std::to_string(s) + " lie in more than one block");
+        bool mixed = false;
+        for (i32 k = 0; k < fd.ns && !mixed; ++k) mixed = node_unit[(size_t)S.perm[(size_t)(fd.col0 + k)]] != u;
+        if (mixed && allow_shared && fd.f == fd.ns && fd.parent < 0 && !has_child[s]) { fu[s] = (i32)nunits; shared = true; continue; }      // (unit `nunits`: the unit behind the last one, whose flag never says "skip")
+        if (mixed) return bad("the pivot columns of front " + std::to_string(s) + " lie in more than one block");
         for (i32 r = 0; r < fd.f; ++r)
             if (node_unit[(size_t)S.perm[(size_t)S.rowidx[(size_t)(fd.rowoff + r)]]] != u) return bad("the rows of front " + std::to_string(s) + " lie in more than one block");
         fu[s] = u;
@@ -1372,6 +1377,7 @@ int skip_build_units(tlpk_handle *h, const std::vector<i32> &row_unit, const std
     for (size_t i = 0; i < nsg; ++i) fu[nf + i] = fu[(size_t)S.sn_of_col[(size_t)S.single_col[i]]];
     h->front_unit.swap(fu);
     h->skip_units = nunits;
+    h->units_shared = shared;
     return TLPK_OK;
 }
 int skip_device_tables(tlpk_handle *h) {

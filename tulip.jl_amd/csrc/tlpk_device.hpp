@@ -20,7 +20,8 @@ struct DevCtx {
     double *xw;         // permuted right-hand side / solution
     double *dinv;       // inverses of the NB_IN x NB_IN diagonal blocks of L (written by k_potrf)
     double *spart;      // split-K scratch: one TILE x TILE partial product per slot
-    int *info;          // info[0] = smallest failing pivot column (INT_MAX = none); info[1] != 0: a sweep gave up waiting
+    int *info;          // info[0] = smallest failing pivot column (INT_MAX = none); info[1] != 0: a sweep gave up waiting; info[INFO_WORDS + col] = col for every
+                        // column that info[0] was offered (kernels.hip: record_fail) -- the marks the per-LP pivot verdicts are folded from
     int upd_remap;         // k_update blockIdx -> task mapping (0 identity, 1 XCD-contiguous, 2 runs of 64 tasks per XCD)
     const double *csign;   // K2 (augmented system): +1 / -1 per permuted column, the S of P K P' = L S L'; nullptr for K1
     const i32 *upd_seg;    // K-segment lists of the update tasks (UpdateTask.seg)
@@ -31,6 +32,7 @@ struct DevCtx {
     const unsigned char *eg_front; const i64 *eg_base, *eg_col, *eg_ptr; const EaGatherEnt *eg_ent; i32 eg_cap;
     const unsigned char *front_skip;   // block skip (tlpk_block_skip / tlpk_ipm_batch_skip): nullptr = no mask; else != 0 per front (then per single) that this update / solve leaves out
 };
+constexpr int INFO_WORDS = 16;   // status and diagnostic words of DevCtx.info, in front of its m mark words
 
 // per-launch arguments of the persistent sweep kernels
 struct SweepArgs {
@@ -97,7 +99,11 @@ struct DevArrays {
     i64 n_fronts = 0;
     i32 *front_unit = nullptr, *asm_front = nullptr;
     unsigned char *skip_bytes = nullptr, *unit_skip = nullptr;
+    // per-LP pivot verdicts, allocated by the first tlpk_ipm_batch_factor_each: the LP of every permuted column; the smallest marked column per LP (FAIL_NONE:
+    // none), written by k_fold_fail after an update that failed.  The marks themselves are the m words behind ctx.info's first INFO_WORDS, set to FAIL_NONE before the update
+    int *unit_fail = nullptr; i32 *col_unit = nullptr;
 };
+constexpr int FAIL_NONE = 0x7f7f7f7f;   // (what hipMemsetAsync(0x7f) leaves: above every column)
 
 void launch_compute_d(hipStream_t st, i64 n, const double *theta, const double *regP, double *D);
 // part: -1 = everything, 0 = the lower fronts only, 1 = the upper fronts only (schedule.cpp, step 13d)
@@ -107,6 +113,8 @@ void launch_tasks(hipStream_t st, const DevArrays &a, const Launch &L, const Swe
 void launch_single_factor(hipStream_t st, const DevArrays &a);
 // a.skip_bytes from the units' bytes (unit_skip, != 0 = skipped) or from the units' flags (unit_active[k * stride], 0.0 = skipped); one of the two is null
 void launch_expand_skip(hipStream_t st, const DevArrays &a, const unsigned char *unit_skip, const double *unit_active, int stride);
+// a.unit_fail[u] = the smallest marked column of unit u (a.unit_fail holds FAIL_NONE before)
+void launch_fold_fail(hipStream_t st, const DevArrays &a);
 // The per-right-hand-side kernels of a solve: nrhs = 1, or 2 for a pair (ONE launch each where the kernel has a grid-y form, grid y = right-hand side; slots
 // 0 .. nrhs - 1 of xw); the pointer arrays hold nrhs entries.  dy_shared / local_only: shards of a multi-device handle publishing into the lead's vectors (nrhs = 1)
 void launch_single_solve(hipStream_t st, const DevArrays &a, int nrhs = 1);

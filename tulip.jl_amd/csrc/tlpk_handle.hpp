@@ -115,6 +115,7 @@ struct tlpk_handle {
     std::vector<i32> front_unit;        // unit of every front, then of every single (the order of S.single_col); empty = not built yet
     i64 skip_units = 0;                 // number of units the table was built for
     bool skip_units_batch = false;      // ... and whether they are the LPs of the batch (tlpk_ipm_batch_skip) or the blocks of row_block (tlpk_block_skip)
+    bool units_shared = false;          // the table holds fronts of unit `skip_units`: shared by several units, never skipped (tlpk_ipm_batch_factor_each's holds only)
     std::vector<unsigned char> skip_host;   // tlpk_block_skip: the bytes in force per front and then per single; empty = no mask
     i64 skip_dev_bytes = 0;             // device memory of the tables (tlpk_symbolic_get "skip_bytes")
     bool batch_skip = false;            // tlpk_ipm_batch_skip(h, 1)
@@ -124,7 +125,9 @@ struct tlpk_handle {
 // K2), verified -- TLPK_BADARG with a sentence and nothing changed if a front is not contained in one unit.  skip_device_tables: the device copies, once.
 // skip_from_flags: the mask of the NEXT update / solves from per-unit flags in device memory (flag[k * stride] == 0.0 -> unit k is skipped), enqueued on the
 // handle's stream; skip_off: no mask (the tables stay)
-int skip_build_units(tlpk_handle *h, const std::vector<i32> &row_unit, const std::vector<i32> &col_unit, i64 nunits, const char *what);
+// allow_shared: a front whose columns lie in several units is accepted, with unit `nunits` (one behind the last: the caller's flags never skip it), if it stands alone -- no rows below its pivot block and no
+// children, so that it neither feeds nor is fed by a front that a mask leaves out (K2: the root front of the columns of A without entries)
+int skip_build_units(tlpk_handle *h, const std::vector<i32> &row_unit, const std::vector<i32> &col_unit, i64 nunits, const char *what, bool allow_shared = false);
 int skip_device_tables(tlpk_handle *h);
 int skip_from_flags(tlpk_handle *h, const double *d_flag, int stride);
 void skip_off(tlpk_handle *h);

@@ -50,6 +50,8 @@ struct IpmBatchState {
     // tlpk_ipm_get_lps, allocated by its first call and grown by a later, larger one: the device staging of the gathered segments and the segment table (device / pinned)
     double *d_stage = nullptr; i64 stage_cap = 0;
     IpmGatherSeg *d_tab = nullptr, *h_tab = nullptr; i64 tab_cap = 0;
+    // tlpk_ipm_batch_factor_each, allocated by its first call with the device tables (DevArrays.fail_words ...): the pinned copy of the per-LP verdicts
+    int *h_fail = nullptr;
 };
 
 // ---- one device or several ---------------------------------------------------------------------------------------------------
@@ -177,6 +179,7 @@ void ipm_free(tlpk_handle *h) {
         if (bs->h_out) hipHostFree(bs->h_out);
         if (bs->h_sc) hipHostFree(bs->h_sc);
         if (bs->h_tab) hipHostFree(bs->h_tab);
+        if (bs->h_fail) hipHostFree(bs->h_fail);
         if (bs->d_tab) hipFree(bs->d_tab);
         if (bs->d_stage) hipFree(bs->d_stage);
         delete bs;
@@ -877,6 +880,23 @@ i64 batch_owner(const tlpk_handle *h, const IpmBatchState &bs, i64 col) {
     if (old < 0 || old >= off->back()) return -1;
     return (i64)(std::upper_bound(off->begin(), off->end(), old) - off->begin()) - 1;
 }
+// the fronts of every LP, verified (skip_build_units): what tlpk_ipm_batch_skip and a hold of tlpk_ipm_batch_factor_each need before a block can be left out
+int batch_unit_tables(tlpk_handle *h, const IpmBatchState &bs, const char *what, bool allow_shared = false) {
+    if (!h->front_unit.empty() && h->skip_units_batch && (allow_shared || !h->units_shared)) return TLPK_OK;
+    // (a table that tlpk_block_skip built before the load names the blocks of row_block, which need not be the LPs: rebuilt, and its device copy refreshed)
+    std::vector<i32> ru((size_t)bs.row_off.back()), cu((size_t)bs.col_off.back());
+    for (i64 k = 0; k < bs.nlp; ++k) {
+        std::fill(ru.begin() + bs.row_off[(size_t)k], ru.begin() + bs.row_off[(size_t)k + 1], (i32)k);
+        std::fill(cu.begin() + bs.col_off[(size_t)k], cu.begin() + bs.col_off[(size_t)k + 1], (i32)k);
+    }
+    if (int rc = skip_build_units(h, ru, cu, bs.nlp, what, allow_shared)) return rc;
+    h->skip_units_batch = true;
+    if (h->d.front_unit) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(h->d.front_unit, h->front_unit.data(), h->front_unit.size() * sizeof(i32), hipMemcpyHostToDevice));
+    }
+    return TLPK_OK;
+}
 // tlpk_ipm_batch_skip: the update / the solves enqueued while a MaskScope lives leave out the LPs whose flag in the call's scalar block is 0 -- the copy
 // batch_scalars has just enqueued, expanded per front on the same stream; no mask is in force once the scope ends
 struct MaskScope {
@@ -996,8 +1016,10 @@ int tlpk_ipm_load_batch(tlpk_handle *h, int64_t nlp, const int64_t *row_off, con
             }
             if (int r = dev_alloc(h, &p, 2 * nlp * IPM_SLOTS)) return r;
             HIPCHK(h, hipMemset(p, 0, (size_t)(2 * nlp * IPM_SLOTS) * 8)); bs->d_out = p;
-            if (int r = dev_alloc(h, &p, nlp * IPM_BSC)) return r;
+            // (one row more than LPs, all ones and never overwritten: the flags of the unit that fronts shared by several LPs belong to -- batch_unit_tables)
+            if (int r = dev_alloc(h, &p, (nlp + 1) * IPM_BSC)) return r;
             HIPCHK(h, hipMemset(p, 0, (size_t)(nlp * IPM_BSC) * 8)); bs->d_sc = p; B.sc = p;
+            { const std::vector<double> ones((size_t)IPM_BSC, 1.0); HIPCHK(h, hipMemcpy(p + nlp * IPM_BSC, ones.data(), IPM_BSC * 8, hipMemcpyHostToDevice)); }
             for (int g = 0; g < 2; ++g) {
                 if (int r = dev_alloc(h, &p, n)) return r;
                 HIPCHK(h, hipMemset(p, 0, (size_t)std::max<i64>(n, 1) * 8)); bs->sx[g] = p;
@@ -1054,6 +1076,76 @@ int tlpk_ipm_batch_factor(tlpk_handle *h, const uint8_t *active, const double *r
     return rc;
 }
 
+/* One update with a role per LP and a verdict per LP (include/tlpk.h; DESIGN.md section 4b'-v).  The pivot kernels mark every column they report
+ * (the words behind DevCtx.info's status words); only an update whose status word says "failed" pays the fold of the marks and the copy of the nlp verdicts. */
+int tlpk_ipm_batch_factor_each(tlpk_handle *h, const uint8_t *role, const double *regP, const double *regD, int64_t *fail_col, int64_t *nfail) {
+    const char *me = "tlpk_ipm_batch_factor_each";
+    if (!h) return TLPK_BADARG;
+    if (!h->ipm) { h->last_error = "tlpk_ipm_load_batch has not been called (load first)"; return TLPK_BADARG; }
+    if (!h->ipm->bat) { h->last_error = "the handle holds one LP (tlpk_ipm_load): the tlpk_ipm_batch_* calls need tlpk_ipm_load_batch"; return TLPK_BADARG; }
+    if (!role || !regP || !regD || !fail_col || !nfail) { h->last_error = std::string(me) + ": a NULL pointer"; return TLPK_BADARG; }
+    IpmBatchState &bs = *h->ipm->bat;
+    const i64 nlp = bs.nlp;
+    bool hold = false;
+    for (i64 k = 0; k < nlp; ++k) {
+        if (role[k] > 3) {
+            h->last_error = std::string(me) + ": LP " + std::to_string(k) + " has role " + std::to_string((int)role[k]) + " (0 parked, 1 active, 2 hold, 3 entering)";
+            return TLPK_BADARG;
+        }
+        hold = hold || role[k] == 2;
+    }
+    if (h->ipm_stale) {
+        h->last_error = "the matrix values changed (tlpk_set_values) after the LPs were loaded: call tlpk_ipm_reload before the device-resident loops";
+        return TLPK_BADARG;
+    }
+    if (hold) {      // a held block is left out of the update: the conditions of tlpk_ipm_batch_skip
+        // (both sentences start with "...: hold refused": what the loops of batch_retry.py tell from every other TLPK_BADARG)
+        if (h->refine_steps > 0) { h->last_error = std::string(me) + ": hold refused: refine_steps > 0: the norms of the refinement run over all rows"; return TLPK_BADARG; }
+        // (a front that LPs share and that stands alone is tolerated: it is factorised by every call, from values that a held LP's segments still hold)
+        if (int rc = batch_unit_tables(h, bs, "tlpk_ipm_batch_factor_each: hold refused", true)) return rc;
+    }
+    if (!h->has_device) return TLPK_NO_DEVICE;
+    for (i64 k = 0; k < nlp; ++k) fail_col[k] = -1;
+    *nfail = 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevArrays &d = h->d;
+    if (!d.unit_fail) {
+        std::vector<i32> cu((size_t)h->S.m);
+        for (i64 j = 0; j < h->S.m; ++j) cu[(size_t)j] = (i32)batch_owner(h, bs, j);
+        i32 *dcu = nullptr; int *uf = nullptr;
+        if (int rc = dev_upload(h, &dcu, cu)) return rc;
+        if (int rc = dev_alloc(h, &uf, nlp)) return rc;
+        if (!bs.h_fail) HIPCHK(h, hipHostMalloc((void **)&bs.h_fail, (size_t)nlp * sizeof(int), hipHostMallocDefault));
+        d.col_unit = dcu; d.unit_fail = uf;
+    }
+    // the scalars: regP, regD (read for the active LPs only), the flag the mask is expanded from (1 = this update factorises the block), the role
+    const bool masked = hold || h->batch_skip;
+    for (i64 k = 0; k < nlp; ++k) {
+        double *row = bs.h_sc + (size_t)k * IPM_BSC;
+        const int r = role[k];
+        for (int q = 0; q < IPM_BSC; ++q) row[q] = 0.0;
+        if (r == 1) { row[0] = regP[k]; row[1] = regD[k]; }
+        row[2] = (r == 1 || r == 3 || (r == 0 && !h->batch_skip)) ? 1.0 : 0.0;
+        row[IPM_ROLE] = r == 1 ? IPM_ACTIVE : (r == 2 ? IPM_HOLD : (r == 3 ? IPM_ENTERING : IPM_PARKED));
+        row[IPM_BSC - 1] = r == 1 ? 1.0 : 0.0;
+    }
+    HIPCHK(h, hipMemcpyAsync(bs.d_sc, bs.h_sc, (size_t)nlp * IPM_BSC * 8, hipMemcpyHostToDevice, h->stream));
+    ipmb_launch_theta_roles(h->stream, h->ipm->v, bs.B, h->d_theta, h->d_regP, h->d_regD);
+    if (masked) if (int rc = skip_from_flags(h, bs.d_sc + 2, IPM_BSC)) return rc;
+    if (h->S.m > 0) HIPCHK(h, hipMemsetAsync(d.ctx.info + INFO_WORDS, 0x7f, (size_t)h->S.m * sizeof(int), h->stream));      // FAIL_NONE: no column is marked
+    const int rc = tlpk_update_device(h, h->d_theta, h->d_regP, h->d_regD);
+    skip_off(h);
+    if (rc != TLPK_NOT_POSDEF) return rc;
+    HIPCHK(h, hipMemsetAsync(d.unit_fail, 0x7f, (size_t)nlp * sizeof(int), h->stream));
+    launch_fold_fail(h->stream, d);
+    HIPCHK(h, hipMemcpyAsync(bs.h_fail, d.unit_fail, (size_t)nlp * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    for (i64 k = 0; k < nlp; ++k)
+        if (bs.h_fail[k] != FAIL_NONE) { fail_col[k] = bs.h_fail[k]; ++*nfail; }
+    return rc;
+}
+
 int tlpk_ipm_batch_skip(tlpk_handle *h, int on) {
     if (!h) return TLPK_BADARG;
     if (!ipm_is_batch(h)) { h->last_error = "tlpk_ipm_batch_skip: the handle is not batch-loaded (tlpk_ipm_load_batch)"; return TLPK_BADARG; }
@@ -1061,20 +1153,7 @@ int tlpk_ipm_batch_skip(tlpk_handle *h, int on) {
     if (!on) { h->batch_skip = false; return TLPK_OK; }
     const IpmBatchState &bs = *h->ipm->bat;
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->front_unit.empty() || !h->skip_units_batch) {
-        // (a table that tlpk_block_skip built before the load names the blocks of row_block, which need not be the LPs: rebuilt, and its device copy refreshed)
-        std::vector<i32> ru((size_t)bs.row_off.back()), cu((size_t)bs.col_off.back());
-        for (i64 k = 0; k < bs.nlp; ++k) {
-            std::fill(ru.begin() + bs.row_off[(size_t)k], ru.begin() + bs.row_off[(size_t)k + 1], (i32)k);
-            std::fill(cu.begin() + bs.col_off[(size_t)k], cu.begin() + bs.col_off[(size_t)k + 1], (i32)k);
-        }
-        if (int rc = skip_build_units(h, ru, cu, bs.nlp, "tlpk_ipm_batch_skip")) return rc;
-        h->skip_units_batch = true;
-        if (h->d.front_unit) {
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            HIPCHK(h, hipMemcpy(h->d.front_unit, h->front_unit.data(), h->front_unit.size() * sizeof(i32), hipMemcpyHostToDevice));
-        }
-    }
+    if (int rc = batch_unit_tables(h, bs, "tlpk_ipm_batch_skip")) return rc;
     if (int rc = skip_device_tables(h)) return rc;
     h->batch_skip = true;
     return TLPK_OK;

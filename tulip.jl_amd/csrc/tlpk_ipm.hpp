@@ -91,6 +91,9 @@ constexpr int IPM_ROLE = IPM_BSC - 2;
 constexpr double IPM_PARKED = 0.0, IPM_ACTIVE = 1.0, IPM_ENTERING = 2.0;
 // theta / regP / regD by role: active as ipmb_launch_theta (sc[0] = regP, sc[1] = regD), parked as it parks, entering as mpcb_launch_fill
 void mpcb_launch_theta_enter(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD);
+// ... and with a fourth role (tlpk_ipm_batch_factor_each): an LP that holds its factor keeps its segments of theta / regP / regD untouched
+constexpr double IPM_HOLD = 3.0;
+void ipmb_launch_theta_roles(hipStream_t st, const IpmVecs &v, const IpmBatch &B, double *theta, double *regP, double *regD);
 // entering LPs only.  mode 0: (xip, xid) = (0, c), the solution goes to (D0.x, y); mode 1: (xip, xid) = (b, 0), the solution goes to (x, D0.y).
 // The take puts the half of the right-hand side it used back to 0, as tlpk_mpc_batch_start leaves it.
 void mpcb_launch_enter_rhs(hipStream_t st, const IpmVecs &v, const IpmBatch &B, int mode);

@@ -22,6 +22,7 @@ import time
 import numpy as np
 
 from . import _lib
+from .batch_retry import check_retry, factor_failed, warn_hold_refused
 from .hsd_device import Options
 from .kkt import K1, K2, Backend, DimensionMismatch, OutOfMemoryError, _raise_for, setup
 
@@ -72,13 +73,17 @@ def stream_assign(free_slots, slot_keys, queue_keys):
 
 
 class BatchedDeviceHSD:
-    def __init__(self, lps, system="K1", options=None, load=True, skip_parked=False, **backend_kw):
+    def __init__(self, lps, system="K1", options=None, load=True, skip_parked=False, retry="all", **backend_kw):
         # options: one Options for every LP, or a sequence with one per LP
         # skip_parked=True: the blocks of the LPs a call's mask leaves out are skipped inside the factorisation and the sweeps (tlpk_ipm_batch_skip); the results
         # of optimize() / optimize_stream() do not depend on it, bit for bit.  Silently off on handles with refine > 0 (the refinement's norms run over all rows).
         # Off by default: with it on, an LP that a tlpk_ipm_batch_factor call left out has NO factor of the parking values -- a caller that drives the
         # tlpk_ipm_batch_* calls itself and solves such an LP gets unspecified values where it used to get the solve against the parked block (the loops here
         # never do that; tests/test_ipm_kernels.py's call-by-call sequences do)
+        # retry="all": an update that fails names one LP, which is bumped, and the whole stack is factorised again.  retry="failed": every LP that failed in
+        # an update is named and bumped (tlpk_ipm_batch_factor_each), the next update factorises those alone and the others keep their factor
+        # (batch_retry.py; DESIGN.md section 4b'-v).  Per LP the two settings give the same run, bit for bit; "failed" falls back to "all", with a warning,
+        # where the library cannot hold a factor (refine > 0, or an ordering that mixes the LPs' fronts)
         # load=False: stop after the analysis (the stacking can be inspected on a machine without a GPU: device=-1)
         # backend_kw: tlpk.Backend's (device, refine, ordering, ...); row_block defaults to the LP index of every row
         import scipy.sparse as sp
@@ -119,6 +124,7 @@ class BatchedDeviceHSD:
                                                     "CorrectionLimit", "StepDampFactor", "GammaMin", "CentralityOutlierThreshold", "PRegMin", "DRegMin")}
         self.time_limit = min(float(o.TimeLimit) for o in options)               # TimeLimit is global
         self.L = _lib.lib()
+        self.retry = check_retry(retry)
         self._host_norms()
         self._init_state()
         self.last_update_rc = None
@@ -177,6 +183,9 @@ class BatchedDeviceHSD:
         self.dual_status = np.array(["Sln_Unknown"] * B, dtype=object)
         self.active = np.zeros(B, dtype=bool)
         self.timers = {name: np.zeros(B, dtype=np.int64) for name in ("n_update", "n_solve", "n_bump", "n_paired", "max_bumps_in_a_step")}
+        self.timers["n_update_calls"] = 0                                    # update calls of the BATCH in this run, under either `retry` (a number, not per LP)
+        self.timers["n_lp_factor"] = 0                                       # ... and the LPs they were asked to factorise, summed over the calls
+        self.bump_log = []                                                   # per pass in which an update failed: how often each LP was bumped in it
         self.rho = np.zeros((B, 3))
         for name in ("rp_nrm", "rl_nrm", "ru_nrm", "rd_nrm", "cx", "xz", "ax_nrm", "xxl_nrm", "xxu_nrm", "delta_nrm", "dualsum", "rg_nrm",
                      "primal_objective", "dual_objective"):
@@ -186,7 +195,7 @@ class BatchedDeviceHSD:
 
     def timers_of(self, k):
         """The timers of LP k as `DeviceHSD.timers` holds them."""
-        return {name: int(v[k]) for name, v in self.timers.items()}
+        return {name: int(v[k]) for name, v in self.timers.items() if isinstance(v, np.ndarray)}
 
     def reload(self, b=None, c=None, l=None, u=None, c0=None):
         """New stacked vectors on the analysed handle (None = keep; bounds may change between finite and infinite): tlpk_ipm_reload
@@ -235,12 +244,14 @@ class BatchedDeviceHSD:
             raise ValueError(f"{what}: one Options object, or one per LP")
         return options
 
-    def refill(self, slots, lps, options=None):
+    def refill(self, slots, lps, options=None, retry=None):
         """New LPs for the listed slots of the analysed handle (tlpk_ipm_batch_refill): lps[i] replaces the LP of slots[i] -- matrix values, b, c, l,
         u, c0, objective sense, options (default: `Options()`) -- and starts from the HSD starting point with its host state (tau, kappa, mu,
         regularisations, niter, statuses, timers, recorded norms) re-initialised; every other slot continues untouched.  An LP whose pattern
         (shape, column pointers, row indices) differs from its slot's raises ValueError, and nothing is changed."""
         self._hsd_only("refill")
+        if retry is not None:                                                # (how the updates after the refill retry: the constructor's `retry`)
+            self.retry = check_retry(retry)
         slots = [int(k) for k in slots]
         lps = list(lps)
         if len(slots) != len(lps) or len(set(slots)) != len(slots) or any(not 0 <= k < self.nlp for k in slots):
@@ -333,7 +344,8 @@ class BatchedDeviceHSD:
         self.status[k] = "Trm_Unknown"; self.primal_status[k] = "Sln_Unknown"; self.dual_status[k] = "Sln_Unknown"
         self.active[k] = False
         for v in self.timers.values():
-            v[k] = 0
+            if isinstance(v, np.ndarray):
+                v[k] = 0
         self.rho[k] = 0.0
         for name in ("rp_nrm", "rl_nrm", "ru_nrm", "rd_nrm", "cx", "xz", "ax_nrm", "xxl_nrm", "xxu_nrm", "delta_nrm", "dualsum", "rg_nrm",
                      "primal_objective", "dual_objective"):
@@ -419,6 +431,8 @@ class BatchedDeviceHSD:
 
     def _factor(self, step):
         """The per-LP retry loop of the update (step.jl:35-51) for the LPs of `step`; returns the LPs that hold a factor."""
+        if self.retry == "failed":
+            return factor_failed(self, step, np.zeros(self.nlp, dtype=bool), self._factor_each)[0]
         B = self.nlp
         step = step.copy()
         nbump = np.zeros(B, dtype=np.int64)
@@ -426,6 +440,8 @@ class BatchedDeviceHSD:
         while step.any():                                                    # step.jl:35-51, per LP
             rc = self.L.tlpk_ipm_batch_factor(self.kkt._h, self._mask(step), _lib.as_pd(self.regP), _lib.as_pd(self.regD), C.byref(fail))
             self.last_update_rc = rc
+            self.timers["n_update_calls"] += 1
+            self.timers["n_lp_factor"] += int(step.sum())
             if rc == _lib.OK:
                 self.timers["n_update"][step] += 1
                 break
@@ -445,7 +461,26 @@ class BatchedDeviceHSD:
             self.status[gone] = "Trm_NumericalProblem"
             step &= ~gone
         self.timers["max_bumps_in_a_step"] = np.maximum(self.timers["max_bumps_in_a_step"], nbump)
+        if nbump.any():
+            self.bump_log.append(nbump.copy())
         return step
+
+    def _factor_each(self, role):
+        """One tlpk_ipm_batch_factor_each with the roles of batch_retry.factor_failed: (rc, fail_col)."""
+        role = np.ascontiguousarray(role, dtype=np.uint8)
+        fail_col = np.full(self.nlp, -1, dtype=np.int64)
+        nfail = C.c_int64(0)
+        rc = self.L.tlpk_ipm_batch_factor_each(self.kkt._h, _lib.as_pu8(role), _lib.as_pd(self.regP), _lib.as_pd(self.regD), _lib.as_p64(fail_col), C.byref(nfail))
+        return rc, fail_col
+
+    def _last_error(self):
+        return self.L.tlpk_last_error(self.kkt._h).decode()
+
+    def _hold_refused(self):
+        """The library refused a hold (batch_retry.factor_failed): this object retries with whole updates from here on, and says so once."""
+        if self.retry == "failed":
+            self.retry = "all"
+            warn_hold_refused(self, self._last_error())
 
     def _direction_and_move(self, step):
         o, B = self._o, self.nlp
@@ -542,7 +577,7 @@ class BatchedDeviceHSD:
         return self._vec(what)[off[k]:off[k + 1]].copy()
 
     # ---- a batch that keeps going (DESIGN.md section 4b'-r) ----
-    def optimize_stream(self, lps, options=None):
+    def optimize_stream(self, lps, options=None, retry=None):
         """N LPs through the B slots of this handle: the LPs of the constructor are the first occupants, `lps` is the queue.  When an LP leaves
         (decided, iteration limit, numerical problem) its record is read through tlpk_ipm_get_lps and, at the top of the next pass, its slot takes
         the first LP of the queue whose pattern is the slot's (`stream_assign`; `refill`) while every other slot continues untouched.  The
@@ -552,6 +587,8 @@ class BatchedDeviceHSD:
         returns, plus zl, zu and the homogeneous iterate xh, yh as the device holds them, tau, timers, the slot the LP ran in and the
         passes (1-based) in which it entered and left.  A queue LP that matches no slot raises ValueError before anything runs."""
         self._hsd_only("optimize_stream")
+        if retry is not None:                                                # (the constructor's `retry`, for this run and the following ones)
+            self.retry = check_retry(retry)
         B = self.nlp
         queue, qopts, slot_keys, qkeys = self._stream_queue(lps, options)
         N = len(queue)

@@ -118,12 +118,13 @@ class Model:
         return self
 
     @classmethod
-    def optimize_batch(cls, models, slots=None, skip_parked=False, **kw):
+    def optimize_batch(cls, models, slots=None, skip_parked=False, retry="all", **kw):
         """`optimize()` of many models in one set of launches (hsd_batch.BatchedDeviceHSD, or mpc_batch.BatchedDeviceMPC where every model
         has algorithm="mpc"): each model is presolved and brought to standard form on its own, ONE batched interior-point run solves the LPs
         presolve did not already finish, each is postsolved, and every model ends as after its own `optimize()`.
         kw: the backend's keywords (system=, device=, ...; default: those of the first model).
         skip_parked=True: the batch leaves the blocks of finished LPs out of its factorisations and sweeps (the results do not depend on it).
+        retry="failed": after an update in which LPs met a bad pivot only those are factorised again (the results do not depend on it either).
         slots=B: the LPs STREAM through handles of at most B slots (BatchedDeviceHSD.optimize_stream) -- the models that reach the interior-point
         method are grouped by the pattern of their standard form, each group runs through one handle of min(B, group size) slots, and a slot whose
         LP is decided takes the group's next one.  The homogeneous self-dual loop only: algorithm="mpc" with slots raises ValueError
@@ -133,7 +134,7 @@ class Model:
             if any(mdl.algorithm != "hsd" for mdl in models):
                 raise ValueError("optimize_batch(slots=...) streams through the homogeneous self-dual loop: every model must have algorithm='hsd' "
                                  "(algorithm='mpc': use Model.optimize_stream, which streams Mehrotra's loop too)")
-            return cls._optimize_stream(models, int(slots), kw, skip_parked, "optimize_batch")
+            return cls._optimize_stream(models, int(slots), kw, skip_parked, "optimize_batch", retry)
         algorithms = {mdl.algorithm for mdl in models}
         if len(algorithms) > 1:
             raise ValueError(f"optimize_batch runs ONE interior-point loop for the whole batch: the models mix the algorithms {sorted(algorithms)}")
@@ -156,7 +157,7 @@ class Model:
                 lp_inner = ps.reduced_problem()
             pending.append((mdl, lp_inner))
         if pending:
-            opt = Batched([standard_form(lp) for _, lp in pending], skip_parked=skip_parked, **(kw or models[0].backend_kw)).optimize()
+            opt = Batched([standard_form(lp) for _, lp in pending], skip_parked=skip_parked, retry=retry, **(kw or models[0].backend_kw)).optimize()
             for k, (mdl, lp_inner) in enumerate(pending):
                 res = mdl.inner = InnerResult(str(opt.status[k]), str(opt.primal_status[k]), str(opt.dual_status[k]), opt._get(k, 0), opt._get(k, 5),
                                               opt._get(k, 3), opt._get(k, 4), float(opt.tau[k]), float(opt.primal_objective[k]),
@@ -168,23 +169,25 @@ class Model:
         return models
 
     @classmethod
-    def optimize_stream(cls, models, slots, skip_parked=False, **kw):
+    def optimize_stream(cls, models, slots, skip_parked=False, retry="all", **kw):
         """`optimize()` of many models through handles of at most `slots` slots, whatever their algorithms: the models that reach the interior-point
         method are grouped by algorithm ("hsd" | "mpc") and by the pattern of their standard form, each group streams through one handle of
         min(slots, group size) slots (BatchedDeviceHSD.optimize_stream / BatchedDeviceMPC.optimize_stream), and every model ends as after its own
-        `optimize()`.  kw: the backend's keywords (default: those of the first model); skip_parked as in `optimize_batch`."""
+        `optimize()`.  kw: the backend's keywords (default: those of the first model); skip_parked and retry as in `optimize_batch`."""
         models = list(models)
         if isinstance(slots, bool) or not isinstance(slots, (int, np.integer)):
             raise TypeError("optimize_stream: slots is the number of slots of a handle (an integer)")
         for mdl in models:
             if not isinstance(mdl, Model):
                 raise TypeError("optimize_stream: models is a sequence of Model objects")
-        return cls._optimize_stream(models, int(slots), kw, skip_parked, "optimize_stream")
+        return cls._optimize_stream(models, int(slots), kw, skip_parked, "optimize_stream", retry)
 
     @classmethod
-    def _optimize_stream(cls, models, slots, kw, skip_parked=False, who="optimize_batch"):
+    def _optimize_stream(cls, models, slots, kw, skip_parked=False, who="optimize_batch", retry="all"):
         from .hsd_batch import BatchedDeviceHSD, pattern_key
+        from .batch_retry import check_retry
         from .mpc_batch import BatchedDeviceMPC
+        check_retry(retry)
         if slots < 1:
             raise ValueError(f"{who}: slots must be at least 1")
         if any(mdl.algorithm not in ("hsd", "mpc") for mdl in models):
@@ -205,7 +208,7 @@ class Model:
         for (algorithm, _), group in groups.items():
             nslots = min(slots, len(group))
             Batched = BatchedDeviceMPC if algorithm == "mpc" else BatchedDeviceHSD
-            opt = Batched([d for _, _, d in group[:nslots]], skip_parked=skip_parked, **(kw or models[0].backend_kw))
+            opt = Batched([d for _, _, d in group[:nslots]], skip_parked=skip_parked, retry=retry, **(kw or models[0].backend_kw))
             records = opt.optimize_stream([d for _, _, d in group[nslots:]])
             for (mdl, lp_inner, _), r in zip(group, records):
                 res = mdl.inner = InnerResult(r["status"], r["primal_status"], r["dual_status"], r["xh"], r["yh"], r["zl"], r["zu"], r["tau"],

@@ -27,6 +27,7 @@ import time
 import numpy as np
 
 from . import _lib
+from .batch_retry import check_retry, factor_failed
 from .hsd_batch import _DECIDED, BatchedDeviceHSD, stream_assign
 from .hsd_device import SQRT_EPS
 from .kkt import OutOfMemoryError
@@ -90,6 +91,8 @@ class BatchedDeviceMPC(BatchedDeviceHSD):
         out = np.zeros(self.nlp)
         self._call(self.L.tlpk_mpc_batch_start(self.kkt._h, _lib.as_pd(out)))
         self.timers["n_update"] += 1
+        self.timers["n_update_calls"] += 1
+        self.timers["n_lp_factor"] += self.nlp
         self.timers["n_solve"] += 2
         self.mu = self._per_p(out)
 
@@ -206,6 +209,8 @@ class BatchedDeviceMPC(BatchedDeviceHSD):
         nothing to bump.  The others retry as in `_factor`."""
         if not enter.any():
             return self._factor(step), enter.copy()
+        if self.retry == "failed":
+            return factor_failed(self, step, enter, self._factor_each)
         B = self.nlp
         step, enter, entering = step.copy(), enter.copy(), enter.copy()
         nbump = np.zeros(B, dtype=np.int64)
@@ -214,6 +219,8 @@ class BatchedDeviceMPC(BatchedDeviceHSD):
             s8, e8 = np.ascontiguousarray(step, dtype=np.uint8), np.ascontiguousarray(enter, dtype=np.uint8)
             rc = self.L.tlpk_mpc_batch_factor_enter(self.kkt._h, _lib.as_pu8(s8), _lib.as_pu8(e8), _lib.as_pd(self.regP), _lib.as_pd(self.regD), C.byref(fail))
             self.last_update_rc = rc
+            self.timers["n_update_calls"] += 1
+            self.timers["n_lp_factor"] += int((step | enter).sum())
             if rc == _lib.OK:
                 self.timers["n_update"][step | enter] += 1
                 break
@@ -238,6 +245,8 @@ class BatchedDeviceMPC(BatchedDeviceHSD):
             self.status[gone] = "Trm_NumericalProblem"
             step &= ~gone; enter &= ~gone
         self.timers["max_bumps_in_a_step"] = np.maximum(self.timers["max_bumps_in_a_step"], np.where(entering, 0, nbump))
+        if nbump.any():
+            self.bump_log.append(nbump.copy())
         return step, enter
 
     def _evict(self, k):
@@ -279,23 +288,25 @@ class BatchedDeviceMPC(BatchedDeviceHSD):
             self._enter_finish(enter)
         return step, enter
 
-    def refill(self, slots, lps, options=None):
+    def refill(self, slots, lps, options=None, retry=None):
         """`BatchedDeviceHSD.refill`, then Mehrotra's starting point for those slots alone (no LP is active in the four calls, the new ones enter).  An LP
         whose starting matrix cannot be factorised ends Trm_NumericalProblem."""
-        super().refill(slots, lps, options)
+        super().refill(slots, lps, options, retry=retry)
         enter = np.zeros(self.nlp, dtype=bool)
         enter[[int(k) for k in slots]] = True
         with np.errstate(all="ignore"):
             self._step_stream(np.zeros(self.nlp, dtype=bool), enter)
         return self
 
-    def optimize_stream(self, lps, options=None):
+    def optimize_stream(self, lps, options=None, retry=None):
         """`BatchedDeviceHSD.optimize_stream` for Mehrotra's loop: the same records, the same FIFO schedule (`stream_assign`), options that travel with the LP,
         `passes`, `refills`, `refill_seconds`, `record_seconds` (and `enter_finish_seconds`).  An LP found decided in pass p leaves in pass p; its slot is
         refilled straight after the leaves of that pass and the new LP is ENTERING for the rest of it (module docstring), active from pass p + 1 -- the pass its
         record names as `entered`.  A slot so holds an LP for niter + 1 passes.  An entering LP whose starting matrix fails the update gets
         Trm_NumericalProblem with niter 0 (entered = left = p) and frees its slot."""
         B = self.nlp
+        if retry is not None:
+            self.retry = check_retry(retry)
         queue, qopts, slot_keys, qkeys = self._stream_queue(lps, options)
         N = len(queue)
         tstart = time.perf_counter()
