@@ -143,7 +143,7 @@ typedef struct tlpk_stats {
                                   (2 per product); 0 on sparse handles */
     /* matrix-free handles (tlpk_options.krylov); 0 on every other handle.  (Placed in front of the tlpk_set_values pair, which stays the tail of the struct;
        tlpk_stats carries no size field, so any new field means a rebuild of the callers wherever it goes.) */
-    int64_t krylov_iters;        /* CG / MINRES / TriCG iterations of the last solve */
+    int64_t krylov_iters;        /* CG / MINRES / TriCG iterations of the last solve (after tlpk_solve2_device: of its second right-hand side, like the next three) */
     int64_t krylov_iters_total;  /* since the last update */
     int64_t krylov_converged;    /* 1 = the last solve met the stopping rule; 0 = it stopped at itmax or broke down */
     double  krylov_resid0, krylov_resid;   /* sqrt(r' M^-1 r) at x = 0 and at exit of the last solve (MINRES: beta1 and phibar, the recurrence's value of it; TriCG: rho_0 and rho_k, the
@@ -199,7 +199,24 @@ int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr,
  *            (spd.jl:100-101 does not look at the outcome): tlpk_stats.krylov_converged / krylov_iters / krylov_resid say what happened -- a caller that
  *            needs a solved system must read them.  The number of launches depends on the data, so tlpk_solve_device on such a handle BLOCKS until the outcome
  *            is known (iterations are enqueued in chunks, the host reads the outcome word between chunks); dx / dy are complete after tlpk_sync as usual.
- *            tlpk_solve2_device is two solves.  Two solves of the same data are bit-identical (no atomics, ordered reductions).
+ *            Two solves of the same data are bit-identical (no atomics, ordered reductions).
+ *   pair   : tlpk_solve2_device runs BOTH right-hand sides through one sequence of launches (all three methods, with and without Jacobi): one pass over A per
+ *            iteration, one set of launches and one host round trip per chunk for the two systems.  Each right-hand side has its own scalar block,
+ *            tolerance, outcome and counters and stops on its own; one that is solved, broken down or at itmax is parked (nothing of it is read or
+ *            written any more) while the launches go on for the other.  dx, dy, iterations, outcome, resid0 and resid of each one are bit for bit those
+ *            of tlpk_solve_device on it alone.  The statistics read as after the two solves one behind the other: krylov_iters / krylov_converged /
+ *            krylov_resid0 / krylov_resid describe the SECOND right-hand side, krylov_iters_total grows by both counts, "krylov_unsolved" by the number
+ *            that did not meet the rule; launches_solve is that of the pair, 5 + 4 per round (CG; 3 per round when n = 0) or 2 + 3 per round (MINRES, TriCG),
+ *            which is the count of the single solve of the longer one.  What the pair itself did:
+ *              tlpk_symbolic_get(h, "krylov_pair")           7 entries: paired solves since create, pairs that fell back to two solves since create; of the last
+ *                                                            pair the iterations of number 0 and 1, their outcome codes (1 solved, 2 itmax, 3 breakdown), the
+ *                                                            rounds of launches enqueued
+ *              tlpk_symbolic_get_f64(h, "krylov_pair_resid") 4 entries: resid0, resid of number 0, then of number 1
+ *            (zeros before the first pair and on every other handle).  The second set of vectors (CG: 3 of order m and 1 of order n; MINRES: 6 of order
+ *            n + m, 8 with Jacobi; TriCG: 6) is allocated by the FIRST pair, not at create: mem_budget_bytes and the footprint of a handle that never
+ *            pairs are unchanged.  If that allocation fails or would cross mem_budget_bytes, every pair runs as two solves (counted above).
+ *            TLPK_KRYLOV_PAIR=0 in the environment at create keeps the two solves.  Device pointers only; the buffers follow the rule stated at
+ *            tlpk_solve2_device.
  *   tlpk_set_values* refreshes the copies of A; the device-resident loops (tlpk_ipm_*, tlpk_mpc_*) run through the same solve path.
  * opt->krylov = TLPK_KRYLOV_MINRES with opt->system = TLPK_SYSTEM_K2 (the reference's src/KKT/Krylov/sid.jl) is the same handle -- the same analysis, refusals,
  * identity permutation (of the n + m nodes of K2: tlpk_get_perm writes n + m entries, as on a direct K2 handle), tlpk_set_values*, loops, blocking solve, chunked enqueue and stats fields -- with preconditioned MINRES (Paige & Saunders) on the
@@ -289,7 +306,10 @@ int tlpk_solve_device(tlpk_handle *h, double *d_dx, double *d_dy, const double *
 int tlpk_update_device_async(tlpk_handle *h, const double *d_theta_inv, const double *d_regP, const double *d_regD);
 /* Two right-hand sides in one pass over the factor (the solve sweeps are HBM-bound on the bytes of L: the pair costs little more than
  * one solve).  Same semantics and bit-identical results as two tlpk_solve_device calls.  Single-rank handles.  Tulip's HSD iteration
- * has such a pair: the h-system and the predictor (HSD/step.jl:63,79); tlpk_ipm_hsolve_newton uses it. */
+ * has such a pair: the h-system and the predictor (HSD/step.jl:63,79); tlpk_ipm_hsolve_newton uses it.  On a matrix-free handle
+ * (tlpk_options.krylov) the pair is one sequence of launches for both iterations (see "pair" there).
+ * Buffers: the four outputs are distinct from each other and from every input; the inputs may alias each other (the same right-hand
+ * side may be given twice). */
 int tlpk_solve2_device(tlpk_handle *h, double *d_dx0, double *d_dy0, const double *d_xi_p0, const double *d_xi_d0,
                        double *d_dx1, double *d_dy1, const double *d_xi_p1, const double *d_xi_d1);
 int tlpk_sync(tlpk_handle *h);
@@ -359,7 +379,8 @@ int tlpk_set_profile(tlpk_handle *h, int on);   /* toggle per-launch HIP-event t
 int tlpk_get_perm(const tlpk_handle *h, int64_t *perm /*m, 0-based, perm[new] = old*/);   /* dense_cols: the constraint nodes in their order
                                                    (the whole order-(m + k) permutation: tlpk_symbolic_get(h, "perm"), node m + t = dense column t) */
 /* Symbolic structures, for tests and tools.  `what` selects an array; returns its length and,
- * if buf != NULL, copies min(len, cap) int64 entries.  One key is a counter, not a structure: "krylov_unsolved" (matrix-free handles; see tlpk_stats).
+ * if buf != NULL, copies min(len, cap) int64 entries.  One key is a counter, not a structure: "krylov_unsolved" (matrix-free handles; see tlpk_stats); "krylov_pair" holds the
+ * counters of tlpk_solve2_device on such a handle (see "pair" at tlpk_options.krylov), and tlpk_symbolic_get_f64 serves "krylov_pair_resid" beside "pair_w".
  * Read-only diagnostics of the launch schedule (tests/test_schedule_identity.py):
  *   "launch_meta"  (stream group, side, pad) of every entry of "factor_launches", then of "fwd_launches", then of "bwd_launches"
  *   "zero_tasks"   (front, first column) of every 64-column panel slice the zero-fill clears

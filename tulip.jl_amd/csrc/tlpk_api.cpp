@@ -676,6 +676,72 @@ static int krylov_upload(tlpk_handle *h) {
     return TLPK_OK;
 }
 
+// The second set of a pair (tlpk_solve2_device), allocated by the first pair and not at create: a handle that never pairs keeps the footprint krylov_bytes
+// states.  Per method the vectors and slot arrays that the iteration writes, the two contiguous scalar blocks and their pinned copy; A, the diagonals and the
+// geometry are shared with the first set.  false: the allocation failed or the handle would cross mem_budget_bytes -- nothing is kept, and the handle stays
+// on two solves per pair (pair_state = -1).
+static double krylov_pair_bytes(const tlpk_handle *h) {
+    const double m = (double)h->S.m, n = (double)h->S.n, N = n + m;
+    const bool jac = h->krylov_precond == TLPK_PRECOND_JACOBI;
+    if (h->krylov == TLPK_KRYLOV_TRICG) return 48.0 * N + 16384.0;                        // w[2], t, x, g[2]
+    if (h->krylov == TLPK_KRYLOV_MINRES) return (jac ? 64.0 : 48.0) * N + 16384.0;        // r[2], u, x, w[2]; Jacobi: z[2]
+    return 24.0 * m + 8.0 * n + 16384.0;                                                  // x, p, q; t
+}
+static bool krylov_pair_alloc(tlpk_handle *h) {
+    if (h->krylov_pair_state != 0) return h->krylov_pair_state > 0;
+    h->krylov_pair_state = -1;
+    if (h->krylov_budget > 0.0 && krylov_bytes(h) + krylov_pair_bytes(h) > h->krylov_budget) return false;
+    const i64 m = h->S.m, n = h->S.n, N = n + m;
+    const bool jac = h->krylov_precond == TLPK_PRECOND_JACOBI;
+    const size_t mark = h->allocs.size();
+    const i64 bytes0 = h->device_bytes;
+    const std::string err0 = h->last_error;
+    int rc;
+    size_t pin_bytes;
+    if (h->krylov == TLPK_KRYLOV_TRICG) {
+        const TcArrays &c = h->tc;
+        TcArrays &r = h->tc2;
+        r = c; r.sc = nullptr;
+        const KrylovGeom &g = c.geo;
+        if ((rc = alloc_doubles(h, {{&r.w[0], N}, {&r.w[1], N}, {&r.t, N}, {&r.x, N}, {&r.g[0], N}, {&r.g[1], N},
+                                    {&r.slots_a, std::max(1, g.g_cols + g.g_rows + g.g_lcols + g.g_lrows)}, {&r.slots_g, g.g_vec}, {&r.slots_b, g.g_vec}})) == TLPK_OK)
+            rc = dev_alloc(h, &r.sc, 2);
+        pin_bytes = 2 * sizeof(TcScalars);
+    } else if (h->krylov == TLPK_KRYLOV_MINRES) {
+        const MrArrays &c = h->mr;
+        MrArrays &r = h->mr2;
+        r = c; r.sc = nullptr;
+        const KrylovGeom &g = c.geo;
+        if ((rc = alloc_doubles(h, {{&r.r[0], N}, {&r.r[1], N}, {&r.u, N}, {&r.x, N}, {&r.w[0], N}, {&r.w[1], N},
+                                    {&r.slots_a, std::max(1, g.g_cols + g.g_rows + g.g_lcols + g.g_lrows)}, {&r.slots_g, g.g_vec}})) == TLPK_OK)
+            rc = dev_alloc(h, &r.sc, 2);
+        if (rc == TLPK_OK && jac) rc = alloc_doubles(h, {{&r.z[0], N}, {&r.z[1], N}});
+        if (rc == TLPK_OK && !jac) { r.z[0] = r.r[0]; r.z[1] = r.r[1]; }
+        pin_bytes = 2 * sizeof(MrScalars);
+    } else {
+        const CgArrays &c = h->cg;
+        CgArrays &r = h->cg2;
+        r = c; r.sc = nullptr;
+        const KrylovGeom &g = c.geo;
+        if ((rc = alloc_doubles(h, {{&r.x, m}, {&r.p, m}, {&r.q, m}, {&r.t, n}, {&r.slots_r, g.g_rows + g.g_lrows}, {&r.slots_v, g.g_vec}})) == TLPK_OK)
+            rc = dev_alloc(h, &r.sc, 2);
+        pin_bytes = 2 * sizeof(CgScalars);
+    }
+    if (rc == TLPK_OK && hipHostMalloc(&h->krylov_pin2, pin_bytes, hipHostMallocDefault) != hipSuccess) { h->krylov_pin2 = nullptr; rc = TLPK_OOM; }
+    if (rc != TLPK_OK) {
+        (void)hipGetLastError();
+        for (size_t k = mark; k < h->allocs.size(); ++k) hipFree(h->allocs[k]);
+        h->allocs.resize(mark);
+        h->device_bytes = bytes0;
+        h->last_error = err0;
+        h->cg2 = CgArrays(); h->mr2 = MrArrays(); h->tc2 = TcArrays();
+        return false;
+    }
+    std::memset(h->krylov_pin2, 0, pin_bytes);
+    h->krylov_pair_state = 1;
+    return true;
+}
+
 // tlpk_create in two steps (tlpk_create_multi runs the first one once for all shards and the second per device):
 //   create_host   : options -> handle, block detection, host analyse (or: copy of an analysed Symbolic + this rank's part)
 //   create_device : streams / events, memory gate, upload
@@ -891,6 +957,8 @@ int tlpk_create(tlpk_handle **out, int64_t m, int64_t n, const int64_t *colptr, 
         const double se = std::sqrt(std::numeric_limits<double>::epsilon());
         h->krylov_atol = def.krylov_atol > 0.0 ? def.krylov_atol : se;
         h->krylov_rtol = def.krylov_rtol > 0.0 ? def.krylov_rtol : se;
+        if (const char *e = std::getenv("TLPK_KRYLOV_PAIR")) h->krylov_pair_on = std::atoi(e) != 0;
+        h->krylov_budget = def.mem_budget_bytes > 0 ? (double)def.mem_budget_bytes : 0.0;
     }
     try {
         rc = create_host(h, def, m, n, colptr, rowval, nzval, index_base, nullptr);
@@ -1001,6 +1069,7 @@ void tlpk_destroy(tlpk_handle *h) {
         if (h->pin_in) hipHostFree(h->pin_in);
         if (h->pin_out) hipHostFree(h->pin_out);
         if (h->krylov_pin) hipHostFree(h->krylov_pin);
+        if (h->krylov_pin2) hipHostFree(h->krylov_pin2);
         if (h->krylov_ev) hipEventDestroy(h->krylov_ev);
         for (hipEvent_t e : h->io_events) hipEventDestroy(e);
         for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
@@ -1735,12 +1804,16 @@ static int solve_composed(tlpk_handle *h, const SolveIo &io, bool whole) {
 // chunk goes out before the first look (a zero right-hand side is settled by init(), and the chunk behind it returns at once), so a solve that fits the
 // first chunk costs one host round trip.  BLOCKS until the outcome is known and fills the statistics of the solve.  order: of the system, 0 = nothing to
 // iterate on; launches: those the caller accounts for outside iter(k), which returns its own.
+// nr = 2: a pair.  d_sc holds two contiguous blocks, one copy per chunk brings both back (krylov_pin2), a round of launches serves both right-hand sides,
+// and the chunks go on until BOTH outcomes are set: the pair costs the launches of the longer of its two solves.  The statistics read as after the two
+// solves one behind the other (those of the last solve describe number 1); what the pair itself did is kept for tlpk_symbolic_get "krylov_pair".
 extern "C++" template <class Sc, class Init, class Iter>
-static int krylov_run(tlpk_handle *h, const Sc *d_sc, i64 order, const char *method, i64 launches, Init init, Iter iter) {
+static int krylov_run(tlpk_handle *h, const Sc *d_sc, int nr, i64 order, const char *method, i64 launches, Init init, Iter iter) {
     const i64 itmax = h->krylov_itmax;
-    const Sc &sc = *static_cast<const Sc *>(h->krylov_pin);
+    const Sc *sc = static_cast<const Sc *>(nr == 2 ? h->krylov_pin2 : h->krylov_pin);
     { ProfScope ps(h, TLPK_KC_SPMV); init(); }
     i64 enq = 0, chunk = h->krylov_chunk0;
+    bool running = false;
     for (;;) {
         const i64 cnt = order > 0 ? std::min(chunk, itmax - enq) : 0;
         {
@@ -1750,16 +1823,26 @@ static int krylov_run(tlpk_handle *h, const Sc *d_sc, i64 order, const char *met
         HIPCHK(h, hipGetLastError());
         enq += cnt;
         chunk = std::min(chunk * 2, h->krylov_chunk_max);
-        HIPCHK(h, hipMemcpyAsync(h->krylov_pin, d_sc, sizeof(Sc), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(const_cast<Sc *>(sc), d_sc, (size_t)nr * sizeof(Sc), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipEventRecord(h->krylov_ev, h->stream));
         HIPCHK(h, hipEventSynchronize(h->krylov_ev));
-        if (sc.outcome != CG_RUNNING || enq >= itmax || order <= 0) break;
+        running = false;
+        for (int r = 0; r < nr; ++r) running = running || sc[r].outcome == CG_RUNNING;
+        if (!running || enq >= itmax || order <= 0) break;
     }
     // (MINRES and TriCG stamp the deciding iteration into the word above the code)
-    h->krylov_iters = sc.iters; h->krylov_iters_total += sc.iters; h->krylov_converged = (sc.outcome & 0xff) == CG_SOLVED ? 1 : 0;
-    if (!h->krylov_converged) ++h->krylov_unsolved;
-    h->krylov_resid0 = sc.resid0; h->krylov_resid = sc.resid; h->krylov_launches = launches;
-    if (sc.outcome == CG_RUNNING) {
+    for (int r = 0; r < nr; ++r) {
+        h->krylov_iters = sc[r].iters; h->krylov_iters_total += sc[r].iters; h->krylov_converged = (sc[r].outcome & 0xff) == CG_SOLVED ? 1 : 0;
+        if (!h->krylov_converged) ++h->krylov_unsolved;
+        h->krylov_resid0 = sc[r].resid0; h->krylov_resid = sc[r].resid;
+        if (nr == 2) {
+            h->krylov_pair_iters[r] = sc[r].iters; h->krylov_pair_outcome[r] = sc[r].outcome & 0xff;
+            h->krylov_pair_resid[2 * r] = sc[r].resid0; h->krylov_pair_resid[2 * r + 1] = sc[r].resid;
+        }
+    }
+    h->krylov_launches = launches;
+    if (nr == 2) { ++h->krylov_pairs; h->krylov_pair_rounds = enq; }
+    if (running) {
         solve_end(h);
         h->last_error = std::string(method) + ": every iteration was enqueued and the outcome word is still unset";
         return TLPK_INTERNAL;
@@ -1771,41 +1854,52 @@ static int krylov_run(tlpk_handle *h, const Sc *d_sc, i64 order, const char *met
 // ordered [n; m], which its all-ones fixture cannot tell apart -- the system of KKT.jl is the one solved here).  Launches: 2 (init) + 3 per enqueued iteration;
 // dx = x[0:n], dy = x[n:n+m] are two device copies behind the last chunk.
 // K1 (conjugate gradients): b into xw, the iteration from x = 0, then dy = x and dx.  Launches: 2 (b) + 2 (init) + 3 or 4 per enqueued iteration + 1 (dx).
-static int krylov_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
-    if (!d_dx || !d_dy) return TLPK_BADARG;
-    if (int g = refuse(h, d_xip && d_xid, R_MULTI | R_DEVICE | R_FACTORED)) return g;
+// nr = 2 (the second set is allocated): the same launches carry both right-hand sides, number 1 on the second set and the second half of xw.
+static int krylov_solve(tlpk_handle *h, int nr, double *const *dx, double *const *dy, const double *const *xp, const double *const *xd) {
+    for (int r = 0; r < nr; ++r) if (!dx[r] || !dy[r]) return TLPK_BADARG;
+    if (int g = refuse(h, xp[0] && xd[0] && xp[nr - 1] && xd[nr - 1], R_MULTI | R_DEVICE | R_FACTORED)) return g;
     if (int rc = solve_begin(h)) return rc;
     const i64 m = h->S.m, n = h->S.n, itmax = h->krylov_itmax;
     const double atol = h->krylov_atol, rtol = h->krylov_rtol;
-    const double *xp[2] = {d_xip, d_xip}, *xd[2] = {d_xid, d_xid};      // (conjugate gradients: launch_rhs and launch_dx take a pair)
-    double *dy[2] = {d_dy, d_dy}, *dx[2] = {d_dx, d_dx};
-    const double *x = nullptr;          // K2: the iterate [dx; dy]
+    const bool pair = nr == 2;
+    const double *x[2] = {nullptr, nullptr};          // K2: the iterates [dx; dy]
     int rc;
     if (h->krylov == TLPK_KRYLOV_MINRES) {
-        x = h->mr.x;
-        rc = krylov_run(h, h->mr.sc, n + m, "MINRES", 2, [&] { launch_mr_init(h->stream, h->d, h->mr, d_xip, d_xid, atol, rtol, itmax); },
-                        [&](i64 k) { return launch_mr_iter(h->stream, h->d, h->mr, h->d_D, h->d_regD, k); });
+        const MrArrays *c2 = pair ? &h->mr2 : nullptr;
+        x[0] = h->mr.x; x[1] = h->mr2.x;
+        rc = krylov_run(h, pair ? h->mr2.sc : h->mr.sc, nr, n + m, "MINRES", 2, [&] { launch_mr_init(h->stream, h->d, h->mr, xp, xd, atol, rtol, itmax, c2); },
+                        [&](i64 k) { return launch_mr_iter(h->stream, h->d, h->mr, h->d_D, h->d_regD, k, c2); });
     } else if (h->krylov == TLPK_KRYLOV_TRICG) {
-        x = h->tc.x;
-        rc = krylov_run(h, h->tc.sc, n + m, "TriCG", 2, [&] { launch_tc_init(h->stream, h->d, h->tc, d_xip, d_xid, atol, rtol, itmax); },
-                        [&](i64 k) { return launch_tc_iter(h->stream, h->d, h->tc, k); });
+        const TcArrays *c2 = pair ? &h->tc2 : nullptr;
+        x[0] = h->tc.x; x[1] = h->tc2.x;
+        rc = krylov_run(h, pair ? h->tc2.sc : h->tc.sc, nr, n + m, "TriCG", 2, [&] { launch_tc_init(h->stream, h->d, h->tc, xp, xd, atol, rtol, itmax, c2); },
+                        [&](i64 k) { return launch_tc_iter(h->stream, h->d, h->tc, k, c2); });
     } else {
-        rc = krylov_run(h, h->cg.sc, m, "conjugate gradients", 4 + 1,
-                        [&] { launch_rhs(h->stream, h->d, h->d_D, xp, xd, 0, 1); launch_cg_init(h->stream, h->d, h->cg, atol, rtol, itmax); },
-                        [&](i64 k) { return launch_cg_iter(h->stream, h->d, h->cg, h->d_D, h->d_regD, k); });
+        const CgArrays *c2 = pair ? &h->cg2 : nullptr;
+        rc = krylov_run(h, pair ? h->cg2.sc : h->cg.sc, nr, m, "conjugate gradients", 4 + 1,
+                        [&] { launch_rhs(h->stream, h->d, h->d_D, xp, xd, 0, nr); launch_cg_init(h->stream, h->d, h->cg, atol, rtol, itmax, c2); },
+                        [&](i64 k) { return launch_cg_iter(h->stream, h->d, h->cg, h->d_D, h->d_regD, k, c2); });
     }
     if (rc != TLPK_OK) return rc;
     {
         ProfScope ps(h, TLPK_KC_SPMV);
-        if (x) {
-            if (n > 0) HIPCHK(h, hipMemcpyAsync(d_dx, x, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
-            if (m > 0) HIPCHK(h, hipMemcpyAsync(d_dy, x + n, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
+        if (x[0]) {
+            for (int r = 0; r < nr; ++r) {
+                if (n > 0) HIPCHK(h, hipMemcpyAsync(dx[r], x[r], (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
+                if (m > 0) HIPCHK(h, hipMemcpyAsync(dy[r], x[r] + n, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
+            }
         } else {
-            if (m > 0) HIPCHK(h, hipMemcpyAsync(d_dy, h->cg.x, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
-            launch_dx(h->stream, h->d, h->d_D, dy, xd, dx, 0, 1);
+            if (m > 0) HIPCHK(h, hipMemcpyAsync(dy[0], h->cg.x, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
+            if (m > 0 && pair) HIPCHK(h, hipMemcpyAsync(dy[1], h->cg2.x, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
+            launch_dx(h->stream, h->d, h->d_D, dy, xd, dx, 0, nr);
         }
     }
     return solve_end(h);
+}
+static int krylov_solve(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid) {
+    const double *xp[2] = {d_xip, d_xip}, *xd[2] = {d_xid, d_xid};      // (conjugate gradients: launch_rhs and launch_dx take a pair)
+    double *dy[2] = {d_dy, d_dy}, *dx[2] = {d_dx, d_dx};
+    return krylov_solve(h, 1, dx, dy, xp, xd);
 }
 
 int tlpk_solve_local(tlpk_handle *h, const double *d_xip, const double *d_xid) {
@@ -1900,12 +1994,22 @@ int tlpk_refine_finish(tlpk_handle *h, double *d_dx, double *d_dy) {
 }
 
 // Two right-hand sides against the same factor in ONE pass over L (SolveIo).  Single-rank handles; with refine_steps > 0 the pair falls back to two refined solves.
+// A matrix-free handle runs both iterations through one sequence of launches (krylov_solve, nr = 2); TLPK_KRYLOV_PAIR=0 at create, or a second set of
+// vectors that does not fit, leaves it on two ordinary solves.
 int tlpk_solve2_device(tlpk_handle *h, double *d_dx0, double *d_dy0, const double *d_xip0, const double *d_xid0,
                        double *d_dx1, double *d_dy1, const double *d_xip1, const double *d_xid1) {
     if (int g = refuse(h, d_dx0 && d_dy0 && d_xip0 && d_xid0 && d_dx1 && d_dy1 && d_xip1 && d_xid1, R_MULTI)) return g;
     if (int g = sharded_needs_split(h, "tlpk_solve2_device")) return g;
     if (int g = refuse(h, true, R_DEVICE | R_FACTORED)) return g;
-    if (h->refine_steps > 0 || !h->S.sweep || h->krylov) {            // refinement / launch-per-block schedule / matrix-free handle: two ordinary solves
+    if (h->krylov && h->krylov_pair_on) {                             // matrix-free handle: both through one sequence of launches, once the second set is there
+        if (krylov_pair_alloc(h)) {
+            const double *xp[2] = {d_xip0, d_xip1}, *xd[2] = {d_xid0, d_xid1};
+            double *dx[2] = {d_dx0, d_dx1}, *dy[2] = {d_dy0, d_dy1};
+            return krylov_solve(h, 2, dx, dy, xp, xd);
+        }
+        ++h->krylov_pair_fallbacks;
+    }
+    if (h->refine_steps > 0 || !h->S.sweep || h->krylov) {            // refinement / launch-per-block schedule / matrix-free handle without a second set: two ordinary solves
         const int rc = tlpk_solve_device(h, d_dx0, d_dy0, d_xip0, d_xid0);
         return rc != TLPK_OK ? rc : tlpk_solve_device(h, d_dx1, d_dy1, d_xip1, d_xid1);
     }
@@ -2862,6 +2966,10 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
     else if (w == "chain_items") { for (auto &t : S.chain_items) { for (i32 v : {t.role, t.task, t.sub, t.w0, t.n0, t.need0, t.w1, t.n1, t.need1, t.w2, t.need2, t.sig}) tmp.push_back(v); } }
     else if (w == "chain_counters") tmp.assign(1, S.chain_counters);
     else if (w == "krylov_unsolved") tmp.assign(1, h->krylov_unsolved);         // matrix-free handles: solves since create that did NOT meet the stopping rule
+    // tlpk_solve2_device on a matrix-free handle: paired solves and fallbacks to two solves since create; of the last pair the iterations of number 0 and 1,
+    // their outcome codes (1 solved, 2 itmax, 3 breakdown) and the rounds of launches enqueued
+    else if (w == "krylov_pair") tmp = {h->krylov_pairs, h->krylov_pair_fallbacks, h->krylov_pair_iters[0], h->krylov_pair_iters[1], h->krylov_pair_outcome[0],
+                                        h->krylov_pair_outcome[1], h->krylov_pair_rounds};
     else if (w == "chain_retries") tmp.assign(1, h->chain_retries);           // updates of this handle that were replayed after a dependency-driven launch gave up waiting (tlpk_update)
     else if (w == "chain_trace") {                               // diagnostics: the time stamps of the last update (the caller has synchronised)
         if (!h->d.chain_trace) return -1;
@@ -2909,6 +3017,11 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
 int64_t tlpk_symbolic_get_f64(const tlpk_handle *h, const char *what, double *buf, int64_t cap) {
     if (!h || !what) return -1;
     const std::string w(what);
+    if (w == "krylov_pair_resid") {              // of the last pair on a matrix-free handle: resid0, resid of number 0, then of number 1
+        const i64 len = 4;
+        if (buf) std::copy(h->krylov_pair_resid, h->krylov_pair_resid + std::min(len, cap), buf);
+        return len;
+    }
     if (w != "pair_w") return -1;
     const auto &v = h->S.pair_w;
     i64 len = (i64)v.size();

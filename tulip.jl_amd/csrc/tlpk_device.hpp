@@ -183,10 +183,13 @@ struct CgArrays {
     KrylovGeom geo;                               // k_cg_rows: g_rows (at least 1) + g_lrows workgroups; k_cg_cols and k_cg_jacobi size their own grids
 };
 void launch_cg_jacobi(hipStream_t st, const DevArrays &a, const CgArrays &c, const double *D, const double *regD);
-// r (= a.ctx.xw) holds b: x = 0, p = M^-1 r, gamma, tolerance, outcome (a zero right-hand side is solved at once)
-void launch_cg_init(hipStream_t st, const DevArrays &a, const CgArrays &c, double atol, double rtol, i64 itmax);
+// r (= a.ctx.xw) holds b: x = 0, p = M^-1 r, gamma, tolerance, outcome (a zero right-hand side is solved at once).
+// c2 (here and below, for the three methods): not null = a PAIR of right-hand sides in the same launches.  Number 0 works on c's vectors and slots, number 1
+// on c2's (conjugate gradients: its b / r in the second half of xw, at xw2), and c2->sc holds the TWO scalar blocks of the pair, contiguous; what c2 shares
+// with c (the diagonals, the geometry) is read from c.  Each right-hand side stops on its own (krylov_reduce.hpp).
+void launch_cg_init(hipStream_t st, const DevArrays &a, const CgArrays &c, double atol, double rtol, i64 itmax, const CgArrays *c2 = nullptr);
 // iteration k (0-based) of the solve: four launches; returns their number
-int launch_cg_iter(hipStream_t st, const DevArrays &a, const CgArrays &c, const double *D, const double *regD, i64 k);
+int launch_cg_iter(hipStream_t st, const DevArrays &a, const CgArrays &c, const double *D, const double *regD, i64 k, const CgArrays *c2 = nullptr);
 
 // ---- matrix-free K2: MINRES on [-E A'; A Rd] [dx; dy] = [xi_d; xi_p] (krylov_k2_kernels.hip; DESIGN.md section 1b''''') ----
 // The recurrence's state, kept twice: iteration k reads st[k & 1] and ONE thread of its last kernel writes st[(k + 1) & 1]
@@ -214,10 +217,12 @@ struct MrArrays {
 };
 void launch_mr_diag(hipStream_t st, i64 n, const double *theta, const double *regP, double *E);
 void launch_mr_jacobi(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *E, const double *regD);
-// b = [xi_d; xi_p]: x = w = 0, z = M^-1 b, beta1, tolerance, outcome (a zero right-hand side is solved at once); two launches
-void launch_mr_init(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *xi_p, const double *xi_d, double atol, double rtol, i64 itmax);
+// b = [xi_d; xi_p]: x = w = 0, z = M^-1 b, beta1, tolerance, outcome (a zero right-hand side is solved at once); two launches.  xi_p, xi_d: one
+// pointer, or the two of a pair (c2 not null)
+void launch_mr_init(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *const *xi_p, const double *const *xi_d, double atol, double rtol, i64 itmax,
+                    const MrArrays *c2 = nullptr);
 // iteration k (0-based) of the solve: three launches; returns their number
-int launch_mr_iter(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *E, const double *regD, i64 k);
+int launch_mr_iter(hipStream_t st, const DevArrays &a, const MrArrays &c, const double *E, const double *regD, i64 k, const MrArrays *c2 = nullptr);
 
 // ---- matrix-free K2, quasi-definite form: TriCG on [Rd A; A' -E] [dy; dx] = [xi_p; xi_d] (krylov_sqd_kernels.hip; DESIGN.md section 1b'''''') ----
 // The recurrence's state, kept twice like MrState: beta_k, gamma_k (the norms that scaled v_k, u_k), the inverse of the previous 2 x 2 pivot block
@@ -247,9 +252,11 @@ struct TcArrays {
 // W, 1 / W and the quasi-definiteness check (one launch; *c.bad must hold LLONG_MAX before it)
 void launch_tc_diag(hipStream_t st, const DevArrays &a, const TcArrays &c, const double *theta, const double *regP, const double *regD);
 // b = [xi_d; xi_p]: beta1, gamma1, v_1, u_1, x = G = 0, tolerance, outcome (a zero right-hand side is solved at once); two launches
-void launch_tc_init(hipStream_t st, const DevArrays &a, const TcArrays &c, const double *xi_p, const double *xi_d, double atol, double rtol, i64 itmax);
+// xi_p, xi_d: one pointer, or the two of a pair (c2 not null)
+void launch_tc_init(hipStream_t st, const DevArrays &a, const TcArrays &c, const double *const *xi_p, const double *const *xi_d, double atol, double rtol, i64 itmax,
+                    const TcArrays *c2 = nullptr);
 // iteration k (0-based) of the solve: three launches; returns their number
-int launch_tc_iter(hipStream_t st, const DevArrays &a, const TcArrays &c, i64 k);
+int launch_tc_iter(hipStream_t st, const DevArrays &a, const TcArrays &c, i64 k, const TcArrays *c2 = nullptr);
 
 // new values on an analysed pattern (refresh_kernels.hip): w[t] = value(a[t]) * value(b[t]); out[q] = value(src[q]); the strided copy of a dense A
 void launch_refresh_pairs(hipStream_t st, i64 np, const i32 *a, const i32 *b, const double *nz, double *w);

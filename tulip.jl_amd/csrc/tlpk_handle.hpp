@@ -111,6 +111,19 @@ struct tlpk_handle {
     i64 krylov_chunk0 = 4, krylov_chunk_max = 32;   // iterations enqueued before the first look at the outcome / at most between two looks (TLPK_CG_CHUNK=first,max)
     i64 krylov_iters = 0, krylov_iters_total = 0, krylov_converged = 0, krylov_launches = 0, krylov_unsolved = 0;
     double krylov_resid0 = 0, krylov_resid = 0;
+    // tlpk_solve2_device on such a handle: both right-hand sides through one sequence of launches (tlpk_api.cpp: krylov_solve2).  The second set of vectors and
+    // slots (cg2 / mr2 / tc2; its sc holds the TWO scalar blocks of a pair) and the pinned copy of both blocks are allocated by the first pair.  pair_state:
+    // 0 = not tried, 1 = ready, -1 = the allocation failed or would cross the budget (every pair then runs as two solves and is counted in pair_fallbacks)
+    bool krylov_pair_on = true;         // TLPK_KRYLOV_PAIR=0 at create: two ordinary solves, as before
+    int krylov_pair_state = 0;
+    double krylov_budget = 0;           // mem_budget_bytes (0 = none given)
+    CgArrays cg2;
+    MrArrays mr2;
+    TcArrays tc2;
+    void *krylov_pin2 = nullptr;
+    i64 krylov_pairs = 0, krylov_pair_fallbacks = 0, krylov_pair_rounds = 0;      // paired solves / fallbacks since create; rounds enqueued by the last pair
+    i64 krylov_pair_iters[2] = {0, 0}, krylov_pair_outcome[2] = {0, 0};          // of the last pair, per right-hand side (outcome: CG_SOLVED, CG_ITMAX, CG_BREAKDOWN)
+    double krylov_pair_resid[4] = {0, 0, 0, 0};                                  // resid0, resid of number 0; resid0, resid of number 1
     // block skip (tlpk_block_skip / tlpk_ipm_batch_skip; tlpk_api.cpp: skip_*): units are the blocks of row_block, or the LPs of a batch-loaded handle
     std::vector<i32> front_unit;        // unit of every front, then of every single (the order of S.single_col); empty = not built yet
     i64 skip_units = 0;                 // number of units the table was built for

@@ -125,7 +125,18 @@ class KrylovBackend(_BackendOptions):
 
     method="tricg": `Krylov.TricgSolver` (src/KKT/Krylov/sqd.jl) -- TriCG on the symmetric quasi-definite form `[Rd A; A' -E]`, K2 only.
     precond must be None (`E` and `Rd` are the method's inner products); itmax = 0 means 2 (m + n).  An update with an `E_j <= 0` or an
-    `Rd_i <= 0` raises PosDefException (`stats()["fail_col"]`: `j`, or `n + i`) and leaves the handle usable."""
+    `Rd_i <= 0` raises PosDefException (`stats()["fail_col"]`: `j`, or `n + i`) and leaves the handle usable.
+
+    What a handle of this backend reports: `stats()` -- `krylov_iters`, `krylov_iters_total`, `krylov_converged`, `krylov_resid0`, `krylov_resid`,
+    `launches_solve` of the last solve; `symbolic("krylov_unsolved")` -- solves since create that did not meet the stopping rule.
+    `solve2_device` runs its two right-hand sides through ONE sequence of launches, each bit for bit as `solve_device` would solve it alone and each
+    stopping on its own; afterwards `stats()` reads as after the two solves one behind the other (the last-solve fields describe the second
+    right-hand side, `launches_solve` is that of the pair) and
+      `symbolic("krylov_pair")`        -> [paired solves since create, pairs that fell back to two solves since create, iterations of right-hand side 0
+                                          and of 1 in the last pair, their outcome codes (1 solved, 2 itmax, 3 breakdown), rounds of launches enqueued]
+      `symbolic_f64("krylov_pair_resid")` -> [resid0, resid of right-hand side 0, resid0, resid of 1] of the last pair.
+    The vectors of the second right-hand side are allocated by the first pair (`stats()["device_bytes"]` grows then); if they would cross
+    `mem_budget_bytes`, or with `TLPK_KRYLOV_PAIR=0` in the environment at setup, a pair is two solves."""
 
     def __init__(self, device=0, precond=None, itmax=0, atol=0.0, rtol=0.0, profile=False, mem_budget_bytes=0, method="cg"):
         if precond not in (None, "none", "jacobi"):
@@ -327,6 +338,10 @@ class HIPNormalEquations:
     def symbolic(self, what):
         return _lib.symbolic_array(self._h, what)
 
+    def symbolic_f64(self, what):
+        """tlpk_symbolic_get_f64: "pair_w", "krylov_pair_resid" (KrylovBackend)"""
+        return _lib.symbolic_array_f64(self._h, what)
+
     def factor_panels(self):
         st = self.stats()
         buf = np.empty(max(st["nnzL_stored"], 1))
@@ -347,7 +362,9 @@ class HIPNormalEquations:
             _raise_for(_lib.lib().tlpk_sync(self._h), self._h)
 
     def solve2_device(self, d_dx0, d_dy0, d_xip0, d_xid0, d_dx1, d_dy1, d_xip1, d_xid1, sync=True):
-        """Two right-hand sides in one pass over the factor (tlpk_solve2_device); bit-identical to two solve_device calls."""
+        """Two right-hand sides in one pass over the factor (tlpk_solve2_device); bit-identical to two solve_device calls.  A KrylovBackend handle runs
+        both iterations through one sequence of launches (see there).  The four outputs are distinct from each other and from every input; the inputs may
+        alias each other."""
         _raise_for(_lib.lib().tlpk_solve2_device(self._h, d_dx0, d_dy0, d_xip0, d_xid0, d_dx1, d_dy1, d_xip1, d_xid1), self._h)
         if sync:
             _raise_for(_lib.lib().tlpk_sync(self._h), self._h)
