@@ -160,6 +160,46 @@ def bump_lp(seed=99, m=60, n=160, pairs=20, big=3.0e5):
     return LP(A, c, 0.0, b, b, lvar, uvar, True, "BUMP")
 
 
+def planted_tree(nodes, seed):
+    """A constraint matrix whose K1 analysis (natural ordering, relax=False) has EXACTLY the elimination tree asked for: `nodes` is a
+    postorder list of (ns, parent) -- parent = index of a later node, or -1 for a root (several roots: a forest).  Node q owns ns_q
+    consecutive rows.  A = [one pair of dense columns per node | I]; the pair of node q covers
+
+        its own rows, its parent's rows EXCEPT the parent's first, and whatever the parent's pair covers above the parent's rows.
+
+    In A D A' + Rd a pair is a clique on the rows it covers, so the columns of node q all have the structure {own rows from the diagonal
+    down} + cover(q) above: one supernode.  Its last column's structure without the diagonal is one row longer than the parent's first
+    column could match (the skipped row), so the fundamental-supernode rule never merges a child into its parent, and two children of one
+    parent keep the parent's first column from merging with either.  Hence front q has ns = ns_q pivot columns and
+    f = ns_q + (ns_parent - 1) + (f_parent - ns_parent) = ns_q + f_parent - 1 rows (a root: f = ns), and nchild = its children in `nodes`.
+    (A parent of ONE row leaves none of its rows for a child to cover: the child would hang under the grandparent.  Refused.)
+
+    Returns (A csc of N x (2 len(nodes) + N), [(ns, f, nchild) per node, in the order of `nodes`]); the values are N(0, 1), the unit
+    columns are the slacks."""
+    rng = np.random.default_rng(seed)
+    ns = np.array([q[0] for q in nodes], dtype=np.int64)
+    parent = [int(q[1]) for q in nodes]
+    assert all(p == -1 or q < p < len(nodes) for q, p in enumerate(parent)) and (ns >= 1).all(), "postorder: a parent comes after its children"
+    first = np.concatenate([[0], np.cumsum(ns)])
+    N = int(first[-1])
+    cover_above = [None] * len(nodes)                      # rows of the ancestors that the node's pair covers
+    for q in range(len(nodes) - 1, -1, -1):
+        p = parent[q]
+        cover_above[q] = np.zeros(0, dtype=np.int64) if p < 0 else np.concatenate([np.arange(first[p] + 1, first[p + 1]), cover_above[p]])
+        assert p < 0 or ns[p] > 1, "a child covers none of a one-row parent's rows: it would hang under the grandparent, or be a root"
+    ri, ci = [], []
+    for q in range(len(nodes)):
+        rows = np.concatenate([np.arange(first[q], first[q + 1]), cover_above[q]])
+        for c in (2 * q, 2 * q + 1):
+            ri.append(rows); ci.append(np.full(len(rows), c))
+    ri, ci = np.concatenate(ri), np.concatenate(ci)
+    dense = sp.csc_matrix((rng.standard_normal(len(ri)), (ri, ci)), shape=(N, 2 * len(nodes)))
+    A = sp.hstack([dense, sp.identity(N, format="csc")], format="csc"); A.sort_indices()
+    nchild = np.bincount([p for p in parent if p >= 0], minlength=len(nodes))
+    shapes = [(int(ns[q]), int(ns[q] + len(cover_above[q])), int(nchild[q])) for q in range(len(nodes))]
+    return A, shapes
+
+
 def write_free_mps(lp, path):
     """Free-format MPS (row names R<i>, column names C<j>, objective row COST).  Values are written
     with repr() so that reading the file back reproduces the LP bit for bit."""

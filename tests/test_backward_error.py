@@ -93,8 +93,9 @@ def data_of(m, n, regime):
     return ipm_like_data(m, n, SEED, regime)
 
 
-def make_handle(name, device):
-    kind, backend, make = INPUTS[name]
+def make_handle(name, device, inputs=None):
+    """`inputs`: a table like INPUTS (tests/test_front_shapes.py brings its own)"""
+    kind, backend, make = (INPUTS if inputs is None else inputs)[name]
     A, kw = make()
     if backend == "dense":
         return A, tk.setup(A, tk.K1(), tk.DenseBackend(device=device))
@@ -104,9 +105,10 @@ def make_handle(name, device):
 class Problem:
     """One input and regime: the analysed handle, K^ and the data in long double, the restatement with its statistics."""
 
-    def __init__(self, name, regime):
-        self.name, self.regime, self.kind = name, regime, INPUTS[name][0]
-        self.A, self.kkt = make_handle(name, -1)
+    def __init__(self, name, regime, inputs=None):
+        self.inputs = INPUTS if inputs is None else inputs
+        self.name, self.regime, self.kind = name, regime, self.inputs[name][0]
+        self.A, self.kkt = make_handle(name, -1, self.inputs)
         m, n = self.A.shape
         self.data = data_of(m, n, regime)
         self.perm = self.kkt.symbolic("perm")
@@ -154,7 +156,7 @@ def pb(request):
 
 
 def emulator_of(pb):
-    kind, backend, _ = INPUTS[pb.name]
+    kind, backend, _ = pb.inputs[pb.name]
     if backend == "dense":
         from test_dense_backend import DenseEmulator
         return DenseEmulator(pb.kkt)
@@ -174,6 +176,10 @@ def test_restatement_is_inside_the_bound(pb):
 
 def test_emulated_schedule_is_inside_the_bound(pb):
     """(b): the factor of the exported schedule, executed by tests/emulate.py with substitution."""
+    emulator_leg(pb)
+
+
+def emulator_leg(pb):
     pb.assert_good_input()
     em = emulator_of(pb)
     em.update(*pb.data[:3])
@@ -200,6 +206,10 @@ def small_entry(pb, allow):
 def test_mutation_one_small_entry_passes_the_normwise_criteria_and_fails_the_bound(pb):
     """(c): L_ij (1 + 1e-9) for one small entry is invisible to max|L - L_ref| <= 1e-11 max|L|, w_i (1 + 1e-10) to max|w - w_ref| <= 1e-9
     max(1, max|w|) -- the criteria of compare_with_oracle / check_factor_and_solution -- and both break omega_hard <= 1."""
+    mutation_leg(pb)
+
+
+def mutation_leg(pb):
     name, regime = pb.name, pb.regime
     pb.assert_good_input()
     if pb.system.N == 1:                                    # dense_1x5: a 1 x 1 factor has no below-diagonal entry and its solve is one division
@@ -252,13 +262,16 @@ def test_k2_late_data_with_zero_diagonal_entries_is_not_an_input():
 # ---------------------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------------------
-def device_leg(pb, who="device"):
+def device_leg(pb, who="device", first=None):
+    """`first`: (theta, regP, regD) the handle factorises before the data of `pb` -- what the checked factor's storage then held before"""
     name, regime = pb.name, pb.regime
     pb.assert_good_input()
-    A, kkt = make_handle(name, 0)
+    A, kkt = make_handle(name, 0, pb.inputs)
     for what in ("perm", "front_col0", "front_ns"):
         assert np.array_equal(kkt.symbolic(what), pb.kkt.symbolic(what)), what
     th, rp, rd, xp, xd = pb.data
+    if first is not None:
+        tk.update(kkt, *first)
     tk.update(kkt, th, rp, rd)
     dx = np.zeros(A.shape[1]); dy = np.zeros(A.shape[0])
     tk.solve(dx, dy, kkt, xp, xd)
