@@ -270,6 +270,7 @@ __global__ __launch_bounds__(256) void k_extend_add(const EaTask *__restrict__ t
 // and the rel / U loads of EG_EB contributors (of at most EG_CH x 64 rows each) are in flight together.  LDS operations of one wave execute in
 // order and nothing crosses waves: no barrier, no flag, no atomic.  A slice is at most 8 KB: LDS leaves room for five workgroups per CU, the
 // launch bounds ask for four (with whole columns of up to 4 569 rows in LDS, one workgroup per CU, the kernel was latency-bound: DESIGN.md section 5c).
+// The panel columns of a FORMED front (TLPK_EA_FORM) are not read back: their segments start from zeros and the assembled entries (k_ea_gather<true>).
 // ------------------------------------------------------------------------------------------
 constexpr int EG_LD = EG_CAP_MAX / 64, EG_EB = 8, EG_CH = 2;
 struct EgBatch { const i32 *rl[EG_EB]; const double *sr[EG_EB]; i32 n[EG_EB]; };
@@ -284,18 +285,61 @@ __device__ __forceinline__ EgBatch eg_entries(const DevCtx &c, const i64 e, cons
     }
     return b;
 }
+// ... for the formed instance: lane u loads entry e + u and the wave reads the eight entries lane by lane (v_readlane), so that a batch costs six VGPRs
+// and its pointers are scalar whatever the compiler decides about the loads -- with the stores of the formed path in front of them it took the eight
+// uniform 24-byte loads of eg_entries as vector loads, 40 VGPRs in flight, and the kernel went to scratch (profiles/ea_form_resources.txt).  The list may be
+// EMPTY here (e == e1: a segment nothing lands in is still written): every n is 0 then and the pointers are those of a neighbouring entry, valid to read.
+__device__ __forceinline__ i64 eg_rl64(const i64 v, const int l) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l);
+    return (i64)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ EgBatch eg_entries_lanes(const DevCtx &c, const i64 e, const i64 e1, const int lane) {
+    const EaGatherEnt g = c.eg_ent[max(min(e + (lane & (EG_EB - 1)), e1 - 1), (i64)0)];
+    EgBatch b;
+#pragma unroll
+    for (int u = 0; u < EG_EB; ++u) {
+        const i64 src = eg_rl64(g.src, u), rel = eg_rl64(g.rel, u);
+        b.rl[u] = c.rel + rel;
+        b.sr[u] = (((src >> EG_UBUF_BIT) & 1) ? c.U1 : c.U0) + (src & (((i64)1 << EG_UBUF_BIT) - 1));
+        b.n[u] = (e + u < e1) ? __builtin_amdgcn_readlane(g.n, u) : 0;
+    }
+    return b;
+}
 __device__ __forceinline__ i32 eg_nmax(const EgBatch &b) {
     i32 m = 0;
 #pragma unroll
     for (int u = 0; u < EG_EB; ++u) m = max(m, b.n[u]);
     return m;
 }
-__global__ __launch_bounds__(256, 4) void k_ea_gather(const EaTask *__restrict__ tasks, DevCtx c, int slice_rows) {
+// Formed fronts: the wave's slice becomes zeros and the na entries k_assemble stored in the segment.  The first EG_AL x 64 of them
+// travelled in registers beside the first batch's loads (rows arow, values av); a longer list (rare) is walked 64 entries per trip.  The rows of a list are
+// distinct, and the LDS operations of a wave execute in order: the zero of a row comes before its entry.
+constexpr int EG_AL = 2;
+__device__ __forceinline__ void eg_put_formed(const unsigned short *__restrict__ asm_row, double *slice, const double *col, const double (&av)[EG_AL], const i32 (&arow)[EG_AL], const i64 a0, const i32 na,
+                                              const i32 n, const int lane) {
+#pragma unroll
+    for (int u = 0; u < EG_LD; ++u) if (lane + 64 * u < n) slice[lane + 64 * u] = 0.0;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int k = 0; k < EG_AL; ++k) if (lane + 64 * k < na) slice[arow[k]] = av[k];
+    for (i32 i = 64 * EG_AL + lane; i < na; i += 64) { const i32 r = asm_row[a0 + i]; slice[r] = col[r]; }
+}
+// the task is a panel-part task of a formed front (workgroup-uniform: a task lies in the panel part or in the U part)
+__device__ __forceinline__ bool ea_task_formed(const DevCtx &c, const EaTask &t, const i32 ns) { return (c.eg_front[t.front] & EG_FORMED) != 0 && t.j0 < ns; }
+// FORM: the instance of the panel columns of the FORMED fronts -- the panel has not been zero-filled, it holds the entries k_assemble stored and otherwise the
+// previous factor.  A segment starts from zeros and those entries (their rows come from the index: asm_ptr, asm_row = DevArrays::eg_asm_ptr, eg_asm_row; null for the other instance) and is written whether or
+// not anything lands in it; the column's stored rows outside [tc, f) -- above the diagonal in its 64-column slice, the padding rows [f, lda) -- are written
+// as zeros: every stored double of the panel gets what zero-fill + k_assemble + extend-add leave there, and nothing else of the panel is read.  Each
+// instance returns at once for the other's tasks (an instance of its own: with both seeds in one kernel the registers did not fit the launch bounds).
+template <bool FORM>
+__global__ __launch_bounds__(256, 4) void k_ea_gather(const EaTask *__restrict__ tasks, DevCtx c, int slice_rows, const i64 *__restrict__ asm_ptr,
+                                                      const unsigned short *__restrict__ asm_row) {
     extern __shared__ double eg_slices[];           // [4 waves][slice_rows], slice_rows = min(c.eg_cap, longest column of the launch)
     const EaTask t = tasks[blockIdx.x];
     if (!ea_task_gathered(c, t) || front_skipped(c, t.front)) return;
     const FrontDesc fd = c.fronts[t.front];
     const i32 f = fd.f, ns = fd.ns, rs = f - ns, cap = c.eg_cap;
+    if (ea_task_formed(c, t, ns) != FORM) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     double *slice = eg_slices + (size_t)wave * slice_rows;
@@ -304,18 +348,41 @@ __global__ __launch_bounds__(256, 4) void k_ea_gather(const EaTask *__restrict__
     for (i32 tc = t.j0 + wave; tc < t.j1; tc += 4) {
         double *__restrict__ col0 = (tc < ns) ? pcol(c, fd, tc) : (Up + (i64)(tc - ns) * rs - ns);      // virtual row 0 of the stored column
         const i64 g0 = colseg[tc], g1 = colseg[tc + 1];
+        if constexpr (FORM) {
+            for (i32 r = (tc & ~63) + lane; r < tc; r += 64) col0[r] = 0.0;
+            for (i32 r = f + lane; r < fd.lda; r += 64) col0[r] = 0.0;
+        }
         for (i64 g = g0; g < g1; ++g) {
             const i64 e0 = c.eg_ptr[g], e1 = c.eg_ptr[g + 1];
-            if (e0 == e1) continue;                 // nothing lands in this segment
+            if (!FORM && e0 == e1) continue;        // nothing lands in this segment
             const i32 r0 = tc + (i32)(g - g0) * cap, n = min(cap, f - r0);      // rows [r0, r0 + n) of the front
             if (n > slice_rows) continue;           // (never: the launch's slice is sized by the same rule)
             double *__restrict__ col = col0 + r0;
-            EgBatch b = eg_entries(c, e0, e1);
-            double cv[EG_LD];
+            // FORM: the segment's assembled entries, the first EG_AL x 64 of them in flight with the first batch's rel and U loads, as the stored rows are.  A
+            // segment without a contributor runs the loop below once, on an empty batch: it is seeded and written like every other
+            i32 na = 0; i64 a0 = 0;
+            i32 arow[EG_AL] = {}; double av[EG_AL] = {};
+            if constexpr (FORM) {
+                a0 = asm_ptr[g];
+                na = (i32)(asm_ptr[g + 1] - a0);
+                if (na > 0) {
 #pragma unroll
-            for (int u = 0; u < EG_LD; ++u) cv[u] = col[min(lane + 64 * u, n - 1)];
+                    for (int k = 0; k < EG_AL; ++k) arow[k] = asm_row[a0 + min(lane + 64 * k, na - 1)];
+                }
+            }
+            EgBatch b = FORM ? eg_entries_lanes(c, e0, e1, lane) : eg_entries(c, e0, e1);
+            double cv[FORM ? 1 : EG_LD];
+            if constexpr (FORM) {
+                if (na > 0) {
+#pragma unroll
+                    for (int k = 0; k < EG_AL; ++k) av[k] = col[arow[k]];
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < EG_LD; ++u) cv[u] = col[min(lane + 64 * u, n - 1)];
+            }
             bool seeded = false;
-            for (i64 e = e0; e < e1; e += EG_EB) {
+            for (i64 e = e0; e < e1 || (FORM && !seeded); e += EG_EB) {
                 // rel and U of the whole batch, clamped (a guarded load would wait for its guard): row r of contributor u goes to front row rl[u][r]
                 const bool thin = eg_nmax(b) <= 64 * EG_CH;
                 i32 tg[EG_EB][EG_CH]; double v[EG_EB][EG_CH];
@@ -328,13 +395,16 @@ __global__ __launch_bounds__(256, 4) void k_ea_gather(const EaTask *__restrict__
                             tg[u][k] = b.rl[u][ru] - r0; v[u][k] = b.sr[u][ru];
                         }
                 }
-                if (!seeded) {                      // the stored rows into the slice, behind the first batch's loads
+                if (!seeded) {                      // the stored rows (formed: zeros and the assembled entries) into the slice, behind the first batch's loads
+                    if constexpr (FORM) eg_put_formed(asm_row, slice, col, av, arow, a0, na, n, lane);
+                    else {
 #pragma unroll
-                    for (int u = 0; u < EG_LD; ++u) if (lane + 64 * u < n) slice[lane + 64 * u] = cv[u];
+                        for (int u = 0; u < EG_LD; ++u) if (lane + 64 * u < n) slice[lane + 64 * u] = cv[u];
+                    }
                     seeded = true;
                 }
                 EgBatch nb = b;
-                if (e + EG_EB < e1) nb = eg_entries(c, e + EG_EB, e1);      // the next batch's entries come while this one is added
+                if (e + EG_EB < e1) nb = FORM ? eg_entries_lanes(c, e + EG_EB, e1, lane) : eg_entries(c, e + EG_EB, e1);      // the next batch's entries come while this one is added
                 __builtin_amdgcn_wave_barrier();
                 if (thin) {
                     // contributor after contributor (list order); the rows of one contributor are distinct front rows: read all, then write all
@@ -4483,8 +4553,12 @@ void launch_tasks(hipStream_t st, const DevArrays &a, const Launch &L, const Swe
         if (a.eg_launch) {
             const EaGatherLaunch *e = std::lower_bound(a.eg_launch, a.eg_launch + a.n_eg_launch, L.first, [](const EaGatherLaunch &x, i64 first) { return x.first < first; });
             if (e != a.eg_launch + a.n_eg_launch && e->first == L.first) {
-                if (e->n_gather > 0)
-                    hipLaunchKernelGGL(k_ea_gather, g, dim3(256), (unsigned)(4 * 8 * e->rows), st, a.ea_tasks + L.first, a.ctx, (int)e->rows);
+                // (of the gathered tasks, n_form are panel-part tasks of formed fronts: the instance that starts from zeros and the assembled entries)
+                if (e->n_gather > e->n_form)
+                    hipLaunchKernelGGL(k_ea_gather<false>, g, dim3(256), (unsigned)(4 * 8 * e->rows), st, a.ea_tasks + L.first, a.ctx, (int)e->rows, (const i64 *)nullptr,
+                                       (const unsigned short *)nullptr);
+                if (e->n_form > 0)
+                    hipLaunchKernelGGL(k_ea_gather<true>, g, dim3(256), (unsigned)(4 * 8 * e->rows), st, a.ea_tasks + L.first, a.ctx, (int)e->rows, a.eg_asm_ptr, a.eg_asm_row);
                 plain = e->n_plain > 0;
             }
         }

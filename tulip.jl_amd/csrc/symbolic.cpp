@@ -1416,6 +1416,61 @@ int analyse_rank(Symbolic &S, const Options &opt) {
     // k_update walks its K range in slabs of 16 columns and relies on a slab lying inside ONE 64-column slice of the packed panel
     for (const UpdateTask &u : S.update_tasks)
         if ((u.k0 & 15) != 0) return fail(S, TLPK_INTERNAL, "update task: K range does not start on a multiple of 16 columns");
+    // ---- 14'. formed fronts (TLPK_EA_FORM = 0 | 1, unset = 1).  A gathered front whose panel columns all belong to k_ea_gather -- its
+    // extend-add tasks cover [0, ns) and none of them is a row band (TLPK_EA_BANDS) -- needs no zero-fill: the kernel starts a segment from zeros and the
+    // entries of S that k_assemble has stored in it, and writes every stored double of the column.  For that it needs the rows of those entries per segment:
+    // from the assembly targets and the packed layout, ascending.  After the schedule (the tasks decide), and nothing the schedule digest covers moves.
+    S.ea_form.clear(); S.ea_gather_asm_ptr.clear(); S.ea_gather_asm_row.clear();
+    {
+        bool on = true;
+        if (const char *e = std::getenv("TLPK_EA_FORM")) on = std::atoi(e) != 0;
+        const size_t nf = S.fronts.size();
+        std::vector<unsigned char> form(nf, 0);
+        bool any = false;
+        if (on && !S.ea_gather_ent.empty()) {
+            std::vector<i64> covered(nf, 0);
+            std::vector<char> banded(nf, 0);
+            for (const EaTask &t : S.ea_tasks) {
+                if (S.ea_gather_base[(size_t)t.front] < 0) continue;
+                if (t.br1 != 0) banded[(size_t)t.front] = 1;
+                else if (t.j1 <= S.fronts[(size_t)t.front].ns) covered[(size_t)t.front] += t.j1 - t.j0;
+            }
+            for (size_t s = 0; s < nf; ++s)
+                if (S.ea_gather_base[s] >= 0 && !S.front_fa[s] && !banded[s] && covered[s] == S.fronts[s].ns) { form[s] = 1; any = true; }
+        }
+        if (any) {
+            const i32 cap = S.ea_gather_cap;
+            const i64 nseg = (i64)S.ea_gather_ptr.size() - 1;
+            std::vector<i64> &ptr = S.ea_gather_asm_ptr;
+            ptr.assign((size_t)nseg + 1, 0);
+            // two passes over the entries of the formed fronts' pivot columns: count per segment, then place
+            for (int pass = 0; pass < 2; ++pass) {
+                std::vector<i64> fill;
+                if (pass == 1) {
+                    for (i64 g = 0; g < nseg; ++g) ptr[(size_t)g + 1] += ptr[(size_t)g];
+                    S.ea_gather_asm_row.assign((size_t)ptr[(size_t)nseg], 0);
+                    fill.assign(ptr.begin(), ptr.end() - 1);
+                }
+                for (size_t s = 0; s < nf; ++s) {
+                    if (!form[s]) continue;
+                    const FrontDesc &w = S.fronts[s];
+                    const i64 *colseg = S.ea_gather_col.data() + S.ea_gather_base[s];
+                    for (i32 tc = 0; tc < w.ns; ++tc) {
+                        const i64 kk = (i64)w.col0 + tc, vrow0 = w.loff + pk_off(w.lda, tc);
+                        for (i64 e = S.Sp[(size_t)kk]; e < S.Sp[(size_t)kk + 1]; ++e) {
+                            const i64 row = S.s_target[(size_t)e] - vrow0;
+                            if (!S.s_local[(size_t)e] || row < tc || row >= w.f) return fail(S, TLPK_INTERNAL, "formed front: an assembly target outside its panel column");
+                            const i64 pc = (row - tc) / cap, g = colseg[tc] + pc;
+                            if (pass == 0) ptr[(size_t)g + 1]++;
+                            else S.ea_gather_asm_row[(size_t)fill[(size_t)g]++] = (uint16_t)(row - tc - pc * cap);
+                        }
+                    }
+                }
+            }
+            for (i64 g = 0; g < nseg; ++g) std::sort(S.ea_gather_asm_row.begin() + ptr[(size_t)g], S.ea_gather_asm_row.begin() + ptr[(size_t)g + 1]);
+            S.ea_form = std::move(form);
+        }
+    }
     pt.mark(nullptr);
     return TLPK_OK;
 }

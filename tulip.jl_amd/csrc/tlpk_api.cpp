@@ -247,10 +247,13 @@ std::vector<EaGatherLaunch> eg_count_launches(const Symbolic &S) {
     if (S.ea_gather_ent.empty()) return out;
     for (const Launch &L : S.factor_launches) {
         if (L.kind != LK_EXTEND_ADD || L.count <= 0) continue;
-        EaGatherLaunch g{L.first, 0, 0, 1};
+        EaGatherLaunch g{L.first, 0, 0, 1, 0};
         for (i64 k = L.first; k < L.first + L.count; ++k) {
             const EaTask &t = S.ea_tasks[(size_t)k];
-            if (S.ea_gather_base[(size_t)t.front] >= 0 && t.br1 == 0) { g.n_gather++; g.rows = std::max(g.rows, std::min(S.fronts[(size_t)t.front].f - t.j0, S.ea_gather_cap)); }
+            if (S.ea_gather_base[(size_t)t.front] >= 0 && t.br1 == 0) {
+                g.n_gather++; g.rows = std::max(g.rows, std::min(S.fronts[(size_t)t.front].f - t.j0, S.ea_gather_cap));
+                if (!S.ea_form.empty() && S.ea_form[(size_t)t.front] && t.j0 < S.fronts[(size_t)t.front].ns) g.n_form++;      // (kernels.hip: ea_task_formed)
+            }
             else g.n_plain++;
         }
         if (g.n_gather > 0) out.push_back(g);
@@ -387,7 +390,7 @@ int upload_all(tlpk_handle *h) {
         // per-column extend-add index: the tables, the per-front byte that splits the task list between k_ea_gather and k_extend_add, and per launch how
         // many tasks each kernel has and the longest segment k_ea_gather holds (its LDS slice)
         std::vector<unsigned char> gf(S.fronts.size(), 0);
-        for (size_t s = 0; s < gf.size(); ++s) gf[s] = S.ea_gather_base[s] >= 0;
+        for (size_t s = 0; s < gf.size(); ++s) gf[s] = S.ea_gather_base[s] < 0 ? 0 : (unsigned char)(EG_GATHERED | (!S.ea_form.empty() && S.ea_form[s] ? EG_FORMED : 0));
         { unsigned char *p; UP(p, gf); d.ctx.eg_front = p; }
         { i64 *p; UP(p, S.ea_gather_base); d.ctx.eg_base = p; }
         { i64 *p; UP(p, S.ea_gather_col); d.ctx.eg_col = p; }
@@ -397,6 +400,11 @@ int upload_all(tlpk_handle *h) {
         h->eg_launches = eg_count_launches(S);
         if (!h->eg_launches.empty()) { d.eg_launch = h->eg_launches.data(); d.n_eg_launch = (i64)h->eg_launches.size(); }
         else d.ctx.eg_front = nullptr;              // (no launch has a task for it: k_extend_add does everything)
+        if (d.ctx.eg_front && !S.ea_form.empty()) {
+            // formed fronts (bit EG_FORMED of the per-front byte): the rows of the assembled entries per segment
+            { i64 *p; UP(p, S.ea_gather_asm_ptr); d.eg_asm_ptr = p; }
+            { uint16_t *p; UP(p, S.ea_gather_asm_row); d.eg_asm_row = p; }
+        }
     }
     UP(d.update_tasks, S.update_tasks); UP(d.reduce_tasks, S.reduce_tasks);
     UP(d.chain_items, S.chain_items); d.n_chain_cnt = S.chain_counters;
@@ -405,8 +413,22 @@ int upload_all(tlpk_handle *h) {
     { i32 *p; UP(p, S.upd_seg); d.ctx.upd_seg = p; }
     d.n_single = (i64)S.single_col.size();
     UP(d.single_loff, S.single_loff); UP(d.single_dinvoff, S.single_dinvoff); UP(d.single_col, S.single_col);
-    UP(d.zero_tasks, S.zero_tasks); d.n_zero_tasks = (i64)S.zero_tasks.size() / 2; d.n_zero_lower = d.has_upper ? S.n_zero_lower : d.n_zero_tasks;
-    UP(d.zero_small, S.zero_small); d.n_zero_small = (i64)S.zero_small.size();
+    if (d.eg_asm_ptr) {
+        // formed fronts are not zero-filled: the device gets the zero-fill lists without them (the lists of the analysis stay whole)
+        std::vector<i32> zt, zs;
+        i64 lower = 0;
+        for (size_t k = 0; k + 1 < S.zero_tasks.size(); k += 2) {
+            if (S.ea_form[(size_t)S.zero_tasks[k]]) continue;
+            zt.push_back(S.zero_tasks[k]); zt.push_back(S.zero_tasks[k + 1]);
+            if ((i64)k / 2 < S.n_zero_lower) ++lower;
+        }
+        for (const i32 s : S.zero_small) if (!S.ea_form[(size_t)s]) zs.push_back(s);
+        UP(d.zero_tasks, zt); d.n_zero_tasks = (i64)zt.size() / 2; d.n_zero_lower = d.has_upper ? lower : d.n_zero_tasks;
+        UP(d.zero_small, zs); d.n_zero_small = (i64)zs.size();
+    } else {
+        UP(d.zero_tasks, S.zero_tasks); d.n_zero_tasks = (i64)S.zero_tasks.size() / 2; d.n_zero_lower = d.has_upper ? S.n_zero_lower : d.n_zero_tasks;
+        UP(d.zero_small, S.zero_small); d.n_zero_small = (i64)S.zero_small.size();
+    }
     UP(d.fwd_gather_tasks, S.fwd_gather_tasks); UP(d.fwd_diag_tasks, S.fwd_diag_tasks);
     UP(d.fwd_update_tasks, S.fwd_update_tasks); UP(d.bwd_update_tasks, S.bwd_update_tasks);
     UP(d.fwd_small_tasks, S.fwd_small_tasks); UP(d.bwd_small_tasks, S.bwd_small_tasks);
@@ -2931,6 +2953,10 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
     else if (w == "ea_gather_ent") { for (auto &g : S.ea_gather_ent) { tmp.push_back(g.src); tmp.push_back(g.rel); tmp.push_back(g.n); tmp.push_back(g.child); } }
     else if (w == "ea_gather_cap") tmp.assign(1, S.ea_gather_cap);
     else if (w == "ea_gather_launches") { for (auto &g : eg_count_launches(S)) { tmp.push_back(g.first); tmp.push_back(g.n_gather); tmp.push_back(g.n_plain); tmp.push_back(g.rows); } }
+    // formed fronts (TLPK_EA_FORM): one byte per front (empty: none is formed); per segment the first of its assembled entries; their rows from the segment's first row
+    else if (w == "ea_form") tmp.assign(S.ea_form.begin(), S.ea_form.end());
+    else if (w == "ea_gather_asm_ptr") tmp = S.ea_gather_asm_ptr;
+    else if (w == "ea_gather_asm_row") tmp.assign(S.ea_gather_asm_row.begin(), S.ea_gather_asm_row.end());
     else if (w == "front_eatab") field([](const FrontDesc &f) { return f.eatab; });
     else if (w == "children") from32(S.children);
     else if (w == "depth") from32(S.depth);

@@ -30,9 +30,13 @@ struct DevCtx {
     // per-column extend-add index (k_ea_gather): eg_front == nullptr: none; else != 0 per front whose extend-add k_ea_gather does (k_extend_add leaves its
     // tasks alone); eg_col + eg_base[front] = per column of the front its first segment (eg_cap rows each), eg_ptr[segment] = its first entry of eg_ent
     const unsigned char *eg_front; const i64 *eg_base, *eg_col, *eg_ptr; const EaGatherEnt *eg_ent; i32 eg_cap;
-    const unsigned char *front_skip;   // block skip (tlpk_block_skip / tlpk_ipm_batch_skip): nullptr = no mask; else != 0 per front (then per single) that this update / solve leaves out
+    // Bit 1 of a front's byte (EG_FORMED): the front is FORMED (Symbolic::ea_form) -- its panel is not zero-filled, k_ea_gather<true> writes every stored double
+    // of its columns.  (In this byte and not in a field of its own: DevCtx is an argument of every front kernel, and three more pointers in it moved k_chain's
+    // scratch from 500 to 532 bytes per lane; the index of the formed fronts is an argument of the one kernel that reads it, DevArrays::eg_asm_*.)
+    const unsigned char *front_skip;  // block skip (tlpk_block_skip / tlpk_ipm_batch_skip): nullptr = no mask; else != 0 per front (then per single) that this update / solve leaves out
 };
-constexpr int INFO_WORDS = 16;   // status and diagnostic words of DevCtx.info, in front of its m mark words
+constexpr unsigned char EG_GATHERED = 1, EG_FORMED = 2;   // bits of DevCtx::eg_front[front]
+constexpr int INFO_WORDS = 16;  // status and diagnostic words of DevCtx.info, in front of its m mark words
 
 // per-launch arguments of the persistent sweep kernels
 struct SweepArgs {
@@ -46,12 +50,14 @@ struct SweepArgs {
 };
 
 // an LK_EXTEND_ADD launch as its two kernels see it, counted at create (tlpk_api.cpp: eg_count_launches): tasks of k_ea_gather / of k_extend_add,
-// rows of a wave's LDS slice = the longest segment k_ea_gather holds in the launch
-struct EaGatherLaunch { i64 first; i32 n_gather, n_plain, rows; };
+// rows of a wave's LDS slice = the longest segment k_ea_gather holds in the launch; n_form of the n_gather tasks are panel-part tasks of formed fronts
+struct EaGatherLaunch { i64 first; i32 n_gather, n_plain, rows, n_form; };
 
 struct DevArrays {
     DevCtx ctx{};
     const EaGatherLaunch *eg_launch = nullptr; i64 n_eg_launch = 0;   // host memory of the handle, ascending `first`; nullptr: no front is gathered
+    // formed fronts (Symbolic::ea_gather_asm_*): eg_asm_row[eg_asm_ptr[segment] ..] = the rows, from the segment's first row, of the entries k_assemble stores in it
+    const i64 *eg_asm_ptr = nullptr; const unsigned short *eg_asm_row = nullptr;
     i64 m = 0, n = 0;                         // m: order of the factored matrix (K2: n + m; dense columns: m + k), n: columns of the stored matrix
     i64 mu = 0;                               // rows of A as the caller sees them (= m for plain K1): the residual kernels of the refinement
     // K1 with dense columns (tlpk_options.dense_cols): sparse_col[j] = 1 for a column formed into A_s D_s A_s', 0 for a dense one;

@@ -195,6 +195,10 @@ struct Symbolic {
     // contributors ea_gather_ent[ptr[g] .. ptr[g + 1]) in child order
     std::vector<i64> ea_gather_base, ea_gather_col, ea_gather_ptr; std::vector<EaGatherEnt> ea_gather_ent;
     i32 ea_gather_cap = 0;
+    // formed fronts (step 14', TLPK_EA_FORM): ea_form[s] != 0: k_ea_gather writes every stored double of the panel of gathered front s, so
+    // the panel is not zero-filled (empty: no front is formed).  Per segment g of a panel column of a formed front, the entries of S that k_assemble stores in
+    // it: ea_gather_asm_row[asm_ptr[g] .. asm_ptr[g + 1]) = their rows, counted from the segment's first row, ascending (no entries for every other segment)
+    std::vector<unsigned char> ea_form; std::vector<i64> ea_gather_asm_ptr; std::vector<uint16_t> ea_gather_asm_row;
     std::vector<i64> gth_ptr, gth_src;     // forward gather lists: front row (rowoff + t) -> children's uc entries, in child order
     std::vector<i32> children;             // concatenated child lists
     std::vector<i32> depth;                // depth of each front (roots = 0)
