@@ -200,6 +200,69 @@ def planted_tree(nodes, seed):
     return A, shapes
 
 
+def planted_tree_k2(nodes, seed, transposed=False):
+    """A constraint matrix and a permutation of the K2 nodes (variable j = node j, constraint i = node n + i) whose K2 analysis
+    (ordering="user", relax=False) has EXACTLY the fronts asked for, each with the SIGN PATTERN asked for: `nodes` is a postorder list of
+    (pattern, parent), pattern a string over '+' (a constraint node, pivot sign +1) and '-' (a variable node, -1) -- the signs of the
+    front's pivot columns in elimination order.  Every pattern starts with '+', holds a '-', and a parent holds two '+' at least.
+
+    Node q owns the rows of its '+', the columns of its '-' and one HELPER column.  The helper and every own column have entries on
+    T_q = q's rows + cover(q), cover(q) = the parent's rows except the parent's first, then cover(parent) (the skipped-row rule of
+    planted_tree).  The order is, node by node: the helper, then q's nodes as the pattern lists them.  In the graph of K2 a column is
+    adjacent to its rows only.  The helper is eliminated first and makes T_q a clique: a leaf front of one column, f = 1 + |T_q|, sign -.
+    q's first row then sees the rest of T_q and all of q's columns, and after it all of these are one clique: one supernode, whatever the
+    order of the further pivots.  The helper does not merge into it (its column is |own columns| >= 1 entries short), q's last column is one
+    row longer than the parent's first could match (the skipped row), and the parent's columns see no child's column.  Hence front q has
+    ns = len(pattern), f = ns + |cover(q)| (the rows below are the ancestors' '+' rows) and nchild = its children in `nodes` + 1.
+
+    transposed: the same tree with rows and columns exchanged (the matrix is the transpose) -- every pattern starts with '-', the helper
+    is a ROW (a front of sign +) and the rows below a front are its ancestors' '-' columns.
+
+    Returns (A csc, perm of length m + n, [(ns, f, nchild)], [sign string]), the last two per front in elimination order: the helper
+    of node q is front 2q, node q is front 2q + 1.  The values are N(0, 1)."""
+    if transposed:
+        swap = str.maketrans("+-", "-+")
+        A, perm, shapes, signs = planted_tree_k2([(pat.translate(swap), p) for pat, p in nodes], seed)
+        m0, n0 = A.shape                                       # old variable j -> constraint j = node m0 + j; old constraint i -> variable i
+        perm = np.where(perm < n0, perm + m0, perm - n0)
+        return A.T.tocsc(), perm, shapes, [s.translate(swap) for s in signs]
+    rng = np.random.default_rng(seed)
+    parent = [int(q[1]) for q in nodes]
+    assert all(p == -1 or q < p < len(nodes) for q, p in enumerate(parent)), "postorder: a parent comes after its children"
+    for q, (pat, _) in enumerate(nodes):
+        assert pat[0] == "+" and "-" in pat and set(pat) <= {"+", "-"}, f"node {q}: a pattern starts with '+' and holds a '-'"
+    rows, cols, helper, order = [], [], [], []               # order: ('c', column) | ('r', row) in elimination order
+    m = n = 0
+    for pat, _ in nodes:
+        helper.append(n); order.append(("c", n)); n += 1
+        r, c = [], []
+        for ch in pat:
+            if ch == "+":
+                r.append(m); order.append(("r", m)); m += 1
+            else:
+                c.append(n); order.append(("c", n)); n += 1
+        rows.append(np.array(r, dtype=np.int64)); cols.append(np.array(c, dtype=np.int64))
+    cover = [None] * len(nodes)
+    for q in range(len(nodes) - 1, -1, -1):
+        p = parent[q]
+        cover[q] = np.zeros(0, dtype=np.int64) if p < 0 else np.concatenate([rows[p][1:], cover[p]])
+        assert p < 0 or len(rows[p]) > 1, "a child covers none of the rows of a parent with one '+': it would hang under the grandparent"
+    ri, ci = [], []
+    for q in range(len(nodes)):
+        T = np.concatenate([rows[q], cover[q]])
+        for c in [helper[q]] + cols[q].tolist():
+            ri.append(T); ci.append(np.full(len(T), c))
+    ri, ci = np.concatenate(ri), np.concatenate(ci)
+    A = sp.csc_matrix((rng.standard_normal(len(ri)), (ri, ci)), shape=(m, n)); A.sort_indices()
+    perm = np.array([i if kind == "c" else n + i for kind, i in order], dtype=np.int64)
+    nchild = np.bincount([p for p in parent if p >= 0], minlength=len(nodes))
+    shapes, signs = [], []
+    for q, (pat, _) in enumerate(nodes):
+        shapes += [(1, 1 + len(rows[q]) + len(cover[q]), 0), (len(pat), len(pat) + len(cover[q]), int(nchild[q]) + 1)]
+        signs += ["-", pat]
+    return A, perm, shapes, signs
+
+
 def write_free_mps(lp, path):
     """Free-format MPS (row names R<i>, column names C<j>, objective row COST).  Values are written
     with repr() so that reading the file back reproduces the LP bit for bit."""

@@ -363,9 +363,15 @@ def test_device_factor_and_solves_are_inside_the_bound(pb, monkeypatch):
 
 
 def with_rhs(system, xp, xd):
-    """The K1 system with another right-hand side (xi_p, xi_d): rhs = xi_p + A D xi_d and its allowances, as System forms them."""
-    assert system.kind == "k1"
+    """The K1 system with another right-hand side (xi_p, xi_d): rhs = xi_p + A D xi_d and its allowances, as System forms them.  K2: rhs =
+    [xi_d; xi_p], a permutation of the caller's -- no arithmetic, no allowance."""
     out = copy.copy(system)
+    if system.kind == "k2":
+        out.data = system.data[:3] + (xp, xd)
+        out.rhs = np.concatenate([xd, xp]).astype(LD)[system.perm]
+        out.rhs_hard = out.rhs_unit = np.zeros(system.N)
+        return out
+    assert system.kind == "k1"
     A, D = system.A, system.D
     absA = abs(A)
     q = np.asarray((absA != 0).sum(axis=1)).ravel().astype(np.float64)

@@ -102,6 +102,43 @@ def test_k2_wrong_sign_pivot_is_reported():
     assert em.fail_col is not None
 
 
+def user_perm_case():
+    """A 50 x 110 matrix and a random permutation of its 160 K2 nodes, variables and constraints interleaved"""
+    A = random_lp_matrix(50, 110, 3, 17)
+    return A, np.random.default_rng(5).permutation(160).astype(np.int64)
+
+
+def test_k2_user_perm():
+    """ordering="user" with system = K2: perm[new] = old over the m + n nodes, old < n a variable node, old = n + i constraint node i."""
+    A, perm = user_perm_case()
+    m, n = A.shape
+    kkt = k2_setup(A, ordering="user", user_perm=perm, relax=False)
+    p1 = kkt.perm()
+    assert sorted(p1.tolist()) == list(range(m + n))
+    # the final permutation is the user's order up to an etree postorder: same fill; a postorder comes back as it was given
+    assert kkt.stats()["nnzL"] == OracleK2(A, perm).nnzL == OracleK2(A, p1).nnzL
+    kkt = k2_setup(A, ordering="user", user_perm=p1, relax=False)
+    assert np.array_equal(kkt.perm(), p1)
+    assert np.array_equal(kkt.symbolic("perm") < n, p1 < n)            # the signs follow the permutation
+    th, rp, rd, xp, xd = ipm_like_data(m, n, 2)
+    em = Emulator(kkt)
+    em.update(th, rp, rd)
+    assert em.fail_col is None
+    dx, dy = em.solve(xp, xd, A)
+    orc = OracleK2(A, p1); orc.update(th, rp, rd)
+    dxo, dyo = orc.solve(xp, xd)
+    assert np.abs(dx - dxo).max() <= 1e-9 * max(1.0, np.abs(dxo).max())
+    assert np.abs(dy - dyo).max() <= 1e-9 * max(1.0, np.abs(dyo).max())
+    # refused: a duplicate and an entry out of range, each in the LAST place (all m + n entries are read), a negative entry, and row_block
+    for bad in (np.r_[perm[:-1], perm[0]], np.r_[perm[:-1], m + n], np.r_[-1, perm[1:]]):
+        with pytest.raises(Exception):
+            k2_setup(A, ordering="user", user_perm=bad)
+    with pytest.raises(Exception):
+        k2_setup(A, ordering="user", user_perm=perm, row_block=np.zeros(m, dtype=np.int64))
+    with pytest.raises(tk.DimensionMismatch):                # a K1-length array is not read m + n entries far
+        k2_setup(A, ordering="user", user_perm=np.arange(m, dtype=np.int64))
+
+
 # ---------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------
@@ -146,6 +183,14 @@ def test_k2_golden_vectors_on_device(g):
 def test_k2_random_sparse_vs_k2_oracle(seed):
     A = random_lp_matrix(300 + 170 * seed, 800 + 300 * seed, 3, 200 + seed, slack=(seed == 1))
     gpu_compare(A, seed, relax=(seed != 2))
+
+
+@pytest.mark.gpu
+def test_k2_user_perm_on_device():
+    """A caller's permutation of the m + n nodes (signs interleaved in every front) against the K2 oracle with the same permutation."""
+    A, perm = user_perm_case()
+    kkt, _, _ = gpu_compare(A, 2, ordering="user", user_perm=perm, relax=False)
+    assert kkt.stats()["nnzL"] == OracleK2(A, perm).nnzL
 
 
 @pytest.mark.gpu

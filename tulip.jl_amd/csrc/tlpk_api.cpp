@@ -826,9 +826,11 @@ static int create_host(tlpk_handle *h, const tlpk_options &def, int64_t m, int64
         if (drc == TLPK_OK && nb >= 2) h->opt.row_block = h->row_block_copy.data();
         else h->row_block_copy.clear();          // no structure (or malformed input: analyse reports it): general sparse path
     }
-    if (def.ordering == TLPK_ORDER_USER && def.user_perm && m > 0) {
-        h->user_perm_copy.resize((size_t)m);
-        for (i64 i = 0; i < m; ++i) h->user_perm_copy[(size_t)i] = def.user_perm[i] - index_base;
+    // a permutation of the factored system's nodes: the m rows for K1, the n variable nodes then the m constraint nodes for K2
+    const i64 nperm = (h->opt.system != 1) ? m : (m >= 0 && n >= 0) ? m + n : 0;
+    if (def.ordering == TLPK_ORDER_USER && def.user_perm && nperm > 0) {
+        h->user_perm_copy.resize((size_t)nperm);
+        for (i64 i = 0; i < nperm; ++i) h->user_perm_copy[(size_t)i] = def.user_perm[i] - index_base;
         h->opt.user_perm = h->user_perm_copy.data();
     }
     h->profile = def.profile != 0;
@@ -2524,6 +2526,11 @@ int tlpk_create_multi(tlpk_handle **out, int64_t m, int64_t n, const int64_t *co
         // the dense nodes would be replicated root nodes whose columns span shards, while the multi-shard device-resident loops give every
         // column to exactly one shard: not supported
         g_create_error = "dense_cols: not on tlpk_create_multi handles";
+        return TLPK_BADARG;
+    }
+    if (uopt && uopt->struct_size == (int32_t)sizeof(tlpk_options) && uopt->ordering == TLPK_ORDER_USER) {
+        // these handles are block-angular (row_block, given or detected), which user_perm cannot be combined with: the array is never read here
+        g_create_error = "user_perm: not on tlpk_create_multi handles (their rows are ordered block by block)";
         return TLPK_BADARG;
     }
     if (uopt && uopt->struct_size == (int32_t)sizeof(tlpk_options) && uopt->krylov != TLPK_KRYLOV_NONE) {

@@ -219,6 +219,9 @@ class HIPNormalEquations:
             opt.row_block = _lib.as_p64(backend_.row_block)
             self._keep.append(backend_.row_block)
         if backend_.user_perm is not None:
+            nperm = self.m + self.n if system == _lib.SYSTEM_K2 else self.m      # the nodes of the factored system
+            if backend_.ordering == _lib.ORDER_USER and backend_.user_perm.shape != (nperm,):
+                raise DimensionMismatch(f"length(user_perm)={backend_.user_perm.size} but the system has {nperm} nodes")
             opt.user_perm = _lib.as_p64(backend_.user_perm)
             self._keep.append(backend_.user_perm)
         if isinstance(backend_, KrylovBackend):
