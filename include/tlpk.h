@@ -345,6 +345,32 @@ int tlpk_solve2_finish(tlpk_handle *h, double *d_dx0, double *d_dy0, const doubl
  * refinement step of tlpk_solve_device. */
 int tlpk_refine_local(tlpk_handle *h, const double *d_dx, const double *d_dy, const double *d_xi_p, const double *d_xi_d);
 int tlpk_refine_finish(tlpk_handle *h, double *d_dx, double *d_dy);
+/* Refinement on demand: K1 AND K2, chosen per solve, one system or a pair.  tlpk_polish_device takes any (dx, dy) -- normally the output of a finished
+ * solve against the current factor -- and corrects it in place by up to `steps` guarded refinement steps on
+ *   r1 = xi_p - A dx - Rd dy        r2 = xi_d + (theta_inv + Rp) dx - A' dy
+ * with the theta_inv, Rp, Rd of the last update.  A step is one more solve with (r1, r2) as right-hand side; the candidate is kept only if |r1|inf shrinks
+ * and |r2|inf stays within 16 x of its value at entry (the rule of tlpk_options.refine_steps), decided on the device; after the first rejected step the
+ * remaining steps change nothing.  No host synchronisation: the work is enqueued on tlpk_stream(h) and complete after tlpk_sync.  steps = 0 measures
+ * only: one pass over A, no sweep, dx and dy untouched.  On a K1 handle, tlpk_solve_device + tlpk_polish_device(steps = s) equals bit for bit the solve of
+ * a handle created with refine_steps = s.
+ * tlpk_polish2_device: two systems at once -- the residuals of both from ONE pass over A, each correction ONE paired pass over L (as tlpk_solve2_device),
+ * every state word per system: each system's dx, dy and report are bit for bit those of tlpk_polish_device on it alone.  The four outputs are distinct from
+ * each other and from every input; the inputs may alias each other.  tlpk_polish: host pointers, blocks.
+ * Report (valid after tlpk_sync or a blocking call): tlpk_symbolic_get(h, "polish") = steps asked, accepted, rejected of system 0, then of system 1 (6 entries);
+ * tlpk_symbolic_get_f64(h, "polish_resid") = per system |r1|inf, |r2|inf at entry and |r1|inf, |r2|inf of what was kept (8 entries);
+ * tlpk_symbolic_get(h, "polish_bytes") = the device memory the first call allocated (part of device_bytes).  All zero before the first call and on every
+ * other kind of handle; tlpk_stats.refine_rejected is not touched.
+ * Handles: single-device handles with a factor -- K1 (row_block, dense_cols, refine_steps > 0 included) and K2.  Refused, in this order: a NULL handle;
+ * a multi-device, sharded (nranks > 1), dense-matrix, matrix-free or batch-loaded handle; a NULL pointer; steps < 0; an unfinished split-phase solve, pair
+ * or refinement step (all TLPK_BADARG, with a sentence in tlpk_last_error); TLPK_NO_DEVICE; TLPK_NOT_FACTORED.
+ * Memory: the first call allocates the residuals and corrections (2 (m + n) doubles per system; the second system's by the first pair) and, on a K2 handle
+ * (which holds the incidence matrix of the augmented system, not A), CSC and CSR copies of A -- or shares those of the device-resident loops if an LP is
+ * loaded; tlpk_set_values* marks them stale and the next call refreshes them.  Nothing is allocated at create.  An allocation that would cross
+ * mem_budget_bytes: TLPK_OOM, and the handle stays usable. */
+int tlpk_polish_device(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xi_p, const double *d_xi_d, int steps);
+int tlpk_polish2_device(tlpk_handle *h, double *d_dx0, double *d_dy0, const double *d_xi_p0, const double *d_xi_d0,
+                        double *d_dx1, double *d_dy1, const double *d_xi_p1, const double *d_xi_d1, int steps);
+int tlpk_polish(tlpk_handle *h, double *dx, double *dy, const double *xi_p, const double *xi_d, int steps);   /* host pointers, blocks */
 /* Copy the root panel (which = 0), the root rhs (which = 1) or the second root rhs of a pair (which = 2) out of (dir = 0) / into (dir = 1) a
  * caller-owned device buffer, on the handle's stream -- for callers whose communicator wants to
  * own the memory it reduces (torch.distributed tensors). */
@@ -464,6 +490,11 @@ int tlpk_ipm_hsolve_newton(tlpk_handle *h, const double *sc, double *out);
 /* step.jl:24-94: tlpk_ipm_factor without the wait for its status + tlpk_ipm_hsolve_newton: the paired solve's block-level forward sweeps
  * overlap the factorisation of the root front (tlpk_update_device_async); returns TLPK_NOT_POSDEF where tlpk_ipm_factor would have */
 int tlpk_ipm_factor_hsolve_newton(tlpk_handle *h, double regP, double regD, const double *sc, double *out);
+/* Refinement inside the loops, switched at run time (single-device handles with a factor and ONE LP loaded; anything else TLPK_BADARG with a sentence, an
+ * analysis-only handle TLPK_NO_DEVICE): from now on every KKT solve inside tlpk_ipm_hsolve, _newton, _hsolve_newton, _factor_hsolve_newton, tlpk_mpc_start and
+ * tlpk_mpc_newton is followed by `steps` steps of tlpk_polish_device on the same vectors -- the pair of _hsolve_newton by tlpk_polish2_device, so that the
+ * refined pair still makes paired passes over L.  steps = 0 restores the plain calls bit for bit.  K1 and K2. */
+int tlpk_ipm_set_polish(tlpk_handle *h, int steps);
 int tlpk_ipm_accept(tlpk_handle *h);                         /* step.jl:112-118: candidate -> accepted direction */
 int tlpk_ipm_advance(tlpk_handle *h, double alpha, double *out);   /* step.jl:139-148; out[0] = xl'zl + xu'zu */
 /* Read one device vector (nothing is written on the device; there is no setter).  `len` must be the vector's length.

@@ -87,6 +87,7 @@ EXPORTS = [
     "tlpk_refine_local", "tlpk_refine_finish", "tlpk_solve2_local", "tlpk_root_rhs2", "tlpk_solve2_finish", "tlpk_last_create_error",
     "tlpk_host_copy_threads", "tlpk_create_dense",
     "tlpk_set_values", "tlpk_set_values_device", "tlpk_set_values_dense", "tlpk_set_values_dense_device", "tlpk_ipm_reload",
+    "tlpk_polish_device", "tlpk_polish2_device", "tlpk_polish", "tlpk_ipm_set_polish",
     "tlpk_ipm_load_batch", "tlpk_ipm_batch_residuals", "tlpk_ipm_batch_factor", "tlpk_ipm_batch_hsolve_newton", "tlpk_ipm_batch_newton",
     "tlpk_ipm_batch_targets", "tlpk_ipm_batch_accept", "tlpk_ipm_batch_advance",
     "tlpk_mpc_batch_start", "tlpk_mpc_batch_newton", "tlpk_mpc_batch_gap", "tlpk_mpc_batch_targets", "tlpk_mpc_batch_advance",
@@ -132,6 +133,12 @@ def lib():
     L.tlpk_update_device_async.restype = C.c_int
     L.tlpk_solve2_device.argtypes = [vp] + [vp] * 8
     L.tlpk_solve2_device.restype = C.c_int
+    L.tlpk_polish_device.argtypes = [vp, vp, vp, vp, vp, C.c_int]
+    L.tlpk_polish2_device.argtypes = [vp] + [vp] * 8 + [C.c_int]
+    L.tlpk_polish.argtypes = [vp, pd, pd, pd, pd, C.c_int]
+    L.tlpk_ipm_set_polish.argtypes = [vp, C.c_int]
+    for name in ("tlpk_polish_device", "tlpk_polish2_device", "tlpk_polish", "tlpk_ipm_set_polish"):
+        getattr(L, name).restype = C.c_int
     L.tlpk_sync.argtypes = [vp]
     L.tlpk_stream.argtypes = [vp]
     L.tlpk_stream.restype = vp

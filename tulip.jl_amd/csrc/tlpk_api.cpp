@@ -903,6 +903,7 @@ static int create_device(tlpk_handle *h, const tlpk_options &def) {
             size_t free_b = 0, total_b = 0;
             hipMemGetInfo(&free_b, &total_b);
             const double budget = def.mem_budget_bytes > 0 ? (double)def.mem_budget_bytes : 0.9 * (double)free_b;
+            h->mem_budget = def.mem_budget_bytes > 0 ? def.mem_budget_bytes : 0;
             const double need = 8.0 * ((double)h->S.lval_len + (double)h->S.ubuf_len[0] + (double)h->S.ubuf_len[1] +
                                        (double)h->S.spart_len + (double)h->S.dinv_len + (double)h->S.uc_len +
                                        (double)h->S.gth_ptr.size() + (double)h->S.gth_src.size()) +
@@ -1094,6 +1095,7 @@ void tlpk_destroy(tlpk_handle *h) {
         if (h->pin_out) hipHostFree(h->pin_out);
         if (h->krylov_pin) hipHostFree(h->krylov_pin);
         if (h->krylov_pin2) hipHostFree(h->krylov_pin2);
+        if (h->polish.h_ref) hipHostFree(h->polish.h_ref);
         if (h->krylov_ev) hipEventDestroy(h->krylov_ev);
         for (hipEvent_t e : h->io_events) hipEventDestroy(e);
         for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
@@ -2040,6 +2042,154 @@ int tlpk_solve2_device(tlpk_handle *h, double *d_dx0, double *d_dy0, const doubl
     return solve_whole(h, SolveIo{2, {d_xip0, d_xip1}, {d_xid0, d_xid1}, {d_dx0, d_dx1}, {d_dy0, d_dy1}});
 }
 
+// ---- refinement on demand (include/tlpk.h: tlpk_polish_device; DESIGN.md section 1c') ----
+// The guarded refinement of tlpk_solve_device as a call of its own: any (dx, dy) against the current factor, K1 or K2, one system or a pair.  A step is
+// solve (through the same solve path) + candidate + residuals with their norms + verdict + commit (refine_kernels.hip); a pair forms both systems' residuals
+// in one pass over A and both corrections in one paired pass over L, with the state words of each system kept apart: a system of a pair ends bit for bit
+// as it does alone.  Nothing synchronises; the state words reach pinned memory by one copy at the end of the call.
+// The refusals, in the order the header promises
+static int polish_refuse(tlpk_handle *h, bool ptrs_ok, int steps, const char *me) {
+    if (!h) return TLPK_BADARG;
+    const char *kind = !h->sub.empty() ? "a multi-device handle (tlpk_create_multi)" : h->opt.nranks > 1 ? "a sharded handle (nranks > 1)"
+                     : h->S.dense_matrix ? "a dense-matrix handle (tlpk_create_dense)" : h->krylov ? "a matrix-free handle (tlpk_options.krylov)"
+                     : ipm_is_batch(h) ? "a batch-loaded handle (tlpk_ipm_load_batch)" : nullptr;
+    if (kind) { h->last_error = std::string(me) + ": single-device handles with a factor only; this is " + kind; return TLPK_BADARG; }
+    if (!ptrs_ok) { h->last_error = std::string(me) + ": a NULL pointer"; return TLPK_BADARG; }
+    if (steps < 0) { h->last_error = std::string(me) + ": steps = " + std::to_string(steps) + ", must be >= 0"; return TLPK_BADARG; }
+    if (h->pending != Pending::None) { h->last_error = std::string(me) + " inside an unfinished split-phase solve, pair or refinement step"; return TLPK_BADARG; }
+    if (!h->has_device) return TLPK_NO_DEVICE;
+    if (!h->factored) return TLPK_NOT_FACTORED;
+    return TLPK_OK;
+}
+// The buffers of `nr` systems and, K2, the copies of A, allocated by the first call that needs them.  Held against mem_budget_bytes BEFORE anything is
+// allocated: TLPK_OOM, and the handle is as it was.
+static int polish_prepare(tlpk_handle *h, int nr, const char *me) {
+    tlpk_handle::Polish &P = h->polish;
+    const bool k2 = h->S.system == 1;
+    const i64 un = user_n(h), um = user_m(h), nnz = k2 ? h->S.n : 0;
+    const i64 nn = std::max<i64>(un, 1), mm = std::max<i64>(k2 ? um : h->S.m, 1);
+    PolishMat loops{};
+    const bool shared = k2 && !P.A_ready && ipm_matrix(h, loops);
+    const bool build_A = k2 && !P.A_ready && !shared;
+    const int new_sets = (P.ready ? 0 : 1) + (nr == 2 && !P.pair_ready ? 1 : 0);      // (residuals and corrections of one system: 2 (n + m) doubles)
+    double need = 16.0 * (double)(nn + mm) * new_sets;
+    if (!P.ready) need += 8.0 * 2 * PW;
+    if (build_A) need += 8.0 * (double)(std::max<i64>(un + 1, 1) + std::max<i64>(um + 1, 1)) + 24.0 * (double)std::max<i64>(nnz, 1);
+    if (need > 0.0 && h->mem_budget > 0 && (double)h->device_bytes + need > (double)h->mem_budget) {
+        h->last_error = std::string(me) + ": the first call allocates " + std::to_string((long long)need) + " bytes, the handle holds " + std::to_string((long long)h->device_bytes) +
+                        ", mem_budget_bytes is " + std::to_string((long long)h->mem_budget);
+        return TLPK_OOM;
+    }
+    const i64 before = h->device_bytes;
+    int rc = TLPK_OK;
+    auto account = [&](int q) { P.bytes += h->device_bytes - before; return q; };
+    if (!P.h_ref) {
+        HIPCHK(h, hipHostMalloc((void **)&P.h_ref, 2 * PW * sizeof(unsigned long long), hipHostMallocDefault));
+        std::memset(P.h_ref, 0, 2 * PW * sizeof(unsigned long long));
+    }
+    // (every buffer is checked on its own: an allocation that failed half way leaves the flags unset and the next call completes the set)
+    if (!P.d_ref && (rc = dev_alloc(h, &P.d_ref, 2 * PW)) != TLPK_OK) return account(rc);
+    for (int r = 0; r < nr; ++r) {
+        if (!P.r1[r] && (rc = dev_alloc(h, &P.r1[r], mm)) != TLPK_OK) return account(rc);
+        if (!P.r2[r] && (rc = dev_alloc(h, &P.r2[r], nn)) != TLPK_OK) return account(rc);
+        if (!P.cx[r] && (rc = dev_alloc(h, &P.cx[r], nn)) != TLPK_OK) return account(rc);
+        if (!P.cy[r] && (rc = dev_alloc(h, &P.cy[r], mm)) != TLPK_OK) return account(rc);
+    }
+    P.ready = true;
+    if (nr == 2) P.pair_ready = true;
+    if (!P.A_ready) {
+        if (!k2) P.A = PolishMat{h->d.mu, h->d.n, h->d.Ap, h->d.Ai, h->d.Ax, h->d.Tp, h->d.Tj, h->d.Tx};
+        else if (shared) { P.A = loops; P.A_stale = h->ipm_stale; }
+        else {
+            // the route of the device-resident loops' own copies (tlpk_ipm.cpp: ipm_sub_matrix): A rebuilt from the incidence matrix the handle holds
+            std::vector<i64> ap, tp; std::vector<i32> ai, tj; std::vector<double> ax, tx;
+            if ((rc = ipm_host_matrix(h, ap, ai, ax, tp, tj, tx)) != TLPK_OK) return account(rc);
+            i64 *dp = nullptr, *dt = nullptr; i32 *di = nullptr, *dj = nullptr; double *dxv = nullptr, *dtv = nullptr;
+            if ((rc = dev_upload(h, &dp, ap)) != TLPK_OK || (rc = dev_upload(h, &di, ai)) != TLPK_OK || (rc = dev_upload(h, &dxv, ax)) != TLPK_OK ||
+                (rc = dev_upload(h, &dt, tp)) != TLPK_OK || (rc = dev_upload(h, &dj, tj)) != TLPK_OK || (rc = dev_upload(h, &dtv, tx)) != TLPK_OK) return account(rc);
+            P.A = PolishMat{um, un, dp, di, dxv, dt, dj, dtv};
+            P.own_A = true; P.A_stale = false;
+        }
+        P.A_ready = true;
+    }
+    account(TLPK_OK);
+    if (k2 && P.A_stale) {
+        // new values since the copies were filled (tlpk_set_values*): same pattern, the two value arrays in place.  (Copies shared with the loops: what
+        // tlpk_ipm_reload writes there as well.)
+        std::vector<i64> ap, tp; std::vector<i32> ai, tj; std::vector<double> ax, tx;
+        if ((rc = ipm_host_matrix(h, ap, ai, ax, tp, tj, tx)) != TLPK_OK) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (!ax.empty()) {
+            HIPCHK(h, hipMemcpy(const_cast<double *>(P.A.Ax), ax.data(), ax.size() * 8, hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(const_cast<double *>(P.A.Tx), tx.data(), tx.size() * 8, hipMemcpyHostToDevice));
+        }
+        P.A_stale = false;
+    }
+    return TLPK_OK;
+}
+static int polish_run(tlpk_handle *h, int nr, double *const *dx, double *const *dy, const double *const *xp, const double *const *xd, int steps, const char *me) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = polish_prepare(h, nr, me)) return rc;
+    tlpk_handle::Polish &P = h->polish;
+    const i64 un = user_n(h), um = user_m(h);
+    const bool whole = graph_usable_solve(h);
+    P.asked[0] = steps; P.asked[1] = nr == 2 ? steps : 0;
+    PolishVecs v{}, vc{}; PolishPair pp{};
+    for (int s = 0; s < 2; ++s) {
+        const int r = std::min(s, nr - 1);
+        v.xi_p[s] = vc.xi_p[s] = xp[r]; v.xi_d[s] = vc.xi_d[s] = xd[r];
+        v.dx[s] = dx[r]; v.dy[s] = dy[r]; vc.dx[s] = P.cx[r]; vc.dy[s] = P.cy[r];
+        v.r1[s] = vc.r1[s] = P.r1[r]; v.r2[s] = vc.r2[s] = P.r2[r];
+        pp.x[s] = dx[r]; pp.y[s] = dy[r]; pp.cx[s] = P.cx[r]; pp.cy[s] = P.cy[r];
+    }
+    HIPCHK(h, hipMemsetAsync(P.d_ref, 0, 2 * PW * sizeof(unsigned long long), h->stream));
+    { ProfScope ps(h, TLPK_KC_SPMV); launch_kkt_resid(h->stream, P.A, h->d_theta, h->d_regP, h->d_regD, v, P.d_ref, nr, 1); }
+    for (int it = 0; it < steps; ++it) {
+        int rc;
+        if (nr == 2 && h->S.sweep) rc = solve_whole(h, SolveIo{2, {P.r1[0], P.r1[1]}, {P.r2[0], P.r2[1]}, {P.cx[0], P.cx[1]}, {P.cy[0], P.cy[1]}});
+        else {
+            // (one system; or the launch-per-block schedule, TLPK_SWEEP=0, which has no two-rhs kernels: two ordinary solves, as tlpk_solve2_device)
+            rc = solve_composed(h, solve_io(P.cx[0], P.cy[0], P.r1[0], P.r2[0]), whole);
+            if (rc == TLPK_OK && nr == 2) rc = solve_composed(h, solve_io(P.cx[1], P.cy[1], P.r1[1], P.r2[1]), whole);
+        }
+        if (rc != TLPK_OK) return rc;
+        launch_polish_candidate(h->stream, un, um, pp, nr);
+        // residuals of the candidates: the next step's right-hand sides where a candidate is kept (a system that has stopped is swept on, its commit is skipped)
+        { ProfScope ps(h, TLPK_KC_SPMV); launch_kkt_resid(h->stream, P.A, h->d_theta, h->d_regP, h->d_regD, vc, P.d_ref, nr, 0); }
+        launch_polish_decide(h->stream, P.d_ref, nr);
+        launch_polish_commit(h->stream, un, um, pp, P.d_ref, nr);
+        HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(P.h_ref, P.d_ref, 2 * PW * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipGetLastError());
+    return TLPK_OK;
+}
+int tlpk_polish_device(tlpk_handle *h, double *d_dx, double *d_dy, const double *d_xip, const double *d_xid, int steps) {
+    if (int g = polish_refuse(h, d_dx && d_dy && d_xip && d_xid, steps, "tlpk_polish_device")) return g;
+    double *dx[2] = {d_dx, d_dx}, *dy[2] = {d_dy, d_dy}; const double *xp[2] = {d_xip, d_xip}, *xd[2] = {d_xid, d_xid};
+    return polish_run(h, 1, dx, dy, xp, xd, steps, "tlpk_polish_device");
+}
+int tlpk_polish2_device(tlpk_handle *h, double *d_dx0, double *d_dy0, const double *d_xip0, const double *d_xid0,
+                        double *d_dx1, double *d_dy1, const double *d_xip1, const double *d_xid1, int steps) {
+    if (int g = polish_refuse(h, d_dx0 && d_dy0 && d_xip0 && d_xid0 && d_dx1 && d_dy1 && d_xip1 && d_xid1, steps, "tlpk_polish2_device")) return g;
+    double *dx[2] = {d_dx0, d_dx1}, *dy[2] = {d_dy0, d_dy1}; const double *xp[2] = {d_xip0, d_xip1}, *xd[2] = {d_xid0, d_xid1};
+    return polish_run(h, 2, dx, dy, xp, xd, steps, "tlpk_polish2_device");
+}
+// host pointers; blocks
+int tlpk_polish(tlpk_handle *h, double *dx, double *dy, const double *xi_p, const double *xi_d, int steps) {
+    if (int g = polish_refuse(h, dx && dy && xi_p && xi_d, steps, "tlpk_polish")) return g;
+    HIPCHK(h, hipSetDevice(h->device));
+    const i64 un = user_n(h), um = user_m(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (un > 0) { HIPCHK(h, hipMemcpy(h->d_dx, dx, (size_t)un * 8, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(h->d_xid, xi_d, (size_t)un * 8, hipMemcpyHostToDevice)); }
+    if (um > 0) { HIPCHK(h, hipMemcpy(h->d_dy, dy, (size_t)um * 8, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(h->d_xip, xi_p, (size_t)um * 8, hipMemcpyHostToDevice)); }
+    if (int rc = tlpk_polish_device(h, h->d_dx, h->d_dy, h->d_xip, h->d_xid, steps)) return rc;
+    if (int rc = tlpk_sync(h)) return rc;
+    if (un > 0) HIPCHK(h, hipMemcpy(dx, h->d_dx, (size_t)un * 8, hipMemcpyDeviceToHost));
+    if (um > 0) HIPCHK(h, hipMemcpy(dy, h->d_dy, (size_t)um * 8, hipMemcpyDeviceToHost));
+    return TLPK_OK;
+}
+
 // The pair in two halves, for sharded handles: tlpk_solve2_local -> all-reduce of tlpk_root_rhs AND tlpk_root_rhs2 (the root right-hand
 // sides of the two systems; one collective over both buffers if the communicator allows) -> tlpk_solve2_finish.
 int tlpk_solve2_local(tlpk_handle *h, const double *d_xip0, const double *d_xid0, const double *d_xip1, const double *d_xid1) {
@@ -2806,6 +2956,7 @@ int set_values_common(tlpk_handle *h, const double *nzval, int64_t len, bool fro
         }
     } catch (const std::bad_alloc &) { rc = TLPK_OOM; h->last_error = std::string(what) + ": host out of memory"; }
     if (rc == TLPK_OK && h->ipm) h->ipm_stale = true;
+    if (rc == TLPK_OK && h->polish.A_ready) h->polish.A_stale = true;      // K2: the copies of A the refinement on demand reads are refreshed by its next call
     return rc;
 }
 
@@ -3037,6 +3188,18 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
     else if (w == "front_unit") { if (h->front_unit.empty()) tmp.assign(S.fronts.size() + S.single_col.size(), -1); else from32(h->front_unit); }
     else if (w == "front_skip") tmp.assign(h->skip_host.begin(), h->skip_host.end());
     else if (w == "skip_bytes") tmp.assign(1, h->skip_dev_bytes);
+    // refinement on demand (tlpk_polish_device / tlpk_polish2_device), valid after tlpk_sync: steps asked, accepted, rejected of system 0, then of system 1;
+    // the device memory its first call allocated.  Zeros before the first call
+    else if (w == "polish") {
+        tmp.assign(6, 0);
+        if (const unsigned long long *r = h->polish.h_ref)
+            for (int s = 0; s < 2; ++s) {
+                tmp[3 * s] = h->polish.asked[s];
+                tmp[3 * s + 1] = reinterpret_cast<const int *>(r + s * PW + PW_ACCEPT)[1];
+                tmp[3 * s + 2] = reinterpret_cast<const int *>(r + s * PW + PW_STATE)[0];
+            }
+    }
+    else if (w == "polish_bytes") tmp.assign(1, h->polish.bytes);
     else if (w == "singles") {
         tmp = S.single_loff; tmp.insert(tmp.end(), S.single_dinvoff.begin(), S.single_dinvoff.end()); tmp.insert(tmp.end(), S.single_col.begin(), S.single_col.end());
         tmp.push_back(S.n_zero_lower); tmp.push_back(S.spart_len);
@@ -3053,6 +3216,18 @@ int64_t tlpk_symbolic_get_f64(const tlpk_handle *h, const char *what, double *bu
     if (w == "krylov_pair_resid") {              // of the last pair on a matrix-free handle: resid0, resid of number 0, then of number 1
         const i64 len = 4;
         if (buf) std::copy(h->krylov_pair_resid, h->krylov_pair_resid + std::min(len, cap), buf);
+        return len;
+    }
+    if (w == "polish_resid") {                   // of the last refinement on demand, per system: |r1|inf, |r2|inf at entry, then of what was kept
+        const tlpk_handle *k = h->sub.empty() ? h : h->sub[0];
+        double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (const unsigned long long *r = k->polish.h_ref)
+            for (int s = 0; s < 2; ++s) {
+                const int src[4] = {PW_R1_IN, PW_R2_REF, PW_R1, PW_R2_KEPT};
+                for (int q = 0; q < 4; ++q) std::memcpy(&v[4 * s + q], r + s * PW + src[q], 8);
+            }
+        const i64 len = 8;
+        if (buf) std::copy(v, v + std::min(len, cap), buf);
         return len;
     }
     if (w != "pair_w") return -1;

@@ -136,6 +136,20 @@ void launch_absmax2(hipStream_t st, const DevArrays &a, const double *r1, const 
 void launch_refine_decide(hipStream_t st, unsigned long long *ref);
 void launch_candidate(hipStream_t st, i64 n, const double *x, double *cx, i64 m, const double *y, double *cy);
 void launch_refine_commit(hipStream_t st, i64 n, double *x, const double *cx, i64 m, double *y, const double *cy, const unsigned long long *ref);
+// refinement on demand (refine_kernels.hip; tlpk_polish_device / tlpk_polish2_device): A as the caller sees it (K2: the copies built by the first
+// call), the vectors of one or two systems (slot 1 repeats slot 0 for one), and the state words of a system -- PW of them, system r at ref + r * PW:
+// bit patterns of non-negative doubles (PW_R1: |r1| of the kept iterate, PW_R2_REF: |r2| at entry, PW_C1 / PW_C2: of the candidate, PW_R1_IN: |r1| at
+// entry, PW_R2_KEPT: |r2| of the kept iterate), PW_STATE = {int rejected, int stop}, PW_ACCEPT = {int verdict of the last step, int accepted steps}
+struct PolishMat { i64 m, n; const i64 *Ap; const i32 *Ai; const double *Ax; const i64 *Tp; const i32 *Tj; const double *Tx; };
+struct PolishVecs { const double *xi_p[2], *xi_d[2], *dx[2], *dy[2]; double *r1[2], *r2[2]; };
+struct PolishPair { double *x[2], *y[2], *cx[2], *cy[2]; };
+enum : int { PW_R1 = 0, PW_R2_REF = 1, PW_C1 = 2, PW_C2 = 3, PW_STATE = 4, PW_ACCEPT = 5, PW_R1_IN = 6, PW_R2_KEPT = 7, PW = 8 };
+// residuals of nr systems in one pass over A, with their max-norms: entry != 0 -> the norms of the iterate a call starts from, else the candidate's
+void launch_kkt_resid(hipStream_t st, const PolishMat &A, const double *theta, const double *regP, const double *regD, const PolishVecs &v,
+                      unsigned long long *ref, int nr, int entry);
+void launch_polish_decide(hipStream_t st, unsigned long long *ref, int nr);
+void launch_polish_candidate(hipStream_t st, i64 n, i64 m, const PolishPair &p, int nr);
+void launch_polish_commit(hipStream_t st, i64 n, i64 m, const PolishPair &p, const unsigned long long *ref, int nr);
 void launch_sum_to(hipStream_t st, i64 len, double *out, const double *own, const double *src, int nsrc, i64 stride);
 void launch_sum_ranked(hipStream_t st, i64 len, double *inout, const double *stage, int nranks, int own_rank, i64 stride);
 void launch_k2_diag(hipStream_t st, i64 n, const double *theta, const double *regP, double *D2);

@@ -54,6 +54,19 @@ struct tlpk_handle {
     unsigned long long *d_ref = nullptr;          // guarded refinement: norms and verdict words (kernels.hip: k_refine_decide)
     i64 refine_rejected = 0;                      // refinement steps of the last solve that did not shrink the residual and were discarded
     double *d_bx = nullptr, *d_by = nullptr;      // multi-device refinement: the iterate before a step (restored if the step is rejected)
+    // refinement on demand (tlpk_polish_device / tlpk_polish2_device; tlpk_api.cpp: polish_*), everything allocated by the first call: residuals and
+    // corrections of two systems, the state words of both (tlpk_device.hpp: PolishWord) and their pinned copy, K2: the device copies of A
+    struct Polish {
+        double *r1[2] = {nullptr, nullptr}, *r2[2] = {nullptr, nullptr}, *cx[2] = {nullptr, nullptr}, *cy[2] = {nullptr, nullptr};
+        unsigned long long *d_ref = nullptr, *h_ref = nullptr;
+        bool ready = false, pair_ready = false;   // the first set / the second set (allocated by the first pair) is there
+        PolishMat A{};                            // K1: the handle's own copies; K2: own copies, or the loops' (tlpk_ipm_load)
+        bool own_A = false, A_ready = false, A_stale = false;   // A_stale: tlpk_set_values* since the K2 copies were filled
+        i64 asked[2] = {0, 0};                    // steps asked of the last call, per system
+        i64 bytes = 0;                            // device memory of all of this (tlpk_symbolic_get "polish_bytes")
+        int ipm_steps = 0;                        // tlpk_ipm_set_polish
+    } polish;
+    i64 mem_budget = 0;                           // tlpk_options.mem_budget_bytes (0 = none given): what a first-use allocation is held against
     int *h_info = nullptr;
     double *pin_in = nullptr, *pin_out = nullptr;   // pinned staging of the host-pointer entry points (lazily allocated)
     bool io_timing = false; double io_t_first = 0, io_t_last = 0;   // TLPK_HOSTIO_TIMING: when the first / last device-to-host group had landed
@@ -147,6 +160,10 @@ void skip_off(tlpk_handle *h);
 
 void ipm_free(tlpk_handle *h);          // tlpk_ipm.cpp
 bool ipm_is_batch(const tlpk_handle *h);   // tlpk_ipm.cpp: the handle holds a stack of LPs (tlpk_ipm_load_batch)
+// tlpk_ipm.cpp, for the refinement on demand of a K2 handle (whose own arrays hold the incidence matrix): the host copies of A, column-major and
+// row-major, as the loops build theirs; the loops' own device copies of the whole A (false: none -- no LP loaded, a stack of LPs, or the loops share the handle's)
+int ipm_host_matrix(tlpk_handle *h, std::vector<i64> &ap, std::vector<i32> &ai, std::vector<double> &ax, std::vector<i64> &tp, std::vector<i32> &tj, std::vector<double> &tx);
+bool ipm_matrix(const tlpk_handle *h, PolishMat &A);
 int sync_host_values(tlpk_handle *h);   // tlpk_api.cpp: S.Ax <- the device copy after a tlpk_set_values*_device
 // tlpk_api.cpp, for tlpk_ipm_batch_refill: the refresh of tlpk_set_values restricted to the LPs of a stack whose flag is set (d_flag[k * stride] != 0; d_lp_of: the LP of
 // every entry of nzval; ranges: (lo, hi) pairs, the entries of nzval that are read).  Enqueued on the handle's stream.

@@ -156,7 +156,11 @@ template <class F>
 int solve_all(tlpk_handle *h, Shards &sh, F &&pick) {
     double *dx[MAX_DEVICES], *dy[MAX_DEVICES]; const double *xp[MAX_DEVICES], *xd[MAX_DEVICES];
     for (int r = 0; r < sh.n; ++r) pick(*sh.c[r]->ipm, dx[r], dy[r], xp[r], xd[r]);
-    if (!sh.multi) return tlpk_solve_device(h, dx[0], dy[0], xp[0], xd[0]);
+    if (!sh.multi) {
+        const int rc = tlpk_solve_device(h, dx[0], dy[0], xp[0], xd[0]);
+        // tlpk_ipm_set_polish: every KKT solve of the loops is followed by guarded refinement steps on the same vectors
+        return rc != TLPK_OK || h->polish.ipm_steps == 0 ? rc : tlpk_polish_device(h, dx[0], dy[0], xp[0], xd[0], h->polish.ipm_steps);
+    }
     return multi_solve_resident(h, dx, dy, xp, xd);
 }
 
@@ -266,6 +270,17 @@ static int ipm_sub_matrix(tlpk_handle *h, bool shard, std::vector<i64> &ap, std:
     { std::vector<i64> cur(tp.begin(), tp.end() - 1);
       for (i64 j = 0; j < n; ++j) for (i64 q = ap[(size_t)j]; q < ap[(size_t)j + 1]; ++q) { const i64 c2 = cur[(size_t)ai[(size_t)q]]++; tj[(size_t)c2] = (i32)j; tx[(size_t)c2] = ax[(size_t)q]; } }
     return TLPK_OK;
+}
+extern "C++" int ipm_host_matrix(tlpk_handle *h, std::vector<i64> &ap, std::vector<i32> &ai, std::vector<double> &ax, std::vector<i64> &tp, std::vector<i32> &tj,
+                                 std::vector<double> &tx) {
+    return ipm_sub_matrix(h, false, ap, ai, ax, tp, tj, tx);
+}
+extern "C++" bool ipm_matrix(const tlpk_handle *h, PolishMat &A) {
+    if (!h->ipm || h->ipm->bat || h->S.dense_matrix) return false;
+    const IpmVecs &v = h->ipm->v;
+    if (v.Ap == h->d.Ap || !v.Ap) return false;
+    A = PolishMat{v.m, v.n, v.Ap, v.Ai, v.Ax, v.Tp, v.Tj, v.Tx};
+    return true;
 }
 
 static int ipm_load_impl(tlpk_handle *h, const double *b, const double *c, const double *l, const double *u, bool shard) {
@@ -429,6 +444,20 @@ int tlpk_ipm_reset(tlpk_handle *h) {
         HIPCHK(h, hipSetDevice(c->device));
         ipm_launch_init(c->stream, c->ipm->v);
     }
+    return TLPK_OK;
+}
+
+/* From now on every KKT solve of the unbatched loops on this handle is followed by `steps` guarded refinement steps (tlpk_polish_device; the pair of
+ * tlpk_ipm_hsolve_newton by tlpk_polish2_device).  steps = 0: the calls as they are without it. */
+int tlpk_ipm_set_polish(tlpk_handle *h, int steps) {
+    if (!h) return TLPK_BADARG;
+    const char *kind = !h->sub.empty() ? "a multi-device handle" : h->opt.nranks > 1 ? "a sharded handle" : h->S.dense_matrix ? "a dense-matrix handle"
+                     : h->krylov ? "a matrix-free handle" : ipm_is_batch(h) ? "a batch-loaded handle" : nullptr;
+    if (kind) { h->last_error = std::string("tlpk_ipm_set_polish: single-device handles with a factor and one LP loaded only; this is ") + kind; return TLPK_BADARG; }
+    if (!h->has_device) return TLPK_NO_DEVICE;
+    if (!h->ipm) { h->last_error = "tlpk_ipm_set_polish: tlpk_ipm_load has not been called"; return TLPK_BADARG; }
+    if (steps < 0) { h->last_error = "tlpk_ipm_set_polish: steps = " + std::to_string(steps) + ", must be >= 0"; return TLPK_BADARG; }
+    h->polish.ipm_steps = steps;
     return TLPK_OK;
 }
 
@@ -610,6 +639,7 @@ int tlpk_ipm_hsolve_newton(tlpk_handle *h, const double *sc, double *out) {
     if (!sh.multi) {
         IpmState &s = *h->ipm; const IpmDir &dst = s.D[s.cur];
         rc = tlpk_solve2_device(h, s.v.hx, s.v.hy, s.v.b, s.v.hxid, dst.x, dst.y, s.v.xip, s.v.xid);
+        if (rc == TLPK_OK && h->polish.ipm_steps > 0) rc = tlpk_polish2_device(h, s.v.hx, s.v.hy, s.v.b, s.v.hxid, dst.x, dst.y, s.v.xip, s.v.xid, h->polish.ipm_steps);
     } else {
         double *dx0[MAX_DEVICES], *dy0[MAX_DEVICES], *dx1[MAX_DEVICES], *dy1[MAX_DEVICES];
         const double *xp0[MAX_DEVICES], *xd0[MAX_DEVICES], *xp1[MAX_DEVICES], *xd1[MAX_DEVICES];

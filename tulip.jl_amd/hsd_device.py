@@ -37,7 +37,10 @@ class Options:
 
 
 class DeviceHSD:
-    def __init__(self, A, b, c, l, u, c0=0.0, objsense_min=True, options=None, system="K1", pair_solves=True, overlap_root=False, dense=False, **backend_kw):
+    def __init__(self, A, b, c, l, u, c0=0.0, objsense_min=True, options=None, system="K1", pair_solves=True, overlap_root=False, dense=False, polish=0,
+                 **backend_kw):
+        # polish: guarded refinement steps behind every KKT solve of the loop (tlpk_ipm_set_polish; K1 and K2, one device, not dense / Krylov): on K1 the
+        # iterates of a handle created with refine=k, but the pair of an iteration stays a pair; set_polish(k) switches it at run time
         # dense: A is a dense 2-D array and goes to the dense backend (tlpk_create_dense; K1, one device: device, profile, mem_budget_bytes)
         # pair_solves: the h-system and the predictor share one pass over the factor (tlpk_ipm_hsolve_newton; same arithmetic)
         # overlap_root: the factorisation does not wait for its status before that pair is enqueued (tlpk_ipm_factor_hsolve_newton);
@@ -82,7 +85,15 @@ class DeviceHSD:
         self.L = _lib.lib()
         self._l, self._u = l, u
         self._call(self.L.tlpk_ipm_load(self.kkt._h, _lib.as_pd(self._b), _lib.as_pd(self._c), _lib.as_pd(l), _lib.as_pd(u)))
+        self.polish = 0
+        if int(polish) != 0:
+            self.set_polish(polish)
         self._init_loop()
+
+    def set_polish(self, steps):
+        """tlpk_ipm_set_polish: `steps` guarded refinement steps behind every KKT solve of the loop from now on; 0 restores the plain calls."""
+        self._call(self.L.tlpk_ipm_set_polish(self.kkt._h, int(steps)))
+        self.polish = int(steps)
 
     def _init_loop(self):
         """The host state of a freshly loaded LP (needs L, kkt, m, n, opt and the LP's vectors; tests/test_ipm_kernels.py runs it on a stand-in library)."""

@@ -372,6 +372,42 @@ class HIPNormalEquations:
         if sync:
             _raise_for(_lib.lib().tlpk_sync(self._h), self._h)
 
+    def polish_device(self, d_dx, d_dy, d_xip, d_xid, steps=1, sync=True):
+        """tlpk_polish_device: up to `steps` guarded refinement steps on (dx, dy) in place, K1 or K2; steps=0 measures only (polish_report)."""
+        _raise_for(_lib.lib().tlpk_polish_device(self._h, d_dx, d_dy, d_xip, d_xid, int(steps)), self._h, "polish: ")
+        if sync:
+            _raise_for(_lib.lib().tlpk_sync(self._h), self._h)
+
+    def polish2_device(self, d_dx0, d_dy0, d_xip0, d_xid0, d_dx1, d_dy1, d_xip1, d_xid1, steps=1, sync=True):
+        """tlpk_polish2_device: two systems in one pass over A and one paired pass over L per step; each ends bit for bit as polish_device leaves it alone.
+        Buffer rules as for solve2_device."""
+        _raise_for(_lib.lib().tlpk_polish2_device(self._h, d_dx0, d_dy0, d_xip0, d_xid0, d_dx1, d_dy1, d_xip1, d_xid1, int(steps)), self._h, "polish: ")
+        if sync:
+            _raise_for(_lib.lib().tlpk_sync(self._h), self._h)
+
+    def polish(self, dx, dy, xi_p, xi_d, steps=1):
+        """tlpk_polish on host arrays: dx, dy (the output of `solve`, or any other approximation) are corrected in place; blocks.  Returns polish_report()."""
+        if not (isinstance(dx, np.ndarray) and isinstance(dy, np.ndarray) and dx.dtype == np.float64
+                and dy.dtype == np.float64 and dx.flags.c_contiguous and dy.flags.c_contiguous):
+            raise TypeError("dx, dy must be contiguous float64 numpy vectors (modified in place)")
+        if dx.shape != (self.n,):
+            raise DimensionMismatch(f"length(dx)={dx.shape[0]} but KKT solver has n={self.n}")
+        if dy.shape != (self.m,):
+            raise DimensionMismatch(f"length(dy)={dy.shape[0]} but KKT solver has m={self.m}")
+        xp = _vec(xi_p, "ξp", ("m", self.m), "")
+        xd = _vec(xi_d, "ξd", ("n", self.n), "")
+        rc = _lib.lib().tlpk_polish(self._h, _lib.as_pd(dx), _lib.as_pd(dy), _lib.as_pd(xp), _lib.as_pd(xd), int(steps))
+        _raise_for(rc, self._h, "polish: ")
+        return self.polish_report()
+
+    def polish_report(self):
+        """What the last polish call did (after a sync): per system the steps asked / accepted / rejected and |r1|inf, |r2|inf at entry and of what was kept;
+        `bytes`: the device memory the first call allocated.  All zero before the first call."""
+        cnt = _lib.symbolic_array(self._h, "polish"); res = _lib.symbolic_array_f64(self._h, "polish_resid")
+        sides = [{"asked": int(cnt[3 * s]), "accepted": int(cnt[3 * s + 1]), "rejected": int(cnt[3 * s + 2]),
+                  "r1_in": float(res[4 * s]), "r2_in": float(res[4 * s + 1]), "r1": float(res[4 * s + 2]), "r2": float(res[4 * s + 3])} for s in range(2)]
+        return {"sides": sides, "bytes": int(_lib.symbolic_array(self._h, "polish_bytes")[0])}
+
     def sync(self):
         _raise_for(_lib.lib().tlpk_sync(self._h), self._h)
 

@@ -18,7 +18,8 @@ from .kkt import OutOfMemoryError, PosDefException
 
 
 class DeviceMPC(DeviceHSD):
-    """Shares the vectors on the device, the residual / status quantities and the accessors with DeviceHSD."""
+    """Shares the vectors on the device, the residual / status quantities and the accessors with DeviceHSD -- and its constructor: DeviceMPC(..., polish=k)
+    puts k guarded refinement steps behind every KKT solve of tlpk_mpc_start and tlpk_mpc_newton (set_polish(k) at run time)."""
 
     def _init_loop(self):
         super()._init_loop()
