@@ -443,6 +443,158 @@ __global__ __launch_bounds__(256, 4) void k_ea_gather(const EaTask *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------
+// The panel columns of the formed fronts over the FLAT SEGMENT LIST (TLPK_EA_SEGLIST; symbolic.cpp step 14'') instead of the task list.
+// k_ea_gather<true> gives a wave ONE parent column: task -> FrontDesc -> eg_base -> eg_col -> eg_ptr / asm_ptr, then per segment the entries and assembled
+// rows, then rel, U and the assembled values -- some fifteen dependent round trips in front of a column's stores, and nothing is fetched across a segment
+// or a column.  Here a wave owns `chunk` consecutive records [s0 + w chunk, ...) of the launch's range (static: no ticket, no flag, nothing crosses waves),
+// each record one segment with all of that spelled out.  Records come two ahead (wave-uniform: scalar loads); the contributor entries and assembled rows of
+// record i + 1 are requested before record i is added, lane by lane as in eg_entries_lanes; so a segment whose contributors are thin waits for ONE round trip
+// -- rel, U and the assembled values -- and the start-up chain is paid once per chunk.  Measured, that alone gained 0.1 ms of 1.4 per
+// launch and nothing the step time showed: on C4 most of the U entries sit in batches with a contributor of more than EG_CH x 64 rows, where every trip of
+// 4 x 64 rows was a round trip of its own.  What pays is issuing those trips ahead (es_issue below).  The arithmetic of a segment is k_ea_gather<true>'s: zeros and the assembled
+// entries, the contributors in list order through the wave's LDS slice, one contiguous write, a segment without contributor written all the same; the rows
+// its column stores above the diagonal and below f are zeroed by its first and last segment.  Segments are independent (disjoint rows, own lists): the bits
+// do not depend on which wave takes which.  No DevCtx: the loop keeps eight pointers.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ EaGatherEnt es_entry(const EaGatherEnt *__restrict__ ent, const i64 e, const i64 e1, const int lane) {      // lane u: entry e + u of a list that ends at e1 (may be empty)
+    return ent[max(min(e + (lane & (EG_EB - 1)), e1 - 1), (i64)0)];
+}
+__device__ __forceinline__ EgBatch es_batch(const EaGatherEnt &g, const i64 e, const i64 e1, const i32 *__restrict__ rel, const double *U0, const double *U1) {
+    EgBatch b;
+#pragma unroll
+    for (int u = 0; u < EG_EB; ++u) {
+        const i64 src = eg_rl64(g.src, u), rl = eg_rl64(g.rel, u);
+        b.rl[u] = rel + rl;
+        b.sr[u] = (((src >> EG_UBUF_BIT) & 1) ? U1 : U0) + (src & (((i64)1 << EG_UBUF_BIT) - 1));
+        b.n[u] = (e + u < e1) ? __builtin_amdgcn_readlane(g.n, u) : 0;
+    }
+    return b;
+}
+// A contributor of more than EG_CH x 64 rows is added in TRIPS of 4 x 64 rows (the thick path of k_ea_gather: a trip's loads, then its adds, then the next trip's
+// loads).  Here the trips of a batch -- contributor after contributor, rows ascending: the order of the adds is unchanged -- are issued one ahead: while a trip is
+// added the loads of the next one are in flight, and the first trip of a batch is requested before the slice is seeded (a second trip ahead took the
+// kernel to 52 bytes of scratch per lane).  The cursor (cu, crr) = (contributor of the batch, its first row not yet requested) is wave-uniform; the
+// contributor's entry is read from lane cu of the batch's entries.
+struct EsTrip { i32 tq[4]; double w[4]; i32 rem; };        // targets in the slice and values of rows crr + lane + 64 k; rem = rows of the contributor from crr on (0: no trip)
+__device__ __forceinline__ void es_issue(EsTrip &t, const EaGatherEnt &g, int &cu, i32 &crr, const i32 *__restrict__ rel, const double *U0, const double *U1, const i32 r0, const int lane) {
+    const i32 nu = __builtin_amdgcn_readlane(g.n, cu);
+    const i64 src = eg_rl64(g.src, cu), rl = eg_rl64(g.rel, cu);
+    const i32 *rp = rel + rl + crr;
+    const double *sp = (((src >> EG_UBUF_BIT) & 1) ? U1 : U0) + (src & (((i64)1 << EG_UBUF_BIT) - 1)) + crr;
+    t.rem = nu - crr;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const i32 ru = min(lane + 64 * k, t.rem - 1); t.tq[k] = rp[ru] - r0; t.w[k] = sp[ru]; }
+    crr += 256;
+    if (crr >= nu) { ++cu; crr = 0; }
+}
+__global__ __launch_bounds__(256, 4) void k_ea_seglist(const EaSeg *__restrict__ seg, const i64 s0, const i64 s1, const int chunk, const int slice_rows, double *Lval,
+                                                       const double *U0, const double *U1, const i32 *__restrict__ rel, const EaGatherEnt *__restrict__ ent,
+                                                       const unsigned short *__restrict__ asm_row, const unsigned char *__restrict__ front_skip) {
+    extern __shared__ double es_slices[];           // [4 waves][slice_rows], slice_rows = the longest segment of the launch (EaGatherLaunch::rows)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double *slice = es_slices + (size_t)wave * slice_rows;
+    const i64 i0 = s0 + ((i64)blockIdx.x * 4 + wave) * chunk;
+    if (i0 >= s1) return;                           // (the last workgroup of a launch: fewer chunks than waves)
+    const i64 i1 = min(i0 + chunk, s1);
+    // records i and i + 1, and of record i what was requested while record i - 1 was added: lane u's contributor entry, the first EG_AL x 64 assembled rows
+    EaSeg r = seg[i0], rn = seg[min(i0 + 1, i1 - 1)];
+    EaGatherEnt ge = es_entry(ent, r.e0, r.e0 + r.ne, lane);
+    i32 arow[EG_AL];
+#pragma unroll
+    for (int k = 0; k < EG_AL; ++k) arow[k] = r.na > 0 ? asm_row[r.a0 + min(lane + 64 * k, (i32)r.na - 1)] : 0;      // (wave-uniform guard: an empty list may end the array)
+    bool skip = front_skip != nullptr && front_skip[r.front] != 0;      // block skip (wave-uniform): the record is passed over before anything its front owns is touched
+    for (i64 i = i0; i < i1; ++i) {
+        const EaSeg rnn = seg[min(i + 2, i1 - 1)];
+        // record i + 1 (past the chunk: the last record again, valid to read): its entries and assembled rows are on their way while record i is added
+        const EaGatherEnt gen = es_entry(ent, rn.e0, rn.e0 + rn.ne, lane);
+        i32 arown[EG_AL];
+#pragma unroll
+        for (int k = 0; k < EG_AL; ++k) arown[k] = rn.na > 0 ? asm_row[rn.a0 + min(lane + 64 * k, (i32)rn.na - 1)] : 0;
+        const bool skipn = front_skip != nullptr && front_skip[rn.front] != 0;
+        const i32 n = r.n, na = r.na, r0 = r.r0;
+        if (!skip && n <= slice_rows) {             // (n > slice_rows never: the slice is sized by the same rule)
+            double *__restrict__ col = Lval + r.dst;
+            const i64 e0 = r.e0, e1 = r.e0 + r.ne, a0 = r.a0;
+            // what the column stores outside [tc, f): above the diagonal in its 64-column slice (first segment), the padding rows [f, lda) (last segment)
+            if (lane < (i32)r.za) col[lane - (i32)r.za] = 0.0;
+            for (i32 q = lane; q < (i32)r.zb; q += 64) col[n + q] = 0.0;
+            EaGatherEnt gb = ge;                    // the batch's entries, lane by lane
+            EgBatch b = es_batch(gb, e0, e1, rel, U0, U1);
+            double av[EG_AL] = {};
+            if (na > 0) {
+#pragma unroll
+                for (int k = 0; k < EG_AL; ++k) av[k] = col[arow[k]];
+            }
+            bool seeded = false;
+            for (i64 e = e0; e < e1 || !seeded; e += EG_EB) {
+                // rel and U of the whole batch, clamped (a guarded load would wait for its guard): row r of contributor u goes to front row rl[u][r]
+                const bool thin = eg_nmax(b) <= 64 * EG_CH;
+                i32 tg[EG_EB][EG_CH]; double v[EG_EB][EG_CH];
+                // ... or, with a contributor of more than EG_CH x 64 rows in the batch, of its first trip
+                EsTrip t0 = {}, t1 = {};
+                int cu = 0; i32 crr = 0;
+                const int nbe = (int)min((i64)EG_EB, e1 - e);       // contributors of the batch (every one has a row)
+                if (thin) {
+#pragma unroll
+                    for (int u = 0; u < EG_EB; ++u)
+#pragma unroll
+                        for (int k = 0; k < EG_CH; ++k) {
+                            const i32 ru = max(min(lane + 64 * k, b.n[u] - 1), 0);
+                            tg[u][k] = b.rl[u][ru] - r0; v[u][k] = b.sr[u][ru];
+                        }
+                } else {
+                    es_issue(t0, gb, cu, crr, rel, U0, U1, r0, lane);
+                }
+                if (!seeded) {                      // zeros and the assembled entries into the slice, behind the first batch's loads
+                    eg_put_formed(asm_row, slice, col, av, arow, a0, na, n, lane);
+                    seeded = true;
+                }
+                EaGatherEnt gnb = gb;
+                EgBatch nb = b;
+                if (e + EG_EB < e1) {               // the next batch's entries come while this one is added
+                    gnb = es_entry(ent, e + EG_EB, e1, lane);
+                    nb = es_batch(gnb, e + EG_EB, e1, rel, U0, U1);
+                }
+                __builtin_amdgcn_wave_barrier();
+                if (thin) {
+                    // contributor after contributor (list order); the rows of one contributor are distinct front rows: read all, then write all
+#pragma unroll
+                    for (int u = 0; u < EG_EB; ++u) {
+                        double d[EG_CH];
+#pragma unroll
+                        for (int k = 0; k < EG_CH; ++k) d[k] = slice[tg[u][k]];
+#pragma unroll
+                        for (int k = 0; k < EG_CH; ++k) if (lane + 64 * k < b.n[u]) slice[tg[u][k]] = d[k] + v[u][k];
+                        __builtin_amdgcn_wave_barrier();
+                    }
+                } else {
+                    // each contributor in turn, 4 x 64 rows per trip; the next trip is requested before this one is added
+                    while (t0.rem > 0) {
+                        t1.rem = 0;
+                        if (cu < nbe) es_issue(t1, gb, cu, crr, rel, U0, U1, r0, lane);
+                        double d[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) d[k] = slice[t0.tq[k]];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) if (lane + 64 * k < t0.rem) slice[t0.tq[k]] = d[k] + t0.w[k];
+                        __builtin_amdgcn_wave_barrier();
+                        t0 = t1;
+                    }
+                }
+                b = nb; gb = gnb;
+            }
+            __builtin_amdgcn_wave_barrier();
+            for (i32 q = lane; q < n; q += 64) col[q] = slice[q];
+            __builtin_amdgcn_wave_barrier();
+        }
+        r = rn; rn = rnn; ge = gen; skip = skipn;
+#pragma unroll
+        for (int k = 0; k < EG_AL; ++k) arow[k] = arown[k];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // Front assembly of the LARGE fronts (f >= fa_min_f(), symbolic.cpp): a workgroup FORMS one tile of the panel -- FA_CW = 16 parent
 // columns x <= 256 rows -- in LDS: zero, the entries of S = A D A' + Rd that land in it (the arithmetic of k_assemble), then the
 // children's update matrices in child order (the arithmetic and the order of k_extend_add), and writes the tile to the panel once.
@@ -4557,7 +4709,12 @@ void launch_tasks(hipStream_t st, const DevArrays &a, const Launch &L, const Swe
                 if (e->n_gather > e->n_form)
                     hipLaunchKernelGGL(k_ea_gather<false>, g, dim3(256), (unsigned)(4 * 8 * e->rows), st, a.ea_tasks + L.first, a.ctx, (int)e->rows, (const i64 *)nullptr,
                                        (const unsigned short *)nullptr);
-                if (e->n_form > 0)
+                if (e->n_form > 0 && a.eg_seg && e->s1 > e->s0) {
+                    // ... over the launch's records of the flat segment list (TLPK_EA_SEGLIST): EG_SEG_CHUNK consecutive records per wave, four waves per workgroup
+                    const i64 nwave = (e->s1 - e->s0 + EG_SEG_CHUNK - 1) / EG_SEG_CHUNK;
+                    hipLaunchKernelGGL(k_ea_seglist, dim3((unsigned)((nwave + 3) / 4)), dim3(256), (unsigned)(4 * 8 * e->rows), st, a.eg_seg, e->s0, e->s1, (int)EG_SEG_CHUNK,
+                                       (int)e->rows, a.ctx.Lval, (const double *)a.ctx.U0, (const double *)a.ctx.U1, a.ctx.rel, a.ctx.eg_ent, a.eg_asm_row, a.ctx.front_skip);
+                } else if (e->n_form > 0)
                     hipLaunchKernelGGL(k_ea_gather<true>, g, dim3(256), (unsigned)(4 * 8 * e->rows), st, a.ea_tasks + L.first, a.ctx, (int)e->rows, a.eg_asm_ptr, a.eg_asm_row);
                 plain = e->n_plain > 0;
             }

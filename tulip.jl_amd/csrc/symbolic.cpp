@@ -1471,6 +1471,45 @@ int analyse_rank(Symbolic &S, const Options &opt) {
             S.ea_form = std::move(form);
         }
     }
+    // ---- 14''. flat segment list of the formed fronts' panel columns (TLPK_EA_SEGLIST = 0 | 1, unset = 1).  k_ea_gather<true> reaches a
+    // segment through task -> FrontDesc -> eg_base -> eg_col -> eg_ptr / asm_ptr, a chain of dependent loads per column; the list spells every segment out --
+    // where it is stored, its rows, its contributors, its assembled rows, what its column zeroes besides -- in the order the launches, their tasks, the tasks'
+    // columns and the columns' segments come, so that a wave of k_ea_seglist walks a run of consecutive records and fetches ahead across segments and columns.
+    // Per launch with such tasks the range of its records.  Nothing else moves; 0 builds no list and keeps the task-driven kernel.
+    S.ea_seg.clear(); S.ea_seg_launch.clear();
+    {
+        bool on = true;
+        if (const char *e = std::getenv("TLPK_EA_SEGLIST")) on = std::atoi(e) != 0;
+        if (on && !S.ea_form.empty()) {
+            const i32 cap = S.ea_gather_cap;
+            for (const Launch &L : S.factor_launches) {
+                if (L.kind != LK_EXTEND_ADD || L.count <= 0) continue;
+                const i64 s0 = (i64)S.ea_seg.size();
+                for (i64 k = L.first; k < L.first + L.count; ++k) {
+                    const EaTask &t = S.ea_tasks[(size_t)k];
+                    const FrontDesc &w = S.fronts[(size_t)t.front];
+                    if (!S.ea_form[(size_t)t.front] || t.br1 != 0 || t.j0 >= w.ns) continue;        // (kernels.hip: ea_task_gathered, ea_task_formed)
+                    if (w.lda - w.f > UINT16_MAX) return fail(S, TLPK_INTERNAL, "formed front: padding rows do not fit a segment record");
+                    const i64 *colseg = S.ea_gather_col.data() + S.ea_gather_base[(size_t)t.front];
+                    for (i32 tc = t.j0; tc < t.j1; ++tc) {
+                        const i64 g0 = colseg[tc], g1 = colseg[tc + 1], vrow0 = w.loff + pk_off(w.lda, tc);
+                        for (i64 g = g0; g < g1; ++g) {
+                            const i32 r0 = tc + (i32)(g - g0) * cap, n = std::min(cap, w.f - r0);
+                            const i64 e0 = S.ea_gather_ptr[(size_t)g], ne = S.ea_gather_ptr[(size_t)g + 1] - e0;
+                            const i64 a0 = S.ea_gather_asm_ptr[(size_t)g], na = S.ea_gather_asm_ptr[(size_t)g + 1] - a0;
+                            if (ne > INT32_MAX) return fail(S, TLPK_TOO_LARGE, "formed front: a segment has more than 2^31 contributors");
+                            // (k_ea_seglist walks a batch's contributors with a cursor that relies on every one having a row: step 13a' makes no other)
+                            for (i64 q = e0; q < e0 + ne; ++q)
+                                if (S.ea_gather_ent[(size_t)q].n < 1) return fail(S, TLPK_INTERNAL, "formed front: a contributor without rows in the segment list");
+                            S.ea_seg.push_back(EaSeg{vrow0 + r0, e0, a0, t.front, r0, (i32)ne, (uint16_t)n, (uint16_t)na, (uint16_t)(g == g0 ? (tc & 63) : 0),
+                                                     (uint16_t)(g + 1 == g1 ? w.lda - w.f : 0), 0});
+                        }
+                    }
+                }
+                if ((i64)S.ea_seg.size() > s0) S.ea_seg_launch.push_back(EaSegLaunch{L.first, s0, (i64)S.ea_seg.size()});
+            }
+        }
+    }
     pt.mark(nullptr);
     return TLPK_OK;
 }

@@ -256,6 +256,9 @@ std::vector<EaGatherLaunch> eg_count_launches(const Symbolic &S) {
             }
             else g.n_plain++;
         }
+        // (its records of the flat segment list, TLPK_EA_SEGLIST: ascending `first` there too)
+        const auto sl = std::lower_bound(S.ea_seg_launch.begin(), S.ea_seg_launch.end(), L.first, [](const EaSegLaunch &x, i64 first) { return x.first < first; });
+        if (sl != S.ea_seg_launch.end() && sl->first == L.first) { g.s0 = sl->s0; g.s1 = sl->s1; }
         if (g.n_gather > 0) out.push_back(g);
     }
     return out;
@@ -404,6 +407,8 @@ int upload_all(tlpk_handle *h) {
             // formed fronts (bit EG_FORMED of the per-front byte): the rows of the assembled entries per segment
             { i64 *p; UP(p, S.ea_gather_asm_ptr); d.eg_asm_ptr = p; }
             { uint16_t *p; UP(p, S.ea_gather_asm_row); d.eg_asm_row = p; }
+            // their flat segment list (TLPK_EA_SEGLIST): k_ea_seglist takes the formed panel tasks' place in the launches that have records
+            if (!S.ea_seg.empty()) { EaSeg *p; UP(p, S.ea_seg); d.eg_seg = p; }
         }
     }
     UP(d.update_tasks, S.update_tasks); UP(d.reduce_tasks, S.reduce_tasks);
@@ -3115,6 +3120,11 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
     else if (w == "ea_form") tmp.assign(S.ea_form.begin(), S.ea_form.end());
     else if (w == "ea_gather_asm_ptr") tmp = S.ea_gather_asm_ptr;
     else if (w == "ea_gather_asm_row") tmp.assign(S.ea_gather_asm_row.begin(), S.ea_gather_asm_row.end());
+    // flat segment list of the formed fronts' panel columns (TLPK_EA_SEGLIST; empty: not built): (front, dst, n, r0, e0, ne, a0, na, za, zb) per record;
+    // (first task, s0, s1) per extend-add launch that has records
+    else if (w == "ea_seg_rec") { for (auto &r : S.ea_seg) for (i64 v : {(i64)r.front, r.dst, (i64)r.n, (i64)r.r0, r.e0, (i64)r.ne, r.a0, (i64)r.na, (i64)r.za, (i64)r.zb}) tmp.push_back(v); }
+    else if (w == "ea_seg_chunk") tmp.assign(1, EG_SEG_CHUNK);         // consecutive records per wave of k_ea_seglist
+    else if (w == "ea_seg_launch") { for (auto &l : S.ea_seg_launch) { tmp.push_back(l.first); tmp.push_back(l.s0); tmp.push_back(l.s1); } }
     else if (w == "front_eatab") field([](const FrontDesc &f) { return f.eatab; });
     else if (w == "children") from32(S.children);
     else if (w == "depth") from32(S.depth);

@@ -51,13 +51,19 @@ struct SweepArgs {
 
 // an LK_EXTEND_ADD launch as its two kernels see it, counted at create (tlpk_api.cpp: eg_count_launches): tasks of k_ea_gather / of k_extend_add,
 // rows of a wave's LDS slice = the longest segment k_ea_gather holds in the launch; n_form of the n_gather tasks are panel-part tasks of formed fronts
-struct EaGatherLaunch { i64 first; i32 n_gather, n_plain, rows, n_form; };
+// [s0, s1): the launch's records of the flat segment list (Symbolic::ea_seg; empty range: its formed panel tasks, if any, stay on k_ea_gather<true>)
+struct EaGatherLaunch { i64 first; i32 n_gather, n_plain, rows, n_form; i64 s0 = 0, s1 = 0; };
+// consecutive records of that list per wave of k_ea_seglist (measured on C4: 4, 8, 16 and 32 within the noise of each other)
+constexpr int EG_SEG_CHUNK = 8;
 
 struct DevArrays {
     DevCtx ctx{};
     const EaGatherLaunch *eg_launch = nullptr; i64 n_eg_launch = 0;   // host memory of the handle, ascending `first`; nullptr: no front is gathered
     // formed fronts (Symbolic::ea_gather_asm_*): eg_asm_row[eg_asm_ptr[segment] ..] = the rows, from the segment's first row, of the entries k_assemble stores in it
     const i64 *eg_asm_ptr = nullptr; const unsigned short *eg_asm_row = nullptr;
+    // flat segment list of the formed fronts' panel columns (TLPK_EA_SEGLIST; Symbolic::ea_seg): an argument of k_ea_seglist, like eg_asm_* not a field of
+    // DevCtx; nullptr: k_ea_gather<true> does them
+    const EaSeg *eg_seg = nullptr;
     i64 m = 0, n = 0;                         // m: order of the factored matrix (K2: n + m; dense columns: m + k), n: columns of the stored matrix
     i64 mu = 0;                               // rows of A as the caller sees them (= m for plain K1): the residual kernels of the refinement
     // K1 with dense columns (tlpk_options.dense_cols): sparse_col[j] = 1 for a column formed into A_s D_s A_s', 0 for a dense one;

@@ -89,6 +89,13 @@ struct EaGatherEnt { i64 src, rel; i32 n, child; };
 static_assert(sizeof(EaGatherEnt) == 24, "EaGatherEnt layout");
 constexpr int EG_UBUF_BIT = 62;
 constexpr int EG_CAP_MAX = 1024;   // rows of a segment at most = a wave's LDS slice: 4 waves x 1024 doubles = 32 KB per workgroup, four workgroups per CU
+// flat segment list of the formed fronts' panel columns (k_ea_seglist; symbolic.cpp step 14''): one record per (front, panel column, segment), all the kernel
+// needs to know of the segment without FrontDesc, eg_base, eg_col, eg_ptr or asm_ptr.  dst = offset in Lval of the segment's first stored double (row r0 of its
+// column), n rows; contributors ea_gather_ent[e0 .. e0 + ne), assembled rows ea_gather_asm_row[a0 .. a0 + na); za = stored rows above the diagonal inside the
+// 64-column slice, zeroed at dst - za .. dst (the first segment of a column), zb = padding rows [f, lda), zeroed at dst + n .. (the last one)
+struct alignas(16) EaSeg { i64 dst, e0, a0; i32 front, r0, ne; uint16_t n, na, za, zb; i32 pad; };
+static_assert(sizeof(EaSeg) == 48, "EaSeg layout");
+struct EaSegLaunch { i64 first, s0, s1; };   // the records [s0, s1) belong to the LK_EXTEND_ADD launch whose tasks start at `first`
 struct SolveTask { i32 front, k0, nb, row0, slot, nslot, pad0, pad1; };
 // sweep items (LK_FWD_SWEEP): k0/nb = first row / rows of the chunk (<= SWEEP_NB pivot rows or <= SOLVE_NB rows below),
 //   slot = 1 pivot block (solve + publish) | 0 rows below, nslot = SWEEP_NB-wide solved blocks to consume (0 .. nslot-1);
@@ -199,6 +206,8 @@ struct Symbolic {
     // the panel is not zero-filled (empty: no front is formed).  Per segment g of a panel column of a formed front, the entries of S that k_assemble stores in
     // it: ea_gather_asm_row[asm_ptr[g] .. asm_ptr[g + 1]) = their rows, counted from the segment's first row, ascending (no entries for every other segment)
     std::vector<unsigned char> ea_form; std::vector<i64> ea_gather_asm_ptr; std::vector<uint16_t> ea_gather_asm_row;
+    // flat segment list of the formed fronts' panel columns (step 14'', TLPK_EA_SEGLIST): launch -> front -> column -> segment; empty: k_ea_gather<true> does them
+    std::vector<EaSeg> ea_seg; std::vector<EaSegLaunch> ea_seg_launch;
     std::vector<i64> gth_ptr, gth_src;     // forward gather lists: front row (rowoff + t) -> children's uc entries, in child order
     std::vector<i32> children;             // concatenated child lists
     std::vector<i32> depth;                // depth of each front (roots = 0)
