@@ -412,7 +412,15 @@ int tlpk_get_perm(const tlpk_handle *h, int64_t *perm /*m, 0-based, perm[new] = 
  *   "launch_meta"  (stream group, side, pad) of every entry of "factor_launches", then of "fwd_launches", then of "bwd_launches"
  *   "zero_tasks"   (front, first column) of every 64-column panel slice the zero-fill clears
  *   "zero_small"   the fronts whose whole panel one wave clears
- *   "singles"      panel offsets, inverted-diagonal offsets and columns of the isolated 1 x 1 fronts, concatenated; then n_zero_lower and spart_len */
+ *   "singles"      panel offsets, inverted-diagonal offsets and columns of the isolated 1 x 1 fronts, concatenated; then n_zero_lower and spart_len
+ * Launch geometry of a dense-matrix handle (tlpk_create_dense; tests/test_dense_shapes.py), six entries, all zero on any other handle:
+ *   "dense_geometry"  [0] syrk_split   K (= n) parts per 128 x 128 tile of A D A' (1: the tiles go straight into the panel, no reduction)
+ *                     [1] syrk_kc      columns per part, a multiple of 16: part p = columns [p kc, min(n, (p + 1) kc))
+ *                     [2] gemv_chunks  column chunks of xi_p + A (D .* xi_d), whose partial sums are added in chunk order (>= 1)
+ *                     [3] gemv_cw      columns per chunk: chunk c = columns [c cw, min(n, (c + 1) cw))
+ *                     [4] dense_lda    leading dimension of the device copy of A (m rounded up to 16; the padding rows are zero)
+ *                     [5] panel_lda    leading dimension of the one front's packed panel (= "front_lda"[0])
+ *                     -- the values the kernels receive: a device handle is created from these numbers, not from a second computation */
 int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, int64_t cap);
 int64_t tlpk_symbolic_get_f64(const tlpk_handle *h, const char *what, double *buf, int64_t cap);
 /* Copy the numeric factor panels (device -> host), nnzL_stored doubles.  Layout: front s (symbolic arrays front_f, front_ns, front_loff,

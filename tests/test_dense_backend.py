@@ -76,6 +76,10 @@ def test_analyse_only_handle(m, n):
     for name in ("s_target", "s_diag_row", "pair_j", "s_rowidx"):
         assert len(kkt.symbolic(name)) == 0, name
     assert len(_lib.symbolic_array_f64(kkt._h, "pair_w")) == 0
+    # the launch geometry of the dense kernels (tests/test_dense_shapes.py holds its rule): K parts x columns cover n, so do the chunks; the two leading dimensions
+    split, kc, chunks, cw, dlda, plda = kkt.symbolic("dense_geometry").tolist()
+    assert kc % 16 == 0 and (split - 1) * kc < n <= split * kc and (chunks - 1) * cw < n <= chunks * cw
+    assert dlda == (m + 15) // 16 * 16 and plda == kkt.symbolic("front_lda")[0]
     th, rp, rd, xp, xd = ipm_like_data(m, n, 0)
     assert _lib.lib().tlpk_update(kkt._h, _lib.as_pd(th), _lib.as_pd(rp), _lib.as_pd(rd)) == _lib.NO_DEVICE
     # a sparse handle of the same (tiny) matrix reports flops_syrk = 0
@@ -141,7 +145,7 @@ def test_leading_dimension_does_not_change_the_analysis():
     k1 = tk.setup(big[:m], tk.K1(), tk.DenseBackend(device=-1))
     assert k1.A.base is big or k1.A is big[:m] or np.shares_memory(k1.A, big)          # passed as it is, not copied
     for name in ("perm", "front_f", "front_ns", "front_lda", "front_loff", "factor_launches", "fwd_launches", "bwd_launches", "potrf_tasks",
-                 "trsm_tasks", "update_tasks", "reduce_tasks", "chain_items", "fwd_sweep_tasks", "bwd_sweep_tasks"):
+                 "trsm_tasks", "update_tasks", "reduce_tasks", "chain_items", "fwd_sweep_tasks", "bwd_sweep_tasks", "dense_geometry"):
         assert (k0.symbolic(name) == k1.symbolic(name)).all(), name
     # a C-ordered array is copied once into column-major storage
     k2 = tk.setup(np.ascontiguousarray(A), tk.K1(), tk.DenseBackend(device=-1))
@@ -187,10 +191,21 @@ class DenseEmulator(Emulator):
         A = np.asarray(self.kkt.A)
         self.D = 1.0 / (theta + regP)
         self.regD = np.asarray(regD, dtype=float)
-        K = (A * self.D) @ A.T + np.diag(self.regD)
         self.Lval[:] = np.nan                                # nothing may rely on a zero-fill
         self._P = {}
         assert len(self.f) == 1 and self.f[0] == self.ns[0] == self.m
+        K = self.form_panel(A)
+        self._svals = {}; self._upper_pending = {}; self.U = {}; self.fail_col = None
+        self.chain_cnt[:] = 0
+        for s_ in np.nonzero(self.single & (self.local != 0))[0]:      # k_single_factor (m = 1)
+            self.Lval[self.loff[s_]] = np.sqrt(self.Lval[self.loff[s_]])
+        self._resume = self._run(self.factor_launches, True)
+        self.update_finish()
+        return K
+
+    def form_panel(self, A):
+        """What stands for k_dense_syrk (tests/test_dense_shapes.py puts the device's tiles, K parts and slabs here): every stored entry is written."""
+        K = (A * self.D) @ A.T + np.diag(self.regD)
         lda, loff = int(self.lda[0]), int(self.loff[0])
         for c in range(self.m):
             top = (c >> 6) << 6                              # first stored row of the column's 64-column slice
@@ -198,12 +213,6 @@ class DenseEmulator(Emulator):
             self.Lval[a + top: a + c] = 0.0
             self.Lval[a + c: a + self.m] = K[c:, c]
             self.Lval[a + self.m: a + lda] = 0.0
-        self._svals = {}; self._upper_pending = {}; self.U = {}; self.fail_col = None
-        self.chain_cnt[:] = 0
-        for s_ in np.nonzero(self.single & (self.local != 0))[0]:      # k_single_factor (m = 1)
-            self.Lval[self.loff[s_]] = np.sqrt(self.Lval[self.loff[s_]])
-        self._resume = self._run(self.factor_launches, True)
-        self.update_finish()
         return K
 
 
@@ -337,8 +346,8 @@ def test_contracts_of_every_handle(m, n):
         tk.update(kkt, th, rp, np.full(m, -2.0 * lam))
     assert kkt.stats()["fail_col"] >= 0
     check_factor_and_solution(A, kkt, "mid")
-    # a view into a taller column-major array (lda > m): bit-identical to the packed copy
-    big = np.zeros((m + 5, n), order="F"); big[:m] = A
+    # a view into a taller column-major array (lda > m) whose rows beyond m are NaN (a copy that read them would show): bit-identical to the packed copy
+    big = np.full((m + 5, n), np.nan, order="F"); big[:m] = A
     kv = gpu_setup(big[:m])
     tk.update(kv, th, rp, rd)
     assert np.array_equal(kv.factor_panels(), p0, equal_nan=True)

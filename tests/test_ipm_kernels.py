@@ -427,6 +427,39 @@ def test_residuals_on_a_dense_matrix_handle(kind):
         drv.close()
 
 
+# the cuts of the two GEMV kernels (tests/test_dense_shapes.py names them): one row and one column; m = 2 under n mod 4 = 1; a second trip of
+# k_dense_gemv_t's lane loop with an odd m, n = 3 (one live wave short of a workgroup); the second 512-row workgroup of k_dense_gemv_n with 8 live
+# threads, 2 chunks of 9 | 8; 964 chunks of 17 columns, the last of 14
+DENSE_GEMV_SHAPES = [(1, 1), (2, 17), (129, 3), (513, 17), (16, 16385)]
+
+
+@pytest.mark.parametrize("kind", DRIVERS)
+@pytest.mark.parametrize("m,n", DENSE_GEMV_SHAPES, ids=[f"{m}x{n}" for m, n in DENSE_GEMV_SHAPES])
+def test_residuals_on_a_dense_matrix_handle_at_the_gemv_cuts(m, n, kind):
+    """The same branch (D == nullptr in k_dense_gemv_t / k_dense_gemv_n) at the shapes where those kernels change behaviour, m > n among them."""
+    rng = np.random.default_rng(100 * m + n)
+    sparse = make_lp(m, n, 13, per_col=3)
+    Ad = sparse.A.toarray() + 0.1 * rng.standard_normal((m, n))
+    x0 = np.where(np.isfinite(sparse.l), sparse.l, np.where(np.isfinite(sparse.u), sparse.u - 3.0, 0.0)) + 1.0
+    x0 = np.where(np.isfinite(sparse.u), np.minimum(x0, sparse.u - 0.1), x0)
+    lp = ir.LPData(Ad, Ad @ x0, sparse.c, sparse.l, sparse.u, dense=True)
+    drv = Driver(kind, lp, dense=True)
+    out = np.zeros(16)
+    try:
+        for state in ("start", "it3"):
+            tab = Table(kind, f"d{m}x{n}"[:9], state)
+            drv.goto(state)
+            tau = 0.77 * drv.loop.tau
+            pre = drv.read()
+            drv.ok(drv.L.tlpk_ipm_residuals(drv.h, tau, pd(out)))
+            rep = ir.Report("residuals")
+            ir.check_residuals(lp, pre, drv.read(), tau, out, rep)
+            tab.add("residuals", rep)
+            tab.done()
+    finally:
+        drv.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # batched
 # ---------------------------------------------------------------------------------------------------------------------------------

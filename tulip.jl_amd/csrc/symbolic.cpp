@@ -1748,6 +1748,7 @@ int analyse_dense_matrix(Symbolic &S, i64 m64, i64 n64) {
     i64 chunks = std::max<i64>(1, std::min<i64>(1024 / rowblocks, (n64 + 15) / 16));
     const i64 cw = std::max<i64>(1, (n64 + chunks - 1) / chunks);
     S.gemv_chunks = std::max<i64>(1, (n64 + cw - 1) / cw);
+    S.gemv_cw = std::max<i64>(1, (n64 + S.gemv_chunks - 1) / S.gemv_chunks);      // (what the kernels get: the width that spreads n over the chunks kept)
     return TLPK_OK;
 }
 

@@ -278,7 +278,7 @@ int upload_all(tlpk_handle *h) {
         d.syrk_split = S.syrk_split;
         d.syrk_kc = S.syrk_kc;
         d.gemv_chunks = S.gemv_chunks;
-        d.gemv_cw = std::max<i64>(1, (S.n + S.gemv_chunks - 1) / S.gemv_chunks);
+        d.gemv_cw = S.gemv_cw;
         if ((rc = dev_alloc(h, &d.gemv_part, 2 * S.gemv_chunks * d.dlda)) != TLPK_OK) return rc;
     }
     UP(d.Ap, S.Ap); UP(d.Ai, S.Ai); UP(d.Ax, S.Ax);
@@ -3210,6 +3210,12 @@ int64_t tlpk_symbolic_get(const tlpk_handle *h, const char *what, int64_t *buf, 
             }
     }
     else if (w == "polish_bytes") tmp.assign(1, h->polish.bytes);
+    // launch geometry of a dense-matrix handle (analyse_dense_matrix), as the kernels of dense_kernels.hip receive it: K parts of the SYRK and columns per part,
+    // column chunks of k_dense_gemv_n and columns per chunk, leading dimension of the device copy of A, leading dimension of the panel.  Zeros on other handles
+    else if (w == "dense_geometry") {
+        if (S.dense_matrix) tmp = {(i64)S.syrk_split, S.syrk_kc, S.gemv_chunks, S.gemv_cw, dense_lda(S.m), (i64)S.fronts[0].lda};
+        else tmp.assign(6, 0);
+    }
     else if (w == "singles") {
         tmp = S.single_loff; tmp.insert(tmp.end(), S.single_dinvoff.begin(), S.single_dinvoff.end()); tmp.insert(tmp.end(), S.single_col.begin(), S.single_col.end());
         tmp.push_back(S.n_zero_lower); tmp.push_back(S.spart_len);

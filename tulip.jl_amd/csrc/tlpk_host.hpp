@@ -178,6 +178,7 @@ struct Symbolic {
     i32 syrk_split = 1;                  // K (= n) parts per tile of the lower triangle (1: the tiles go straight into the panel)
     i64 syrk_kc = 16;                    // columns per part, a multiple of 16
     i64 gemv_chunks = 0;                 // column chunks of k_dense_gemv_n (partial sums per chunk, summed in chunk order)
+    i64 gemv_cw = 1;                     // columns per chunk, as the kernel receives them: ceil(n / gemv_chunks), at least 1
     double flops_syrk = 0;               // n m (m + 1): 2 flops per product of the lower triangle
     std::vector<i64> dense_cols;
     // A, CSC and CSR (0-based, int32 indices); csr_pos[q] = CSC position of the CSR entry q
